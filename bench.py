@@ -56,8 +56,39 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dump-gemm-launches", default=None, metavar="FILE", help="write every profiled GEMM-family launch (ms, M, N, K, flags, z, variant) in "
                     "issue order as JSON: the input of tools/gemm_classes.py (profiles/r6_gemm_classes.txt)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(float32 / float64; arrays over 2 Mi elements as a fixed seeded sample): two builds compared output for output")
     ap.add_argument("--cpu-batch", type=int, default=4)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_ELEMS = 1 << 21      # per array (8 MB as float32); a larger output is written as this many elements at fixed seeded positions
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy: float64 stays float64, everything else becomes float32.  An array of more than
+    DUMP_MAX_ELEMS elements is flattened and sampled at positions drawn from a generator seeded by its size alone, so two runs (or two
+    builds) with the same arguments write the same positions."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    out, total = {}, 0
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(t.numel()))
+            t = t.reshape(-1)[idx.sort().values.to(t.device)]
+        a = t.cpu().numpy()
+        out[name] = a
+        total += a.nbytes
+    assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def launch_ranks(args):
@@ -191,6 +222,8 @@ def bench_eval(args, model, dev, world, rank):
         res[name] = {"ms_per_batch": dt * 1e3, "utterances_per_s": B / dt}
         outs[name] = out.float().cpu()
     model_linear.SCORE_FP32 = True
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logp_" + k: v for k, v in outs.items()})
     d = (outs["bf16"] - outs["fp32"]).abs()
     line = {"metric": "scoring utterances/sec (64600-sample clips)", "value": res["fp32"]["utterances_per_s"], "unit": "utterances/s", "n_gpus": 1,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["fp32"]["ms_per_batch"], "higher_is_better": True, "scaling": "weak",
@@ -272,10 +305,14 @@ def main():
         from scl_amd.datautils_common import default_rawboost_args
         rb_args = default_rawboost_args()
 
+    last_out = {} if args.dump_outputs else None      # the tensors the last step handed back (detached: no autograd graph kept alive)
+
     def step():
         xs = augment.rawboost_batch(x, rb_args, args.rawboost, 16000, sampler="fast") if args.rawboost else x
         out, feats, emb = model(xs, *fwd_extra)
         losses = model.loss(out, feats, emb, y, conf)
+        if last_out is not None:
+            last_out.update(out=out.detach(), feats=feats.detach(), emb=emb.detach(), **{"loss_" + k: v.detach() for k, v in losses.items()})
         total = None
         for v in losses.values():
             total = v if total is None else total + v
@@ -328,6 +365,9 @@ def main():
     if rank != 0:
         torch.distributed.destroy_process_group()
         return
+    if args.dump_outputs:
+        # rank 0's outputs of the last timed step, its total loss, and the weights / gradients AdamW left behind (replicated over ranks)
+        dump_outputs(args.dump_outputs, dict(last_out, loss_total=last.detach(), params=model.P.flat[g_lo:g_hi], grads=model.P.grad[g_lo:g_hi]))
     utt_s = world * B * args.steps / dt
     flop_per_utt = FLOP_PER_UTT_STEP_64000 if (L == 64000 and not args.tiny) else None
     achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0

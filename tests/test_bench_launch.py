@@ -132,3 +132,52 @@ def test_bench_eval_mode_times_both_scoring_precisions(dev):
     assert line["metric"].startswith("scoring utterances/sec") and line["dtype"] == "f32" and line["config"]["samples"] == 16000
     assert line["fp32"]["utterances_per_s"] > 0 and line["bf16"]["utterances_per_s"] > 0 and line["value"] == line["fp32"]["utterances_per_s"]
     assert line["bf16_vs_fp32"]["max_rel_to_largest"] < 5e-2 and 0.0 <= line["bf16_vs_fp32"]["argmax_agree"] <= 1.0
+
+
+def test_steps_below_one_is_refused():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, (r.returncode, r.stderr)
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_large_ones_at_fixed_positions(tmp_path):
+    """bench.dump_outputs: bf16 / float32 become float32, float64 stays; an array over DUMP_MAX_ELEMS is written as that many elements at
+    positions that depend on its size only (two dumps of the same tensor are identical), and they are positions of the flat array."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 12345, dtype=torch.float32)
+    arrays = {"small": torch.ones(3, 2, dtype=torch.bfloat16), "loss": torch.tensor(0.25, dtype=torch.float64), "big": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "loss.npy", "small.npy"]
+    assert a["small"].dtype == np.float32 and a["small"].shape == (3, 2) and a["loss"].dtype == np.float64 and a["loss"] == 0.25
+    assert a["big"].shape == (bench.DUMP_MAX_ELEMS,) and np.all(np.diff(a["big"]) >= 0) and a["big"].max() < big.numel()
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_MAX_BYTES + 1024
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_two_runs_agree(dev, tmp_path):
+    """`--dump-outputs DIR` after the timed steps: the last step's log-probs, features, embeddings, losses and a sample of the weights and
+    gradients AdamW left.  Same arguments -> same inputs, so two runs agree output for output; `--steps` is the number of timed steps."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--tiny", "--steps", "3", "--warmup", "1", "--batch", "4",
+                            "--samples", "16000", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, env=env, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)})
+    a, b = dumps
+    assert {"out", "feats", "emb", "loss_total", "params", "grads"} <= set(a) and set(a) == set(b)
+    assert a["out"].shape == (4, 2) and a["emb"].shape[0] == 4 and a["feats"].shape[0] == 4
+    assert abs(float(a["loss_total"]) - line["final_loss"]) <= 1e-6 * abs(line["final_loss"])
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].shape == b[k].shape and np.isfinite(a[k]).all(), k
+        rel = np.linalg.norm(a[k] - b[k]) / max(np.linalg.norm(b[k]), 1e-30)
+        assert rel < 1e-4, (k, rel)
