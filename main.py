@@ -391,8 +391,12 @@ def main(argv=None):
     repeat = args.padding_type == "repeat"
     # RawBoost parameter draws of the pack builder: "fast" = every builder thread's own numpy Generator, batched closed-form filter design,
     # ISD positions without a 64000-element permutation per clip (same distributions; scl_amd/augment.py); SCL_PACK_SAMPLER=reference =
-    # the reference's draw-for-draw order on the global np.random stream (what the pack goldens pin; 0.5 ms more host time per clip)
+    # the reference's draw-for-draw order on the global np.random stream (what the pack goldens pin; 0.5 ms more host time per clip), i.e.
+    # SCL_PACK_SAMPLER=reference restores the reference's global-stream draws.  The fast sampler is seeded with [--seed, rank]: each rank
+    # and each --seed draws its own notch filters, ISD positions, SNRs and noise (unseeded, every rank drew the same ones)
     args.rawboost_sampler = os.environ.get("SCL_PACK_SAMPLER", "fast")
+    from scl_amd import augment
+    augment.seed_fast_sampler([args.seed, rank])
     d_label_trn, file_train = genList(dir_meta=proto, is_train=True, is_eval=False, is_dev=False)
     print("no. of training trials", len(file_train))
     train_set = Dataset_for(args, list_IDs=file_train, labels=d_label_trn, base_dir=args.database_path + "/", algo=args.algo,

@@ -149,6 +149,125 @@ def test_fast_sampler_statistics():
     assert all(len(np.unique(p)) == len(p) for p, _ in isd)
 
 
+# ---- the fast sampler's laws, exactly (what main.py trains with and bench.py times) --------------------------------------------------
+# Each law is checked against its analytic distribution on ~1e4 draws from a fixed seed (deterministic); the p-value floor 1e-4 is far
+# below what a correct sampler reaches at these seeds and far above what a wrong law reaches at this sample size.
+def _fast_args():
+    from scl_amd.datautils_common import default_rawboost_args
+    return default_rawboost_args()
+
+
+def _freqz_peak_db(b):
+    """max over the 512 points of scipy.signal.freqz(b, 1) of |H|, in dB (freqz's grid k pi / 512 = bins 0..511 of a 1024-point FFT)"""
+    return 20.0 * np.log10(np.abs(np.fft.rfft(b, 1024)[:512]).max())
+
+
+def test_fast_notch_params_laws():
+    from scipy import stats
+    from scl_amd import augment
+    a = _fast_args()
+    augment.seed_fast_sampler(101)
+    fc, bw, c, G = augment._fast_notch_params(a, 2000, a.minG, a.maxG)
+    assert fc.shape == bw.shape == c.shape == (2000, 5) and G.shape == (2000,)
+    assert stats.kstest(fc.ravel(), stats.uniform(20, 8000 - 20).cdf).pvalue > 1e-4
+    assert stats.kstest(bw.ravel(), stats.uniform(100, 1000 - 100).cdf).pvalue > 1e-4
+    assert 20 <= fc.min() and fc.max() < 8000 and 100 <= bw.min() and bw.max() < 1000
+    # c = int(U(10, 100)) made odd (RawBoost.py:33-36): 11, 13, ..., 99 with probability 2 / 90 each; 101 (from 100) never
+    odd = np.arange(11, 100, 2)
+    assert len(odd) == 45 and set(np.unique(c)) <= set(odd.tolist()) and (c != 101).all()
+    counts = np.array([(c == v).sum() for v in odd])
+    assert counts.sum() == c.size and stats.chisquare(counts).pvalue > 1e-4
+
+
+def test_fast_lnl_and_ssi_gains_from_the_designed_taps(monkeypatch):
+    """The gain law read back from the taps (max |H| over freqz's 512 bins = 10^(G/20) by construction): the linear branch and SSI at
+    0 dB, the four non-linear branches U(-20, -5) (RawBoost.py:62-65: minG - minBias, maxG - maxBias); tap length sum(c) - 4."""
+    from scipy import stats
+    from scl_amd import augment
+    a = _fast_args()
+    params = []
+    orig = augment._fast_notch_params
+    monkeypatch.setattr(augment, "_fast_notch_params", lambda *q: params.append(orig(*q)) or params[-1])
+    augment.seed_fast_sampler(202)
+    n = 2000
+    taps = augment._fast_lnl(a, n, 16000)
+    assert len(params) == 2 and len(params[0][3]) == n and len(params[1][3]) == 4 * n      # linear branch first, then the non-linear ones
+    assert len(taps) == n and all(len(t) == 5 for t in taps)
+    lin = np.array([_freqz_peak_db(t[0]) for t in taps])
+    nl = np.array([_freqz_peak_db(b) for t in taps for b in t[1:]])
+    assert np.abs(lin).max() < 1e-9, np.abs(lin).max()
+    assert -20 <= nl.min() and nl.max() <= -5 and stats.kstest(nl, stats.uniform(-20, 15).cdf).pvalue > 1e-4
+    csum = np.concatenate([params[0][2], params[1][2]]).sum(axis=1)
+    lens = np.array([len(t[0]) for t in taps] + [len(b) for t in taps for b in t[1:]])
+    assert np.array_equal(lens, csum - 4)
+    params.clear()
+    augment.seed_fast_sampler(203)
+    ssi = augment._fast_ssi(a, n, 16, 16000)
+    assert len(params) == 1 and len(ssi) == n
+    g = np.array([_freqz_peak_db(b) for _, b, _ in ssi])
+    assert np.abs(g).max() < 1e-9, np.abs(g).max()
+    assert np.array_equal(np.array([len(b) for _, b, _ in ssi]), params[0][2].sum(axis=1) - 4)
+
+
+def test_fast_isd_laws():
+    """k = int(L beta / 100), beta ~ U(0, 10): at L = 1000 k is uniform on 0..99; positions distinct and uniform over the clip;
+    f_r = (2 u1 - 1)(2 u2 - 1): |f_r| has CDF z (1 - ln z) on (0, 1], and its sign is + or - with probability 1/2."""
+    from scipy import stats
+    from scl_amd import augment
+    a = _fast_args()
+    augment.seed_fast_sampler(303)
+    L = 1000
+    draws = augment._fast_isd(a, 10000, L)
+    k = np.array([len(p) for p, _ in draws])
+    assert k.min() >= 0 and k.max() <= 99
+    assert stats.chisquare(np.bincount(k, minlength=100)).pvalue > 1e-4
+    assert all(len(np.unique(p)) == len(p) and len(f) == len(p) for p, f in draws)
+    pos = np.concatenate([p for p, _ in draws])
+    assert pos.dtype == np.int32 and pos.min() >= 0 and pos.max() < L
+    assert stats.chisquare(np.bincount(pos // 20, minlength=50)).pvalue > 1e-4
+    fr = np.concatenate([f for _, f in draws])
+    assert fr.dtype == np.float32 and np.abs(fr).max() <= 1
+    z = np.abs(fr[:20000].astype(np.float64))
+    assert stats.kstest(z, lambda t: np.where(t <= 0, 0.0, np.clip(t, 0, 1) * (1 - np.log(np.clip(t, 1e-300, 1))))).pvalue > 1e-4
+    assert stats.binomtest(int((fr > 0).sum()), int((fr != 0).sum())).pvalue > 1e-4
+
+
+def test_fast_ssi_snr_and_noise_laws():
+    from scipy import stats
+    from scl_amd import augment
+    a = _fast_args()
+    augment.seed_fast_sampler(404)
+    ssi = augment._fast_ssi(a, 10000, 10, 16000)
+    snr = np.array([s for _, _, s in ssi])
+    assert 10 <= snr.min() and snr.max() < 40 and stats.kstest(snr, stats.uniform(10, 30).cdf).pvalue > 1e-4
+    noise = np.concatenate([w for w, _, _ in ssi])
+    assert noise.dtype == np.float32 and noise.shape == (100000,)
+    assert stats.kstest(noise.astype(np.float64), stats.norm.cdf).pvalue > 1e-4
+    assert abs(noise.mean()) < 0.015 and abs(noise.std() - 1) < 0.01
+
+
+def test_fast_sampler_seed_is_reproducible_and_depends_on_seed_and_rank():
+    """main.py seeds the fast sampler with [--seed, rank]: the main thread's stream is a function of both."""
+    from scl_amd import augment
+    a = _fast_args()
+
+    def draw(seed):
+        augment.seed_fast_sampler(seed)
+        fc, bw, c, G = augment._fast_notch_params(a, 4, a.minG - 5, a.maxG - 20)
+        (p, f), = augment._fast_isd(a, 1, 4000)
+        return np.concatenate([fc.ravel(), bw.ravel(), c.ravel(), G, p, f])
+
+    base = draw([1, 0])
+    assert np.array_equal(base, draw([1, 0]))
+    np.random.seed(0)                                    # the global legacy stream plays no part
+    assert np.array_equal(base, draw([1, 0]))
+    assert np.array_equal(base[:20], np.random.default_rng(np.random.SeedSequence([1, 0])).uniform(20, 8000, 20))
+    for other in ([1, 1], [2, 0], [0, 1]):
+        d = draw(other)
+        assert d.shape != base.shape or not np.array_equal(d, base), other
+        assert not np.array_equal(d[:20], base[:20]), other
+
+
 def test_fairseq_checkpoint_reader_survives_missing_packages(tmp_path):
     """pretrained/xlsr2_300m.pt is a fairseq checkpoint: {'model': tensors, 'cfg': {'model': <omegaconf / dataclass object>}}.
     The reader must work without fairseq / omegaconf installed: classes that cannot be imported become inert stubs, tensors and
