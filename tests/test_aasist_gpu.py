@@ -297,8 +297,10 @@ def test_hip_backend_matches_the_reference_golden(dev, case, tag):
 
 
 def test_full_size_aasist_step_at_batch_64(dev):
-    """BASELINE configs[3] as one rank sees it: XLS-R-300M encoder + AASIST back-end, 64 x 64000-sample clips.  The CPU oracle cannot
-    run this size in test time, so the checks are the size-independent ones: (1) in eval mode (BatchNorm on running statistics) every
+    """BASELINE configs[3] as one rank sees it: XLS-R-300M encoder + AASIST back-end, 64 x 64000-sample clips.  The CPU oracle of the
+    XLS-R encoder cannot run this size in test time, so the checks here are the size-independent ones; the back-end alone is compared
+    with the float64 oracle at this batch (outputs, every gradient, every BatchNorm buffer, two steps) by
+    tests/test_backends_train_gpu.py::test_aasist_backend_matches_float64_oracle.  Here: (1) in eval mode (BatchNorm on running statistics) every
     utterance is independent of its batch, so rows 0-3 of the batch-64 forward reproduce the batch-4 forward, whose pieces the tests
     above pin to the reference; (2) a train step at this size gives finite losses in the band of a seeded-random-init model and
     finite gradients on every trainable element; (3) every BatchNorm of the back-end saw exactly one batch (per-rank statistics:
