@@ -149,3 +149,14 @@ def forward(sd, args, x_ssl, bio, bio_lengths, dropout_masks=None):
         b = torch.cat((emb, s), 1)                                                      # :333
     logp = torch.log_softmax(F.linear(b, sd["fc2.weight"], sd["fc2.bias"]), dim=1)      # :336-338
     return logp, feats, b
+
+
+def forward_chunked(sd, args, x_ssl, bio, bio_lengths, dropout_masks=None, chunk=32):
+    """forward() over consecutive groups of `chunk` utterances, concatenated.  Every utterance is independent in forward() (no
+    BatchNorm; the mean over T, the masks and the bio encoder are per utterance), so this changes nothing but the memory: the
+    attention scores alone are [B, n_heads, L, L]."""
+    outs = []
+    for i in range(0, x_ssl.shape[0], chunk):
+        masks = None if dropout_masks is None else [m[i:i + chunk] for m in dropout_masks]
+        outs.append(forward(sd, args, x_ssl[i:i + chunk], bio[i:i + chunk], bio_lengths[i:i + chunk], masks))
+    return tuple(torch.cat(t) for t in zip(*outs))

@@ -103,24 +103,25 @@ def maxrel(got, ref):
 
 
 @contextlib.contextmanager
-def kink_counter(counts):
-    """Counts, per activation function, the pre-activations within KINK_REL x RMS of zero of every F.selu / F.relu call inside."""
-    orig = {n: getattr(F, n) for n in ("selu", "relu")}
+def kink_counter(counts, sites=((F, "selu"), (F, "relu"))):
+    """Counts, per activation function, the pre-activations within KINK_REL x RMS of zero of every call inside of the (module,
+    function name) sites (default: F.selu / F.relu)."""
+    orig = {(m, n): getattr(m, n) for m, n in sites}
 
-    def wrap(n):
+    def wrap(m, n):
         def f(x, *a, **kw):
             with torch.no_grad():
                 rms = x.detach().pow(2).mean().sqrt()
                 counts[n] = counts.get(n, 0) + int((x.detach().abs() < KINK_REL * rms).sum())
-            return orig[n](x, *a, **kw)
+            return orig[(m, n)](x, *a, **kw)
         return f
-    for n in orig:
-        setattr(F, n, wrap(n))
+    for m, n in orig:
+        setattr(m, n, wrap(m, n))
     try:
         yield counts
     finally:
-        for n, f in orig.items():
-            setattr(F, n, f)
+        for (m, n), f in orig.items():
+            setattr(m, n, f)
 
 
 class Report:
