@@ -356,6 +356,9 @@ int scl_softmax_fwd(const float* S, void* P, int64_t R, int T, int ldS, int Tp, 
 int scl_softmax_bwd(const void* P, const float* dP, void* dS, int64_t R, int T, int lddP, int Tp, void* stream);
 /* the forward with f32 probabilities (columns T..Tp-1 zero): the fp32 scoring path (main.py:161-214 runs fp32 end to end) */
 int scl_softmax_fwd_f32(const float* S, float* P, int64_t R, int T, int ldS, int Tp, void* stream);
+/* the same for rows of any length (one wave per row, looped: online fp32 max / sum, then the write pass); T <= ldS, T <= Tp, Tp % 4 == 0:
+ * the fp32 scoring path above 512 frames */
+int scl_softmax_fwd_f32_long(const float* S, float* P, int64_t R, int T, int ldS, int Tp, void* stream);
 /* Fused attention for head dim 64 (scores stay on chip).  qkv / dqkv: bf16 [B, T, 3, H, 64]; ctx / dctx: bf16 [B, T, H*64];
  * lse: f32 [B, H, T] row log-sum-exp of the scaled scores.  fwd: T <= 256; bwd: T <= 224 (LDS budget).
  * Replaces F.multi_head_attention_forward inside fairseq's TransformerSentenceEncoderLayer (model/xlsr.py:41) and its backward.
@@ -371,6 +374,17 @@ int scl_attn_fwd(const void* qkv, void* ctx, float* lse, int B, int T, int H, in
 int scl_attn_fwd_fp8(const void* qkv, void* ctx, float* lse, int B, int T, int H, int D, float scale, void* stream);
 int scl_attn_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, float* bias_part, int B, int T,
                  int H, int D, float scale, float drop_p, uint32_t drop_seed, void* stream);
+/* Streaming attention for head dim 64 and any T >= 1 (csrc/attention_long.hip): K / V blocks of 64 keys through LDS, online fp32
+ * soft-max; no T x T buffer.  Same operands, layouts, dropout mask index and outputs as scl_attn_fwd / scl_attn_bwd (row r = (b, h, q) of
+ * lse and of the mask).  The encoder's path above 512 frames (and 225-512 with SCL_ATTN_LONG=1).
+ * bwd: P recomputed from lse, delta = rowsum(dO o O) into ws (scl_attn_long_ws_bytes(B, T, H) bytes); dK / dV per block of 128 keys,
+ * dQ per block of 64 queries, no atomics (two launches give identical dqkv).  Writes every dqkv element of rows < T; no bias partials
+ * (the q/k/v bias gradients are column sums of dqkv). */
+int scl_attn_fwd_long(const void* qkv, void* ctx, float* lse, int B, int T, int H, int D, float scale, float drop_p, uint32_t drop_seed,
+                      void* stream);
+long long scl_attn_long_ws_bytes(int B, int T, int H);
+int scl_attn_bwd_long(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, void* ws, int B, int T, int H, int D,
+                      float scale, float drop_p, uint32_t drop_seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* feature-extractor layer 0 (Conv1d(1,C,10,5) + LayerNorm + GELU), fused fwd / bwd            */

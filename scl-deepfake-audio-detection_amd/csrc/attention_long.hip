@@ -1,0 +1,507 @@
+// attention_long.hip — streaming ("flash") attention for head dim 64 and any clip length (T >= 1), forward and backward, plus the
+// looped fp32 row soft-max of the fp32 scoring path.  The encoder routes here above the 512 frames the materialised-score path
+// (attention.hip: a whole score row in registers) accepts; nothing of size T^2 is written to memory.
+//
+// Operands and outputs as scl_attn_fwd / scl_attn_bwd: qkv / dqkv bf16 [B, T, 3, H, 64]; ctx / dctx bf16 [B, T, H*64]; lse f32 [B, H, T]
+// = log sum_k exp(scale * q.k).  Attention dropout draws keep-mask hash(seed, ((b*H + h)*T + q)*T + k), the index of the fused kernels
+// and of scl_dropout_rows.  Every global offset is 64-bit.
+//
+// Forward, one workgroup per (utterance, head, block of 64 queries), 4 waves of 16 queries.  Blocks of 64 keys stream through LDS
+// (double-buffered, the next block's loads are issued before the current block is multiplied and written to LDS after it: one barrier
+// per block).  Per block and wave:
+//   S^T[key][q] = K Q^T       MFMA(A = K rows from LDS, B = the wave's Q rows held in registers)  -> lane owns ONE query (lc) and keys
+//                             16t + 4g + r of each 16-key tile t: the row maximum is an in-lane max plus two cross-lane steps
+//   online soft-max in fp32:  m' = max(m, rowmax), O *= 2^((m - m') scale log2 e), l = l * the same + rowsum(2^((S - m') scale log2 e))
+//   O^T[d][q]  += V^T P^T     the exponentials, packed to bf16, ARE the B operand (the transposed LDS read of V supplies the permuted k)
+// The rescale is applied on every block (no deferred rescale): the probabilities fed to the MFMA are <= 1 as in the fused kernel.
+//
+// Backward (P recomputed from lse, delta = rowsum(dO o O) by a small first kernel into the workspace):
+//   dK / dV: one workgroup per (utterance, head, block of 128 keys); wave w owns keys 32w..32w+31 (their K / V fragments in registers,
+//            dK^T / dV^T in accumulators) while the workgroup sweeps the queries 32 at a time (Q and dO tiles in LDS, row and
+//            transposed images, double-buffered): S = Q K^T, dP = dO V^T, P = exp(scale S - lse), dS = P (dP mask - delta),
+//            dV^T += dO^T (P mask), dK^T += Q^T dS.
+//   dQ:      one workgroup per (utterance, head, block of 64 queries), as the forward: S^T = K Q^T, dP^T = V dO^T, dS^T as above,
+//            dQ^T += K^T dS^T with K's transposed image.
+// Each output element is summed by one wave in a fixed order: no atomics, bitwise reproducible.
+#include "common.h"
+
+namespace {
+
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4_l;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4l;
+constexpr int LD = 64;        // head dim
+constexpr int LKB = 64;       // keys per streamed block (forward, dQ)
+constexpr int LQB = 64;       // queries per workgroup (forward, dQ)
+constexpr int LKW = 128;      // keys per workgroup (dK / dV)
+constexpr float LOG2E = 1.4426950408889634f;
+
+// LDS images of a [rows][64] bf16 tile, 128-byte rows (the same two images as attention.hip's fused kernels):
+// row image for ds_read_b128 row reads, 16-byte slot ^= (row >> 1) & 7; tr image for ds_read_b64_tr_b16, 32-byte chunk ^= (row >> 1) & 3
+__device__ __forceinline__ int lk_off(int row, int c) { return row * 128 + ((c ^ ((row >> 1) & 7)) << 4); }
+__device__ __forceinline__ int lt_off(int row, int d) { return row * 128 + ((((d >> 4) ^ ((row >> 1) & 3))) << 5) + ((d & 15) << 1); }
+
+// operand fragment of 16 rows (rowblk) x 32 columns (k step ks): lane holds row 16 rowblk + (lane & 15), columns 32 ks + 8 (lane >> 4) + 0..7
+__device__ __forceinline__ bf16x8 l_frag_rows(const char* tile, int rowblk, int ks, int lane) {
+    const int row = rowblk * 16 + (lane & 15);
+    return *reinterpret_cast<const bf16x8*>(tile + lk_off(row, 4 * ks + (lane >> 4)));
+}
+// transposed operand [i = d (16, block dt)][k = 8 rows]: rows rowa + 4g + 0..3 and rowb + 4g + 0..3 — the k order of a packed pair of
+// accumulator tiles (rows 4g + r of tile a, then of tile b).  Every lane of the wave must execute it (cross-lane gather).
+__device__ __forceinline__ bf16x8 l_frag_tr(const char* tile, int rowa, int rowb, int dt, int lane) {
+    const int i = lane & 15, g = lane >> 4;
+    const int ra = rowa + 4 * g + (i >> 2), rb = rowb + 4 * g + (i >> 2);
+    const int col = 16 * dt + 4 * (i & 3);
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_l*)(tile + lt_off(ra, col)));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_l*)(tile + lt_off(rb, col)));
+    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, v);
+}
+__device__ __forceinline__ bf16x8 l_pack8(const f32x4& a, const f32x4& b) {
+    u32x4l pk;
+    pk[0] = pack_bf2(a[0], a[1]); pk[1] = pack_bf2(a[2], a[3]); pk[2] = pack_bf2(b[0], b[1]); pk[3] = pack_bf2(b[2], b[3]);
+    return __builtin_bit_cast(bf16x8, pk);
+}
+// 16 rows of a [T][64] bf16 matrix (row pitch `pitch`) as an MFMA operand straight from global memory: the lane passes its own row q
+// (first row + (lane & 15)) and receives columns 32 ks + 8 (lane >> 4) + 0..7 (zeros past T)
+__device__ __forceinline__ void l_load_rows(const bf16_t* __restrict__ base, int64_t pitch, int q, int T, int g, bf16x8 (&f)[2]) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        uint4 u = make_uint4(0, 0, 0, 0);
+        if (q < T) u = *reinterpret_cast<const uint4*>(base + (int64_t)q * pitch + 32 * ks + 8 * g);
+        f[ks] = __builtin_bit_cast(bf16x8, u);
+    }
+}
+
+// K / V block staging for the forward and dQ kernels: 64 keys x 8 16-byte chunks of K and of V = 2 + 2 vectors per thread (256 threads),
+// zeros for keys past T (their scores are masked; a zero V row keeps 0 x garbage out of the P V product)
+struct KVRegs { uint4 k[2], v[2]; };
+__device__ __forceinline__ void kv_fetch(KVRegs& r, const bf16_t* __restrict__ base, int64_t pitch, int E, int key0, int T) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int idx = threadIdx.x + 256 * it, key = key0 + (idx >> 3), c = idx & 7;
+        r.k[it] = make_uint4(0, 0, 0, 0); r.v[it] = make_uint4(0, 0, 0, 0);
+        if (key < T) {
+            r.k[it] = *reinterpret_cast<const uint4*>(base + (int64_t)key * pitch + E + 8 * c);
+            r.v[it] = *reinterpret_cast<const uint4*>(base + (int64_t)key * pitch + 2 * E + 8 * c);
+        }
+    }
+}
+// Kr: K row image, Kt: K tr image (nullptr = not wanted), Vr: V row image (nullptr = not wanted), Vt: V tr image (nullptr = not wanted)
+__device__ __forceinline__ void kv_store(const KVRegs& r, char* Kr, char* Kt, char* Vr, char* Vt) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int idx = threadIdx.x + 256 * it, key = idx >> 3, c = idx & 7;
+        *reinterpret_cast<uint4*>(Kr + lk_off(key, c)) = r.k[it];
+        if (Kt) *reinterpret_cast<uint4*>(Kt + lt_off(key, 8 * c)) = r.k[it];
+        if (Vr) *reinterpret_cast<uint4*>(Vr + lk_off(key, c)) = r.v[it];
+        if (Vt) *reinterpret_cast<uint4*>(Vt + lt_off(key, 8 * c)) = r.v[it];
+    }
+}
+
+// =====================================================================================================================================
+// Forward
+// =====================================================================================================================================
+template <bool DROP>
+__global__ __launch_bounds__(256) void attn_fwd_long_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, float* __restrict__ lse,
+                                                            int T, int H, int nqb, float scale, float drop_p, uint32_t drop_seed) {
+    __shared__ __attribute__((aligned(16))) char smem[2][2][LKB * 128];      // [buffer][K rows, V tr][64 keys x 128 B]
+    const int E = H * LD;
+    const int64_t pitch = 3 * (int64_t)E;
+    const int bh = blockIdx.x / nqb, qblk = blockIdx.x % nqb;
+    const int b = bh / H, h = bh % H;
+    const bf16_t* base = qkv + (int64_t)b * T * pitch + h * LD;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lc = lane & 15, g = lane >> 4;
+    const int q = qblk * LQB + 16 * wave + lc;
+    const int nkb = (T + LKB - 1) / LKB;
+    bf16x8 qf[2];
+    l_load_rows(base, pitch, q, T, g, qf);
+    KVRegs r;
+    kv_fetch(r, base, pitch, E, 0, T);
+    kv_store(r, smem[0][0], nullptr, nullptr, smem[0][1]);
+    __syncthreads();
+    const float sl2 = scale * LOG2E;
+    const uint64_t rowbase = (((uint64_t)b * H + h) * T + (uint64_t)(q < T ? q : 0)) * (uint64_t)T;
+    float m = -INFINITY, l = 0.f;      // running max (raw score units) and this lane's share of the running sum
+    f32x4 o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int kb = 0; kb < nkb; ++kb) {
+        const int p = kb & 1;
+        if (kb + 1 < nkb) kv_fetch(r, base, pitch, E, (kb + 1) * LKB, T);      // in flight under this block's products
+        const char* Kr = smem[p][0];
+        const char* Vt = smem[p][1];
+        const int key0 = kb * LKB;
+        f32x4 s[4];
+        float mb = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l_frag_rows(Kr, t, ks, lane), qf[ks], s[t], 0, 0, 0);
+            if (key0 + LKB > T) {      // the last block only
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr)
+                    if (key0 + 16 * t + 4 * g + rr >= T) s[t][rr] = -INFINITY;
+            }
+            mb = fmaxf(mb, fmaxf(fmaxf(s[t][0], s[t][1]), fmaxf(s[t][2], s[t][3])));
+        }
+        mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
+        mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
+        const float mn = fmaxf(m, mb);      // finite: every block holds at least one key < T
+        const float alpha = __builtin_amdgcn_exp2f((m - mn) * sl2);      // 0 on the first block (m = -inf)
+        m = mn;
+        const float msl = -mn * sl2;
+        float ls = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) { s[t][rr] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t][rr], sl2, msl)); ls += s[t][rr]; }
+        l = l * alpha + ls;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
+        if (DROP) {      // the sum above is of the undropped probabilities; P x mask feeds P V
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const int key = key0 + 16 * t + 4 * g + rr;
+                    s[t][rr] *= dropout_scale(drop_seed, rowbase + (uint64_t)(key < T ? key : 0), drop_p);
+                }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const bf16x8 pf = l_pack8(s[2 * u], s[2 * u + 1]);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l_frag_tr(Vt, 32 * u, 32 * u + 16, dt, lane), pf, o[dt], 0, 0, 0);
+        }
+        if (kb + 1 < nkb) kv_store(r, smem[p ^ 1][0], nullptr, nullptr, smem[p ^ 1][1]);      // its last readers finished before the previous barrier
+        __syncthreads();
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.0f / l;
+    if (q < T) {
+        if (g == 0) lse[((int64_t)b * H + h) * T + q] = scale * m + __logf(l);
+        bf16_t* dst = ctx + ((int64_t)b * T + q) * E + h * LD + 4 * g;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+            *reinterpret_cast<uint2*>(dst + 16 * dt) = make_uint2(pack_bf2(o[dt][0] * inv, o[dt][1] * inv), pack_bf2(o[dt][2] * inv, o[dt][3] * inv));
+    }
+}
+
+// =====================================================================================================================================
+// Backward
+// =====================================================================================================================================
+// delta[(b*H + h)*T + q] = <dO, O> of the row (8 lanes per row, one 16-byte piece each, fixed-order sum)
+__global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restrict__ ctx, const bf16_t* __restrict__ dctx, float* __restrict__ delta,
+                                                         int64_t rows, int T, int H) {
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row = gid >> 3;      // (b, q, h) in memory order
+    const int c = (int)(gid & 7);
+    float dot = 0.f;
+    if (row < rows) {
+        const uint4 vo = *reinterpret_cast<const uint4*>(dctx + row * LD + 8 * c);
+        const uint4 vc = *reinterpret_cast<const uint4*>(ctx + row * LD + 8 * c);
+        const unsigned ow[4] = {vo.x, vo.y, vo.z, vo.w}, cw[4] = {vc.x, vc.y, vc.z, vc.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            dot += __uint_as_float(ow[k] << 16) * __uint_as_float(cw[k] << 16);
+            dot += __uint_as_float(ow[k] & 0xFFFF0000u) * __uint_as_float(cw[k] & 0xFFFF0000u);
+        }
+    }
+    dot = lanes8_sum(dot);
+    if (row < rows && c == 0) {
+        const int64_t bq = row / H;
+        const int h = (int)(row % H);
+        const int64_t b = bq / T, q = bq % T;
+        delta[(b * H + h) * T + q] = dot;
+    }
+}
+
+// ---- dK / dV ------------------------------------------------------------------------------------------------------------------------
+// Query tile of 32 rows per step: Q rows, Q tr, dO rows, dO tr images (4 KiB each), then lse (x log2 e) and delta of the 32 rows.
+constexpr int QT_BYTES = 4 * 4096 + 2 * 32 * 4;
+
+struct QRegs { uint4 q, o; float ls, dl; };
+// thread i: query row i >> 3 of the tile, 16-byte chunk i & 7 (256 threads = 32 rows x 8 chunks); rows past T: zeros, lse = +huge (P = 0)
+__device__ __forceinline__ void qt_fetch(QRegs& r, const bf16_t* __restrict__ base, int64_t pitch, const bf16_t* __restrict__ dob, int E,
+                                         const float* __restrict__ lse_bh, const float* __restrict__ del_bh, int q0, int T) {
+    const int row = threadIdx.x >> 3, c = threadIdx.x & 7, q = q0 + row;
+    r.q = make_uint4(0, 0, 0, 0); r.o = make_uint4(0, 0, 0, 0); r.ls = 1e30f; r.dl = 0.f;
+    if (q < T) {
+        r.q = *reinterpret_cast<const uint4*>(base + (int64_t)q * pitch + 8 * c);
+        r.o = *reinterpret_cast<const uint4*>(dob + (int64_t)q * E + 8 * c);
+        if (c == 0) { r.ls = lse_bh[q] * LOG2E; r.dl = del_bh[q]; }
+    }
+}
+__device__ __forceinline__ void qt_store(const QRegs& r, char* tile) {
+    const int row = threadIdx.x >> 3, c = threadIdx.x & 7;
+    *reinterpret_cast<uint4*>(tile + lk_off(row, c)) = r.q;
+    *reinterpret_cast<uint4*>(tile + 4096 + lt_off(row, 8 * c)) = r.q;
+    *reinterpret_cast<uint4*>(tile + 8192 + lk_off(row, c)) = r.o;
+    *reinterpret_cast<uint4*>(tile + 12288 + lt_off(row, 8 * c)) = r.o;
+    if (c == 0) {
+        float* ld = reinterpret_cast<float*>(tile + 16384);
+        ld[row] = r.ls; ld[32 + row] = r.dl;
+    }
+}
+
+template <bool DROP>
+__global__ __launch_bounds__(256) void attn_bwd_dkdv_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
+                                                                 const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                 bf16_t* __restrict__ dqkv, int T, int H, int nkw, float scale,
+                                                                 float drop_p, uint32_t drop_seed) {
+    __shared__ __attribute__((aligned(16))) char smem[2][QT_BYTES];
+    const int E = H * LD;
+    const int64_t pitch = 3 * (int64_t)E;
+    const int bh = blockIdx.x / nkw, kblk = blockIdx.x % nkw;
+    const int b = bh / H, h = bh % H;
+    const bf16_t* base = qkv + (int64_t)b * T * pitch + h * LD;
+    const bf16_t* dob = dctx + (int64_t)b * T * E + h * LD;
+    const float* lse_bh = lse + ((int64_t)b * H + h) * T;
+    const float* del_bh = delta + ((int64_t)b * H + h) * T;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lc = lane & 15, g = lane >> 4;
+    const int key_w = kblk * LKW + 32 * wave;      // first of this wave's 32 keys
+    // the wave's K / V rows as B operands (lane: key key_w + 16 j + lc, d = 32 ks + 8 g + 0..7)
+    bf16x8 kf[2][2], vf[2][2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        l_load_rows(base + E, pitch, key_w + 16 * j + lc, T, g, kf[j]);
+        l_load_rows(base + 2 * E, pitch, key_w + 16 * j + lc, T, g, vf[j]);
+    }
+    const int nqt = (T + 31) / 32;
+    QRegs r;
+    qt_fetch(r, base, pitch, dob, E, lse_bh, del_bh, 0, T);
+    qt_store(r, smem[0]);
+    __syncthreads();
+    f32x4 dVt[4][2], dKt[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { dVt[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; dKt[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    const float sc2 = scale * LOG2E;
+    for (int u = 0; u < nqt; ++u) {
+        const int p = u & 1;
+        if (u + 1 < nqt) qt_fetch(r, base, pitch, dob, E, lse_bh, del_bh, 32 * (u + 1), T);
+        const char* Qk = smem[p];
+        const char* Qt = Qk + 4096;
+        const char* Ok = Qk + 8192;
+        const char* Ot = Qk + 12288;
+        const float* lsP = reinterpret_cast<const float*>(Qk + 16384);
+        const float* dlP = lsP + 32;
+        bf16x8 qa[2][2], oa[2][2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) { qa[a][ks] = l_frag_rows(Qk, a, ks, lane); oa[a][ks] = l_frag_rows(Ok, a, ks, lane); }
+        float lq[2][4], dq_[2][4];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const float4 l4 = *reinterpret_cast<const float4*>(lsP + 16 * a + 4 * g), d4 = *reinterpret_cast<const float4*>(dlP + 16 * a + 4 * g);
+            lq[a][0] = l4.x; lq[a][1] = l4.y; lq[a][2] = l4.z; lq[a][3] = l4.w;
+            dq_[a][0] = d4.x; dq_[a][1] = d4.y; dq_[a][2] = d4.z; dq_[a][3] = d4.w;
+        }
+        f32x4 P[2][2], dS[2][2];      // [query tile a][key tile j]: D[q = 16a + 4g + r][key = 16j + lc]
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int key = key_w + 16 * j + lc;
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                f32x4 sv = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
+                sv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[a][0], kf[j][0], sv, 0, 0, 0);
+                sv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[a][1], kf[j][1], sv, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oa[a][0], vf[j][0], dp, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oa[a][1], vf[j][1], dp, 0, 0, 0);
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const int qq = 32 * u + 16 * a + 4 * g + rr;
+                    const float pv = key >= T ? 0.f : __builtin_amdgcn_exp2f(__builtin_fmaf(sv[rr], sc2, -lq[a][rr]));      // rows past T: lse = huge -> 0
+                    const float mk = DROP ? dropout_scale(drop_seed, (((uint64_t)b * H + h) * T + (uint64_t)(qq < T ? qq : 0)) * (uint64_t)T +
+                                                                         (uint64_t)(key < T ? key : 0), drop_p) : 1.f;
+                    P[a][j][rr] = pv * mk;
+                    dS[a][j][rr] = pv * (dp[rr] * mk - dq_[a][rr]);
+                }
+            }
+        }
+        bf16x8 pP[2], pS[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { pP[j] = l_pack8(P[0][j], P[1][j]); pS[j] = l_pack8(dS[0][j], dS[1][j]); }
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            const bf16x8 ot = l_frag_tr(Ot, 0, 16, dt, lane);
+            const bf16x8 qt = l_frag_tr(Qt, 0, 16, dt, lane);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                dVt[dt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ot, pP[j], dVt[dt][j], 0, 0, 0);
+                dKt[dt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt, pS[j], dKt[dt][j], 0, 0, 0);
+            }
+        }
+        if (u + 1 < nqt) qt_store(r, smem[p ^ 1]);
+        __syncthreads();
+    }
+    // dK^T / dV^T: lane holds key key_w + 16 j + lc, d = 16 dt + 4 g + 0..3
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int key = key_w + 16 * j + lc;
+        if (key < T) {
+            bf16_t* dst = dqkv + ((int64_t)b * T + key) * pitch + h * LD + 4 * g;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                *reinterpret_cast<uint2*>(dst + E + 16 * dt) = make_uint2(pack_bf2(dKt[dt][j][0] * scale, dKt[dt][j][1] * scale),
+                                                                          pack_bf2(dKt[dt][j][2] * scale, dKt[dt][j][3] * scale));
+                *reinterpret_cast<uint2*>(dst + 2 * E + 16 * dt) = make_uint2(pack_bf2(dVt[dt][j][0], dVt[dt][j][1]), pack_bf2(dVt[dt][j][2], dVt[dt][j][3]));
+            }
+        }
+    }
+}
+
+// ---- dQ -------------------------------------------------------------------------------------------------------------------------------
+template <bool DROP>
+__global__ __launch_bounds__(256) void attn_bwd_dq_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
+                                                               const float* __restrict__ lse, const float* __restrict__ delta,
+                                                               bf16_t* __restrict__ dqkv, int T, int H, int nqb, float scale,
+                                                               float drop_p, uint32_t drop_seed) {
+    __shared__ __attribute__((aligned(16))) char smem[2][3][LKB * 128];      // [buffer][K rows, K tr, V rows]
+    const int E = H * LD;
+    const int64_t pitch = 3 * (int64_t)E;
+    const int bh = blockIdx.x / nqb, qblk = blockIdx.x % nqb;
+    const int b = bh / H, h = bh % H;
+    const bf16_t* base = qkv + (int64_t)b * T * pitch + h * LD;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lc = lane & 15, g = lane >> 4;
+    const int q0 = qblk * LQB + 16 * wave, q = q0 + lc;
+    const int nkb = (T + LKB - 1) / LKB;
+    bf16x8 qf[2], of[2];
+    l_load_rows(base, pitch, q, T, g, qf);
+    l_load_rows(dctx + (int64_t)b * T * E + h * LD, E, q, T, g, of);
+    const int64_t rbh = ((int64_t)b * H + h) * T;
+    const float lq = q < T ? lse[rbh + q] * LOG2E : 1e30f;
+    const float dl = q < T ? delta[rbh + q] : 0.f;
+    KVRegs r;
+    kv_fetch(r, base, pitch, E, 0, T);
+    kv_store(r, smem[0][0], smem[0][1], smem[0][2], nullptr);
+    __syncthreads();
+    const float sc2 = scale * LOG2E;
+    const uint64_t rowbase = ((uint64_t)rbh + (uint64_t)(q < T ? q : 0)) * (uint64_t)T;
+    f32x4 dq[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int kb = 0; kb < nkb; ++kb) {
+        const int p = kb & 1;
+        if (kb + 1 < nkb) kv_fetch(r, base, pitch, E, (kb + 1) * LKB, T);
+        const char* Kr = smem[p][0];
+        const char* Kt = smem[p][1];
+        const char* Vr = smem[p][2];
+        const int key0 = kb * LKB;
+        f32x4 ds[4];      // dS^T[key = 16t + 4g + r][q = lc]
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            f32x4 sv = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                sv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l_frag_rows(Kr, t, ks, lane), qf[ks], sv, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l_frag_rows(Vr, t, ks, lane), of[ks], dp, 0, 0, 0);
+            }
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int key = key0 + 16 * t + 4 * g + rr;
+                const float pv = key >= T ? 0.f : __builtin_amdgcn_exp2f(__builtin_fmaf(sv[rr], sc2, -lq));
+                const float mk = DROP ? dropout_scale(drop_seed, rowbase + (uint64_t)(key < T ? key : 0), drop_p) : 1.f;
+                ds[t][rr] = pv * (dp[rr] * mk - dl);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const bf16x8 sf = l_pack8(ds[2 * u], ds[2 * u + 1]);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+                dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l_frag_tr(Kt, 32 * u, 32 * u + 16, dt, lane), sf, dq[dt], 0, 0, 0);
+        }
+        if (kb + 1 < nkb) kv_store(r, smem[p ^ 1][0], smem[p ^ 1][1], smem[p ^ 1][2], nullptr);
+        __syncthreads();
+    }
+    if (q < T) {
+        bf16_t* dst = dqkv + ((int64_t)b * T + q) * pitch + h * LD + 4 * g;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+            *reinterpret_cast<uint2*>(dst + 16 * dt) = make_uint2(pack_bf2(dq[dt][0] * scale, dq[dt][1] * scale), pack_bf2(dq[dt][2] * scale, dq[dt][3] * scale));
+    }
+}
+
+// =====================================================================================================================================
+// fp32 row soft-max of any length: one wave per row, a looped online (max, sum) pass then a write pass
+// =====================================================================================================================================
+__global__ __launch_bounds__(256) void softmax_fwd_f32_long_kernel(const float* __restrict__ S, float* __restrict__ P, int64_t R, int T,
+                                                                   int ldS, int Tp) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= R) return;
+    const float* s = S + row * ldS;
+    float m = -INFINITY, l = 0.f;
+    for (int c = lane; c < T; c += 64) {
+        const float v = s[c];
+        if (v > m) { l = l * __expf(m - v) + 1.f; m = v; }
+        else if (m != -INFINITY) l += __expf(v - m);      // v = m = -inf adds nothing
+    }
+    const float mx = wave_max(m);
+    const float sum = wave_sum(m == -INFINITY ? 0.f : l * __expf(m - mx));
+    const float inv = 1.0f / sum;
+    float* p = P + row * Tp;
+    for (int c = lane; c < Tp; c += 64) p[c] = c < T ? __expf(s[c] - mx) * inv : 0.f;
+}
+
+}  // namespace
+
+extern "C" int scl_attn_fwd_long(const void* qkv, void* ctx, float* lse, int B, int T, int H, int D, float scale, float drop_p,
+                                 uint32_t drop_seed, void* stream) {
+    SCL_REQUIRE(qkv && ctx && lse && B > 0 && H > 0 && T >= 1 && drop_p >= 0.f && drop_p < 1.f, "attn_fwd_long: bad args");
+    SCL_REQUIRE(D == LD, "attn_fwd_long: needs head dim 64 (got D=%d)", D);
+    const int nqb = (T + LQB - 1) / LQB;
+    SCL_REQUIRE((int64_t)B * H * nqb < 0x7FFFFFFF, "attn_fwd_long: grid too large");
+    const dim3 grid((unsigned)(B * H * nqb));
+    if (drop_p > 0.f)
+        hipLaunchKernelGGL(attn_fwd_long_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)ctx, lse, T, H, nqb,
+                           scale, drop_p, drop_seed);
+    else
+        hipLaunchKernelGGL(attn_fwd_long_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)ctx, lse, T, H, nqb,
+                           scale, drop_p, drop_seed);
+    return scl_check_launch("scl_attn_fwd_long");
+}
+
+extern "C" long long scl_attn_long_ws_bytes(int B, int T, int H) {
+    if (B <= 0 || T <= 0 || H <= 0) return 0;
+    return ((long long)B * H * T * 4 + 255) / 256 * 256;      // delta = rowsum(dO o O), f32 [B, H, T]
+}
+
+extern "C" int scl_attn_bwd_long(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, void* ws, int B, int T,
+                                 int H, int D, float scale, float drop_p, uint32_t drop_seed, void* stream) {
+    SCL_REQUIRE(qkv && ctx && dctx && lse && dqkv && ws && B > 0 && H > 0 && T >= 1 && drop_p >= 0.f && drop_p < 1.f, "attn_bwd_long: bad args");
+    SCL_REQUIRE(D == LD, "attn_bwd_long: needs head dim 64 (got D=%d)", D);
+    const int nqb = (T + LQB - 1) / LQB, nkw = (T + LKW - 1) / LKW;
+    SCL_REQUIRE((int64_t)B * H * nqb < 0x7FFFFFFF, "attn_bwd_long: grid too large");
+    hipStream_t s = (hipStream_t)stream;
+    float* delta = (float*)ws;
+    const int64_t rows = (int64_t)B * T * H;
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, s, (const bf16_t*)ctx, (const bf16_t*)dctx, delta,
+                       rows, T, H);
+    int rc = scl_check_launch("scl_attn_bwd_long (delta)");
+    if (rc) return rc;
+#define ATT_BWD_LONG(DR)                                                                                                                        \
+    hipLaunchKernelGGL(attn_bwd_dkdv_long_kernel<DR>, dim3((unsigned)(B * H * nkw)), dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dctx, \
+                       lse, (const float*)delta, (bf16_t*)dqkv, T, H, nkw, scale, drop_p, drop_seed);                                           \
+    hipLaunchKernelGGL(attn_bwd_dq_long_kernel<DR>, dim3((unsigned)(B * H * nqb)), dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dctx,   \
+                       lse, (const float*)delta, (bf16_t*)dqkv, T, H, nqb, scale, drop_p, drop_seed)
+    if (drop_p > 0.f) { ATT_BWD_LONG(true); }
+    else { ATT_BWD_LONG(false); }
+#undef ATT_BWD_LONG
+    return scl_check_launch("scl_attn_bwd_long");
+}
+
+extern "C" int scl_softmax_fwd_f32_long(const float* S, float* P, int64_t R, int T, int ldS, int Tp, void* stream) {
+    SCL_REQUIRE(S && P && R > 0 && T > 0 && Tp >= T && ldS >= T && (Tp & 3) == 0, "softmax_fwd_f32_long: need T <= Tp, T <= ldS, Tp %% 4 == 0");
+    hipLaunchKernelGGL(softmax_fwd_f32_long_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, S, P, R, T, ldS, Tp);
+    return scl_check_launch("scl_softmax_fwd_f32_long");
+}

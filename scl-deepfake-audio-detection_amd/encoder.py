@@ -17,7 +17,7 @@ import os
 import torch
 
 from . import ops
-from .lib import ACT_GELU, ACT_GELU_DC2, FLAT, RACT_STORED
+from .lib import ACT_GELU, ACT_GELU_DC2, FLAT, RACT_STORED, SclError
 from .ops import Op
 
 # fc1.bias.grad summed by the epilogue of the GEMM that writes its input
@@ -47,6 +47,12 @@ GELU_DC2 = True      # decided by the A/Bs of rounds 2-4; 
 # BASELINE.json configs[4] names fp8 attention: csrc/attention_fp8.hip (e4m3 operands, fp32 accumulation) for the no-grad bf16 forward.  Opt-in:
 # the reference is fp32 and the fused forward is bound by its soft-max VALU work, not by the matrix pipe (profiles/r4_attn_fp8_probe.txt).
 ATTN_FP8 = os.environ.get("SCL_ATTN_FP8", "0") == "1"
+# Attention above 512 frames (64-wide heads): the streaming kernels of csrc/attention_long.hip, no T x T buffer.  SCL_ATTN_LONG=1 sends
+# 225-512 frames there too (same-box A/B against the materialised-score path, which stays the default there).
+ATTN_LONG = os.environ.get("SCL_ATTN_LONG", "0") == "1"
+MAT_ATTN_MAX_T = 512      # the materialised path's soft-max keeps a whole score row in registers (csrc/attention.hip)
+# fp32 scoring path above 512 frames: utterances per chunk of the materialised f32 attention such that S (and Pm) stay within this many bytes
+F32_ATTN_CHUNK_BYTES = 1 << 30
 SCORE_X3PLANES = os.environ.get("SCL_SCORE_X3PLANES", "1") != "0"      # fp32 scoring path: plain linears as one bf16 GEMM over [hi | hi | lo] x [hi | lo | hi] (forward_f32)
 CONV_WGRAD_WIDE = True      # decided by the A/Bs of rounds 2-4; the environment switch is gone
 
@@ -237,9 +243,16 @@ class Encoder:
         d["m1"], d["r1"] = [f32(M) for _ in range(cfg.layers)], [f32(M) for _ in range(cfg.layers)]
         d["qkv"] = [bf(M * 3 * E + slack) for _ in range(cfg.layers)]
         d["fused_attn"] = (E // H == 64) and T <= 224      # scores stay on chip (csrc/attention.hip); else materialised path
-        if d["fused_attn"]:
+        # streaming attention (csrc/attention_long.hip): above 512 frames, or from 225 frames with SCL_ATTN_LONG=1
+        d["long_attn"] = (E // H == 64) and not d["fused_attn"] and (T > MAT_ATTN_MAX_T or ATTN_LONG)
+        if T > MAT_ATTN_MAX_T and not d["long_attn"]:
+            raise SclError("encoder: %d frames need the streaming attention, which takes head dim 64 (got %d); other head dims are limited "
+                           "to %d frames (%d samples)" % (T, E // H, MAT_ATTN_MAX_T, L))
+        if d["fused_attn"] or d["long_attn"]:
             d["lse"] = [f32(B * H * T) for _ in range(cfg.layers)]
-        else:
+        if d["long_attn"]:
+            d["attn_ws"] = torch.empty(ops.attn_long_ws_bytes(B, T, H), dtype=torch.uint8, device=dev)
+        elif not d["fused_attn"]:
             d["S"] = f32(B * H * T * Tp)   # row stride Tp keeps the 4-wide epilogue stores aligned
             d["P"] = [bf(B * H * T * Tp + 1024) for _ in range(cfg.layers)]
         d["ctx"] = [bfz(Mp, E) for _ in range(cfg.layers)]
@@ -257,7 +270,7 @@ class Encoder:
         d["d_h"] = bf(M * E + slack)
         d["d_ctx"] = bf(M * E + slack)
         d["dqkv"] = [bfz(Mp, 3 * E, slack), bfz(Mp, 3 * E, slack)]
-        d["dS"] = None if d["fused_attn"] else bf(B * H * T * Tp + 1024)
+        d["dS"] = None if (d["fused_attn"] or d["long_attn"]) else bf(B * H * T * Tp + 1024)
         d["dcpad"] = bf(B * (T + K) * E + slack)
         d["dz"] = [bf(B * t * C + slack) for t in Ts]
         # conv-stack backward: LayerNorm-backward output of layer i with per-utterance zero rows (Q in front, Qe behind) so that
@@ -492,6 +505,10 @@ class Encoder:
                 e = ops.attn_fwd(qkv, d["ctx"][n], d["lse"][n], B, T, H, D, D ** -0.5, drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
                 if p_attn > 0:
                     self._slot(slots, e, ops.ATTN_FWD_SEED, n, self.SITE_ATTN)
+            elif d["long_attn"]:
+                e = ops.attn_fwd_long(qkv, d["ctx"][n], d["lse"][n], B, T, H, D, D ** -0.5, drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
+                if p_attn > 0:
+                    self._slot(slots, e, ops.ATTN_FWD_LONG_SEED, n, self.SITE_ATTN)
             else:
                 ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=E), d["S"], T, T, D,
                          nb1=B, nb2=H, alpha=D ** -0.5, ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
@@ -560,13 +577,16 @@ class Encoder:
         Ts = cfg.conv_lens(L)
         T = Ts[-1]
         M, Tp = B * T, (T + 7) // 8 * 8
-        key = ("f32", B, L)
+        # above 512 frames the attention runs in chunks of `bc` utterances (the looped soft-max; S / Pm sized per chunk, <= F32_ATTN_CHUNK_BYTES)
+        long_attn = T > MAT_ATTN_MAX_T
+        bc = max(1, min(B, F32_ATTN_CHUNK_BYTES // (4 * H * T * Tp))) if long_attn else B
+        key = ("f32", B, L) if not long_attn else ("f32", B, L, bc)
         if key not in self._bufs:
             f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.dev)
             slack = 128 * max(C, E)
             self._bufs[key] = dict(z=[f32(B * t * C + slack) for t in Ts], y=f32(B * Ts[1] * C), stat=f32(2 * B * Ts[1]), h=f32(M * max(C, E) + slack),
                                    x0=f32(M * E), xpad=torch.zeros(B * (T + K) * E + slack, device=self.dev), xa=f32(M * E), xb=f32(M * E),
-                                   x1=f32(M * E), qkv=f32(M * 3 * E + slack), S=f32(B * H * T * Tp), Pm=torch.zeros(B * H * T * Tp + 1024, device=self.dev),
+                                   x1=f32(M * E), qkv=f32(M * 3 * E + slack), S=f32(bc * H * T * Tp), Pm=torch.zeros(bc * H * T * Tp + 1024, device=self.dev),
                                    ctx=f32(M * E + slack), a=f32(M * Fd + slack), out=f32(M * E),
                                    a3=torch.empty(M * 3 * max(C, E, Fd) + 2 * slack, dtype=torch.bfloat16, device=self.dev),
                                    a3b=torch.empty(M * 3 * Fd + 2 * slack, dtype=torch.bfloat16, device=self.dev))
@@ -619,11 +639,19 @@ class Encoder:
             pn = "encoder.layers.%d." % n
             ln_then_lin(xin, pn + "self_attn_layer_norm.weight", pn + "self_attn_layer_norm.bias", E, pn + "self_attn.q_proj.weight", 3 * E, qkv,
                         bias=self.b(pn + "self_attn.q_proj.bias"))
-            ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=E), S, T, T, D, nb1=B, nb2=H, alpha=D ** -0.5,
-                     ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
-            ops.softmax_fwd_f32(S, Pm, B * H * T, T, Tp, Tp)                                               # fp32 soft-max, as fairseq (one wave per row)
-            ops.gemm(Op(Pm, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=2 * E), d["ctx"], T, D, T, b_t=True,
-                     nb1=B, nb2=H, ldc=E, c_bs1=T * E, c_bs2=D)
+            if not long_attn:
+                ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=E), S, T, T, D, nb1=B, nb2=H, alpha=D ** -0.5,
+                         ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
+                ops.softmax_fwd_f32(S, Pm, B * H * T, T, Tp, Tp)                                               # fp32 soft-max, as fairseq (one wave per row)
+                ops.gemm(Op(Pm, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=2 * E), d["ctx"], T, D, T, b_t=True,
+                         nb1=B, nb2=H, ldc=E, c_bs1=T * E, c_bs2=D)
+            for c0 in range(0, B if long_attn else 0, bc):      # the same three steps per chunk of utterances, the looped soft-max
+                nb, o3 = min(bc, B - c0), c0 * T * 3 * E
+                ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + E), S, T, T, D, nb1=nb, nb2=H,
+                         alpha=D ** -0.5, ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
+                ops.softmax_fwd_f32_long(S, Pm, nb * H * T, T, Tp, Tp)
+                ops.gemm(Op(Pm, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + 2 * E), d["ctx"], T, D, T, b_t=True,
+                         nb1=nb, nb2=H, ldc=E, c_bs1=T * E, c_bs2=D, c_offset=c0 * T * E)
             lin(d["ctx"], E, pn + "self_attn.out_proj.weight", E, d["x1"], bias=self.b(pn + "self_attn.out_proj.bias"), R=xin, rmode=1)
             if use3 and ffn3:
                 # fc1 writes gelu(.) as the triple-plane image itself (SCL_GEMM_C_SPLIT3: no f32 activation, no split pass) and fc2 reads it
@@ -737,6 +765,11 @@ class Encoder:
                         jobs.append((d["qkv_bias_part"], self._qkv_view(pn, "bias"), B, 3 * E))
                     else:
                         ops.colreduce(d["qkv_bias_part"], self._qkv_view(pn, "bias"), B, 3 * E)
+            elif d["long_attn"]:      # q/k/v bias gradients: colsum_reduce below
+                e = ops.attn_bwd_long(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], dqkv, d["attn_ws"], B, T, H, D, D ** -0.5,
+                                      drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
+                if p_attn > 0:
+                    self._slot(slots, e, ops.ATTN_BWD_LONG_SEED, n, self.SITE_ATTN)
             else:
                 Pn = d["P"][n]
                 bq = dict(nb1=B, nb2=H)

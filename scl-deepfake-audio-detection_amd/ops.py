@@ -314,6 +314,7 @@ def layernorm_bwd_nparts(M):
 
 LN_BWD_DIN_SEED, LN_BWD_DOUT_SEED = 22, 24      # positions of the two mask seeds in a recorded scl_layernorm_bwd call
 ATTN_FWD_SEED, ATTN_BWD_SEED, DROPOUT_SEED = 9, 12, 4
+ATTN_FWD_LONG_SEED, ATTN_BWD_LONG_SEED = 9, 12      # positions of the mask seed in recorded scl_attn_fwd_long / scl_attn_bwd_long calls
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, beta, dres, dx_f32, dx_bf16, part, M, C, act=0, sum_dres=False, out_rpb=0,
@@ -481,6 +482,27 @@ def attn_fwd_fp8(qkv, ctx, lse, B, T, H, D, scale):
 def attn_bwd(qkv, ctx, dctx, lse, dqkv, B, T, H, D, scale, bias_part=None, drop_p=0.0, drop_seed=0):
     """bias_part: optional f32 [B, 3*H*D] — per-utterance column sums of dqkv (colreduce over B gives the q/k/v bias gradients)."""
     return _call("scl_attn_bwd", _p(qkv), _p(ctx), _p(dctx), _p(lse), _p(dqkv), _p(bias_part), B, T, H, D, scale, float(drop_p), int(drop_seed), _stream())
+
+
+def softmax_fwd_f32_long(S, P, R, T, ldS, Tp):
+    """scl_softmax_fwd_f32 for rows of any length (the fp32 scoring path above 512 frames)."""
+    _call("scl_softmax_fwd_f32_long", _p(S), _p(P), R, T, ldS, Tp, _stream())
+
+
+def attn_fwd_long(qkv, ctx, lse, B, T, H, D, scale, drop_p=0.0, drop_seed=0):
+    """Streaming attention forward (head dim 64, any T): the operands and outputs of attn_fwd."""
+    return _call("scl_attn_fwd_long", _p(qkv), _p(ctx), _p(lse), B, T, H, D, float(scale), float(drop_p), int(drop_seed), _stream())
+
+
+def attn_long_ws_bytes(B, T, H):
+    return int(L.load().scl_attn_long_ws_bytes(B, T, H))
+
+
+def attn_bwd_long(qkv, ctx, dctx, lse, dqkv, ws, B, T, H, D, scale, drop_p=0.0, drop_seed=0):
+    """Streaming attention backward: dqkv as attn_bwd (no bias partials); ws holds attn_long_ws_bytes(B, T, H) bytes."""
+    assert ws.numel() * ws.element_size() >= attn_long_ws_bytes(B, T, H), "attn_bwd_long: workspace too small"
+    return _call("scl_attn_bwd_long", _p(qkv), _p(ctx), _p(dctx), _p(lse), _p(dqkv), _p(ws), B, T, H, D, float(scale), float(drop_p),
+                 int(drop_seed), _stream())
 
 
 def dropout(x, y_f32, y_bf16, n, seed, p):
