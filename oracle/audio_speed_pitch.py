@@ -211,23 +211,59 @@ def stft(y):
     return np.fft.rfft(frames, axis=0).astype(np.complex64)
 
 
-def phase_vocoder(D, rate):
-    """librosa.phase_vocoder (core/spectrum.py), hop = n_fft / 4."""
+def phase_vocoder(D, rate, angle=np.angle, trace=None):
+    """librosa.phase_vocoder (core/spectrum.py), hop = n_fft / 4.  `angle` stands where librosa calls np.angle (a test substitutes a
+    perturbed one); a dict passed as `trace` receives the accumulator before every output frame ("acc", float32 [nb, steps + 1]) and
+    the float64 increment added after frame t ("inc" [nb, steps]: phi_advance + wrap(angle difference - phi_advance))."""
     nb, nfr = D.shape
     time_steps = np.arange(0, nfr, rate, dtype=np.float64)
     out = np.zeros((nb, len(time_steps)), dtype=D.dtype)
     phi_advance = np.linspace(0, np.pi * HOP, nb)
-    phase_acc = np.angle(D[:, 0])                               # float32, accumulated in float32 as librosa's in-place +=
+    phase_acc = angle(D[:, 0])                                  # float32, accumulated in float32 as librosa's in-place +=
     Dp = np.pad(D, [(0, 0), (0, 2)], mode="constant")
+    if trace is not None:
+        trace["acc"] = np.zeros((nb, len(time_steps) + 1), dtype=phase_acc.dtype)
+        trace["inc"] = np.zeros((nb, len(time_steps)))
+        trace["acc"][:, 0] = phase_acc
     for t, step in enumerate(time_steps):
         cols = Dp[:, int(step): int(step + 2)]
         alpha = np.mod(step, 1.0)
         mag = (1.0 - alpha) * np.abs(cols[:, 0]) + alpha * np.abs(cols[:, 1])
         out[:, t] = mag * np.exp(1j * phase_acc)                # util.phasor(phase_acc, mag=mag)
-        dphase = np.angle(cols[:, 1]) - np.angle(cols[:, 0]) - phi_advance
+        dphase = angle(cols[:, 1]) - angle(cols[:, 0]) - phi_advance
         dphase = dphase - 2.0 * np.pi * np.round(dphase / (2.0 * np.pi))
         phase_acc += phi_advance + dphase
+        if trace is not None:
+            trace["inc"][:, t] = phi_advance + dphase
+            trace["acc"][:, t + 1] = phase_acc
     return out
+
+
+def wrap_pi(a):
+    """a mapped to [-pi, pi)"""
+    return np.mod(np.asarray(a, dtype=np.float64) + np.pi, 2.0 * np.pi) - np.pi
+
+
+def phase_increment_errors(out, D, rate, c=16, mask_rel=1e-6):
+    """Local (per step, non-accumulating) check of a phase-vocoder output `out` [nb, steps] against this restatement fed the same
+    spectrum D.  For every bin k and step t the measured increment arg(out[k, t+1] conj(out[k, t])) is compared with the float64
+    increment inc[k, t] the restatement adds to its accumulator; the wrapped difference may be as large as the float32 rounding of the
+    accumulator after the step (ulp(|acc[k, t+1]|)) plus c float32 steps at pi (last-bit differences of the arctangents and of the
+    phasor).  Elements whose magnitude is below mask_rel of the largest are skipped.  Returns (worst error / bound, worst error in
+    radians, number of elements checked)."""
+    tr = {}
+    ref = phase_vocoder(D, rate, trace=tr)
+    assert out.shape == ref.shape, (out.shape, ref.shape)
+    o = np.asarray(out).astype(np.complex128)
+    meas = np.angle(o[:, 1:] * np.conj(o[:, :-1]))
+    err = np.abs(wrap_pi(meas - tr["inc"][:, :-1]))
+    acc = np.abs(tr["acc"][:, 1:-1]).astype(np.float32)
+    bound = np.spacing(acc).astype(np.float64) + c * float(np.spacing(np.float32(np.pi)))
+    mag = np.abs(ref).astype(np.float64)
+    ok = (mag[:, 1:] > mask_rel * mag.max()) & (mag[:, :-1] > mask_rel * mag.max())
+    if not ok.any():
+        return 0.0, 0.0, 0
+    return float((err[ok] / bound[ok]).max()), float(err[ok].max()), int(ok.sum())
 
 
 def istft(D, length):
@@ -257,10 +293,33 @@ def fix_length(y, size):
 SINC_ZEROS, SINC_BETA, SINC_ROLLOFF = 32, 14.769656459379492, 0.95
 
 
-def resample_sinc(y, ratio):
+def resample_sinc(y, ratio, block=2048):
     """Band-limited resampling by `ratio` = target_sr / orig_sr (stands where librosa calls soxr_hq, see the module header):
     out[n] = sum_k y[k] h(n / ratio - k), h(u) = 2 fc sinc(2 fc u) kaiser(u / W), fc = 0.5 * rolloff * min(1, ratio),
-    W = zeros / (2 fc) the half-width; n_out = ceil(len * ratio) (librosa.resample)."""
+    W = zeros / (2 fc) the half-width; n_out = ceil(len * ratio) (librosa.resample).  Evaluated `block` outputs at a time over a
+    gathered [block, 2W + 2] window of input indices, the taps outside [ceil(t - W), floor(t + W)] and outside the signal masked out."""
+    y = np.asarray(y, dtype=np.float64)
+    n_out = int(np.ceil(len(y) * ratio))
+    fc = 0.5 * SINC_ROLLOFF * min(1.0, ratio)
+    W = SINC_ZEROS / (2.0 * fc)
+    out = np.zeros(n_out)
+    i0b = np.i0(SINC_BETA)
+    span = np.arange(int(math.floor(2.0 * W)) + 2)
+    for b0 in range(0, n_out, block):
+        t = np.arange(b0, min(n_out, b0 + block)) / ratio
+        k0 = np.maximum(0, np.ceil(t - W).astype(np.int64))
+        k1 = np.minimum(len(y) - 1, np.floor(t + W).astype(np.int64))
+        k = k0[:, None] + span[None, :]
+        live = k <= k1[:, None]
+        u = t[:, None] - k
+        win = np.i0(SINC_BETA * np.sqrt(np.maximum(0.0, 1.0 - (u / W) ** 2))) / i0b
+        h = np.where(live, 2.0 * fc * np.sinc(2.0 * fc * u) * win, 0.0)
+        out[b0:b0 + len(t)] = (y[np.minimum(k, len(y) - 1)] * h).sum(axis=1)
+    return out.astype(np.float32)
+
+
+def resample_sinc_loop(y, ratio):
+    """resample_sinc output by output (the form it was first written in; tests pin the blocked form to it)."""
     y = np.asarray(y, dtype=np.float64)
     n_out = int(np.ceil(len(y) * ratio))
     fc = 0.5 * SINC_ROLLOFF * min(1.0, ratio)
