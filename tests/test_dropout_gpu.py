@@ -13,31 +13,10 @@ from scl_amd.encoder import Encoder, W2VConfig  # noqa: E402
 from scl_amd.model_linear import DROP_P, Model  # noqa: E402
 from oracle import head as OH  # noqa: E402
 from oracle import wav2vec2 as W  # noqa: E402
+from tests.attention_cases import enc_masks_for, hash_u32, keep_scale  # noqa: E402,F401
 
 ARGS = {"flag_fix_ssl": False, "contra_mode": "all", "loss_type": 1}
 CONF = {"model": {"contra_mode": "all", "loss_type": 1}}
-M32 = np.uint64(0xFFFFFFFF)
-
-
-def hash_u32(seed, idx):
-    """csrc/common.h::hash_u32, bit for bit (idx: uint64 array)."""
-    idx = idx.astype(np.uint64)
-    seed = np.uint64(seed)
-    x = ((idx & M32) * np.uint64(0x9E3779B1) & M32) ^ (((idx >> np.uint64(32)) * np.uint64(0x85EBCA77)) & M32) ^ seed
-    x ^= x >> np.uint64(16); x = x * np.uint64(0x7feb352d) & M32
-    x ^= x >> np.uint64(15); x = x * np.uint64(0x846ca68b) & M32
-    x ^= x >> np.uint64(16)
-    x = (x + (seed * np.uint64(0xC2B2AE3D) & M32)) & M32
-    x ^= x >> np.uint64(15); x = x * np.uint64(0x2c1b3c6d) & M32
-    x ^= x >> np.uint64(12); x = x * np.uint64(0x297a2d39) & M32
-    x ^= x >> np.uint64(15)
-    return x
-
-
-def keep_scale(seed, n, p):
-    """csrc/common.h::dropout_scale over element indices 0 .. n-1 -> float32 factors (0 or 1 / (1 - p))."""
-    u = (hash_u32(seed, np.arange(n, dtype=np.uint64)) >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-    return torch.from_numpy(np.where(u >= np.float32(p), np.float32(1.0) / (np.float32(1.0) - np.float32(p)), np.float32(0.0)).astype(np.float32))
 
 
 def rl2(got, ref):
@@ -58,28 +37,6 @@ def test_dropout_kernel_draws_the_mask_the_numpy_port_predicts(dev):
     k = keep_scale(seed, n, p)
     assert torch.equal(y.cpu(), x * k) and torch.equal(yb.cpu(), (x * k).to(torch.bfloat16))
     assert abs((k == 0).float().mean().item() - p) < 5e-3
-
-
-def enc_masks_for(step_seed, cfg, B, T, probs):
-    p_res, p_attn, p_act, p_in = probs
-    E, H, Fd = cfg.embed, cfg.heads, cfg.ffn
-    ss = lambda layer, site: Encoder.site_seed(step_seed, layer, site)
-    masks = {}
-    if p_in > 0:
-        masks["in"] = keep_scale(ss(-1, Encoder.SITE_IN), B * T * E, p_in).view(B, T, E)
-    if p_res > 0:
-        masks["enc"] = keep_scale(ss(-1, Encoder.SITE_ENC), B * T * E, p_res).view(B, T, E)
-    for n in range(cfg.layers):
-        m = {}
-        if p_attn > 0:
-            m["attn"] = keep_scale(ss(n, Encoder.SITE_ATTN), B * H * T * T, p_attn).view(B, H, T, T)
-        if p_res > 0:
-            m["d1"] = keep_scale(ss(n, Encoder.SITE_1), B * T * E, p_res).view(B, T, E)
-            m["d3"] = keep_scale(ss(n, Encoder.SITE_3), B * T * E, p_res).view(B, T, E)
-        if p_act > 0:
-            m["d2"] = keep_scale(ss(n, Encoder.SITE_2), B * T * Fd, p_act).view(B, T, Fd)
-        masks[n] = m
-    return masks
 
 
 @pytest.mark.parametrize("probs,heads", [((0.1, 0.1, 0.1, 0.1), 2), ((0.2, 0.0, 0.0, 0.0), 2), ((0.0, 0.15, 0.05, 0.0), 2),

@@ -18,32 +18,11 @@ from scl_amd.encoder import Encoder, W2VConfig  # noqa: E402
 from scl_amd.model_linear import DROP_P, Model  # noqa: E402
 from oracle import head as OH  # noqa: E402
 from oracle import wav2vec2 as W  # noqa: E402
+from tests.attention_cases import hash_u32, keep_scale  # noqa: E402,F401
 
 ARGS = {"flag_fix_ssl": False, "contra_mode": "all", "loss_type": 1}
 CONF = {"model": {"contra_mode": "all", "loss_type": 1}}
 SMALL = dict(conv_dim=32, embed=128, layers=2, heads=2, ffn=256, pos_k=16, pos_groups=4, final_dim=16, latent_vars=8, latent_groups=2)
-M32 = np.uint64(0xFFFFFFFF)
-
-
-def hash_u32(seed, idx):
-    """csrc/common.h::hash_u32, bit for bit (idx: uint64 array)."""
-    idx = idx.astype(np.uint64)
-    seed = np.uint64(seed)
-    x = ((idx & M32) * np.uint64(0x9E3779B1) & M32) ^ (((idx >> np.uint64(32)) * np.uint64(0x85EBCA77)) & M32) ^ seed
-    x ^= x >> np.uint64(16); x = x * np.uint64(0x7feb352d) & M32
-    x ^= x >> np.uint64(15); x = x * np.uint64(0x846ca68b) & M32
-    x ^= x >> np.uint64(16)
-    x = (x + (seed * np.uint64(0xC2B2AE3D) & M32)) & M32
-    x ^= x >> np.uint64(15); x = x * np.uint64(0x2c1b3c6d) & M32
-    x ^= x >> np.uint64(12); x = x * np.uint64(0x297a2d39) & M32
-    x ^= x >> np.uint64(15)
-    return x
-
-
-def keep_scale(seed, n, p):
-    """csrc/common.h::dropout_scale over element indices 0 .. n-1 -> float32 factors (0 or 1 / (1 - p))."""
-    u = (hash_u32(seed, np.arange(n, dtype=np.uint64)) >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-    return torch.from_numpy(np.where(u >= np.float32(p), np.float32(1.0) / (np.float32(1.0) - np.float32(p)), np.float32(0.0)).astype(np.float32))
 
 
 def rl2(got, ref):
