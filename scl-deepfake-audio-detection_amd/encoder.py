@@ -20,18 +20,6 @@ from . import ops
 from .lib import ACT_GELU, ACT_GELU_DC2, FLAT, RACT_STORED, SclError
 from .ops import Op
 
-# fc1.bias.grad summed by the epilogue of the GEMM that writes its input
-FUSED_BIAS_GRAD = True      # decided by the A/Bs of rounds 2-4; the environment switch is gone
-# 12-31-tile weight gradients (out-proj: 16 tiles of 256 x 256) in up to 16 split-K slabs on the wide kernel.  Round-3 re-measurement in one
-# call, three pairs: 47.78 / 47.59 / 47.66 ms per step off, 47.76 / 47.29 / 47.26 on (launch + slab reduction: 61.4 -> 53.8 us) — the earlier
-# "slower" verdict (53.7 vs 51.9 on different boxes) was box-to-box noise.
-WGRAD_SMALL_SPLIT = True      # decided by the A/Bs of rounds 2-4; the environment switch is gone
-# the (up to) four small column reductions that close a layer's backward in ONE launch
-BATCH_REDUCE = True      # decided by the A/Bs of rounds 2-4; the environment switch is gone
-# the split-K slabs of a layer's four weight gradients are combined by ONE launch at the end of the layer's backward (each gradient keeps
-# its own slab buffer until then) instead of one launch behind every weight-gradient GEMM: 72 kernel boundaries per step less
-#
-BATCH_SLABS = True      # decided by the A/Bs of rounds 2-4; the environment switch is gone
 # the four weight gradients of a transformer layer as ONE grouped launch at the end of the layer's backward (ops.gemm_group: 16 + 48 + 64 + 64
 # tiles of 256 x 256, every block walks the whole reduction, finished tiles go straight into the flat gradient buffer): no split-K slabs, no
 # slab reduction, 5 launches -> 1.  SCL_WGRAD_GROUP=0: one split-K launch per gradient + the layer's slab combine, as rounds 2-4 ran.
@@ -39,11 +27,6 @@ BATCH_SLABS = True      # decided by the A/Bs of rounds 2-4 (DESIGN.md section 3
 WGRAD_GROUP = os.environ.get("SCL_WGRAD_GROUP", "1") != "0"
 WGRAD_CARRY = os.environ.get("SCL_WGRAD_CARRY", "1") != "0"      # carry a layer's tile remainder into the next layer's launch (whole rounds of 256 tiles)
 WGRAD_GROUP_MIN_KSTEPS = 16      # from 1024 rows on (measured: 11 x 199 rows 16.2 -> 14.2 ms per step, 16 x 199 20.8 -> 17.6, 32 x 199 29.1 -> 26.1, 64 x 199 44.1 -> 42.5)
-# positional conv forward / data gradient on the LDS-resident-slab kernel (csrc/posconv.hip) instead of the grouped GEMM; 0 = the GEMM (A/B)
-POSCONV_MFMA = True      # decided by the A/Bs of rounds 2-4; the environment switch is gone
-# fc1's forward epilogue stores gelu'(pre-activation) (one erf / exp evaluation serves gelu and its derivative) and fc2's data-gradient
-# epilogue multiplies by the stored number; 0 = store the pre-activation and re-evaluate gelu' in the backward epilogue (rounds 1-2)
-GELU_DC2 = True      # decided by the A/Bs of rounds 2-4; the environment switch is gone
 # BASELINE.json configs[4] names fp8 attention: csrc/attention_fp8.hip (e4m3 operands, fp32 accumulation) for the no-grad bf16 forward.  Opt-in:
 # the reference is fp32 and the fused forward is bound by its soft-max VALU work, not by the matrix pipe (profiles/r4_attn_fp8_probe.txt).
 ATTN_FP8 = os.environ.get("SCL_ATTN_FP8", "0") == "1"
@@ -54,7 +37,6 @@ MAT_ATTN_MAX_T = 512      # the materialised path's soft-max keeps a whole score
 # fp32 scoring path above 512 frames: utterances per chunk of the materialised f32 attention such that S (and Pm) stay within this many bytes
 F32_ATTN_CHUNK_BYTES = 1 << 30
 SCORE_X3PLANES = os.environ.get("SCL_SCORE_X3PLANES", "1") != "0"      # fp32 scoring path: plain linears as one bf16 GEMM over [hi | hi | lo] x [hi | lo | hi] (forward_f32)
-CONV_WGRAD_WIDE = True      # decided by the A/Bs of rounds 2-4; the environment switch is gone
 
 
 class W2VConfig:
@@ -285,14 +267,19 @@ class Encoder:
             d["dyp_geom"].append((Q, Rp))
         nln = max(ops.layernorm_bwd_nparts(B * t) for t in Ts)
         d["ln_part"] = f32(nln * 3 * max(C, E))
-        d["ln_part2"] = f32(nln * 3 * E)      # the layer's second LayerNorm backward when the layer's reductions are batched into one launch
+        d["ln_part2"] = f32(nln * 3 * E)      # the layer's second LayerNorm backward: both reductions wait for the layer's one closing launch
         ncs = max(ops.colsum_nparts(B * (max(Ts[1:] + [T + K]) + 4)), 1) + 1      # conv bias sums run over the zero-padded dyp rows
         d["cs_part"] = f32(ncs * max(3 * E, Fd, C))
         d["qkv_bias_part"] = f32(B * 3 * E)
         d["cs_fused"] = f32(4 * (M // 200 + 2) * Fd)      # per-tile column sums written by the fc2 data-gradient GEMM (main stream only)
         d["conv0_ws"] = f32(ops.conv0_bwd_nparts(B, L, cfg.conv_kernels[0], cfg.conv_strides[0]) * C * (cfg.conv_kernels[0] + 3))
         d["conv0_stats"] = f32(B * Ts[0] * 2)   # per-frame (mean, rstd) of layer 0's LayerNorm
-        d["slab"] = None  # split-K slabs, sized on first use
+        # the weight-gradient queue (_wgrad fills it, _flush_slabs drains it at the end of a layer's backward):
+        d["wgrad_group"] = []       # this layer's gradients waiting for the grouped launch: (A, B, out, Mo, No, Kr, slot)
+        d["wgrad_pending"] = []     # tile work carried between layers: [problem, tiles, next tile, age in layers]
+        d["slab_slots"] = {}        # split-K slab buffer per slot (0..3; None = the shared one of unslotted gradients), sized on first use
+        d["slab_jobs"] = []         # slab combines of the slotted gradients waiting for the layer's one combine launch
+        d["slabs_keep"] = []        # outgrown slab buffers: recorded launch plans may still point into them
         kmax = max(cfg.conv_kernels[1:]) if len(cfg.conv_kernels) > 1 else 1
         d["dwk"] = f32(C * kmax * C)
         d["dwf"] = f32(E * (E // cfg.pos_groups) * K)
@@ -351,23 +338,33 @@ class Encoder:
         if self.wstream is not None:
             ops.stream_wait(torch.cuda.current_stream(), self.wstream)
 
-    def _wgrad(self, d, A, B_, out, Mo, No, Kr, slot=None, **kw):
+    def _slab(self, d, slot, numel):
+        """The split-K slab buffer of `slot` with room for `numel` floats.  A buffer only grows; the outgrown one is kept alive because
+        recorded launch plans may still point into it."""
+        bufs = d["slab_slots"]
+        if slot not in bufs or bufs[slot].numel() < numel:
+            if slot in bufs:
+                d["slabs_keep"].append(bufs[slot])
+            bufs[slot] = torch.empty(numel, dtype=torch.float32, device=self.dev)
+        return bufs[slot]
+
+    def _wgrad(self, d, A, B_, out, Mo, No, Kr, slot=None, queue=True, **kw):
         """out[Mo, No] (f32, contiguous) = A^T B over the Kr reduction rows; split-K when the output is small.
-        slot (0..3, BATCH_SLABS): the slabs stay in their own buffer and the combine is queued for _flush_slabs (end of the layer)."""
+        slot (0..3: the four weight gradients of a transformer layer): the gradient is queued for the layer's grouped launch, or (queue=False,
+        short reductions, SCL_WGRAD_GROUP=0) its slabs stay in the slot's own buffer and the combine is queued; _flush_slabs launches both."""
         ksteps = (Kr + 63) // 64
-        if WGRAD_GROUP and slot is not None and not kw and Kr % 64 == 0 and ksteps >= WGRAD_GROUP_MIN_KSTEPS:
-            d.setdefault("wgrad_group", []).append((A, B_, out, Mo, No, Kr, slot))      # launched by _flush_slabs at the end of the layer
+        if queue and WGRAD_GROUP and slot is not None and not kw and Kr % 64 == 0 and ksteps >= WGRAD_GROUP_MIN_KSTEPS:
+            d["wgrad_group"].append((A, B_, out, Mo, No, Kr, slot))      # launched by _flush_slabs at the end of the layer
             return
         tiles = ((Mo + 127) // 128) * ((No + 127) // 128) * kw.get("nb2", 1)
         sk = _splitk(tiles, ksteps)
         # wide tiles (gemm_w8.hip: 256 x 256 output tiles, one 8-wave block per CU): size the split for one round of the 256 CUs
         t256 = ((Mo + 255) // 256) * ((No + 255) // 256) * kw.get("nb2", 1)
-        # 12-31 tiles with a very long reduction (conv-stack weight gradients: 12 tiles, 800-6400 K steps, utterance-batched K rows): 16 slabs
-        # of >= 50 steps each on the wide ping-pong kernel instead of the 128 x 128 one
-        if t256 >= 32 or ((WGRAD_SMALL_SPLIT or (CONV_WGRAD_WIDE and ksteps >= 700)) and t256 >= 12):
-            # 12-31 tiles (out-proj: 16): up to 16 slabs fill the 256 CUs once; the 128 x 128 sizing below left 160 blocks of 25 K steps
-            # slabs: one round of the 256 CUs; at most 8 (>= 32 tiles) / 16 (12-31 tiles) / 21 (12 tiles and >= 700 K steps: the conv layers;
-            # tools/_wg probe, us incl. the slab reduction, 16 -> 21 slabs: 766 -> 677, 400 -> 358, 207 -> 184, 116 -> 102)
+        if t256 >= 12:
+            # slabs: one round of the 256 CUs; at most 8 (>= 32 tiles) / 16 (12-31 tiles; out-proj: 16 tiles, where the 128 x 128 sizing left
+            # 160 blocks of 25 K steps.  Measured in one call, three pairs, ms per step: 47.78 / 47.59 / 47.66 on the 128 x 128 sizing, 47.76 /
+            # 47.29 / 47.26 with 16 slabs; launch + slab reduction 61.4 -> 53.8 us) / 21 (12 tiles and >= 700 K steps: the conv layers, utterance-
+            # batched K rows; tools/_wg probe, us incl. the slab reduction, 16 -> 21 slabs: 766 -> 677, 400 -> 358, 207 -> 184, 116 -> 102)
             skw = max(1, min(8 if t256 >= 32 else (21 if ksteps >= 700 else 16), (256 + t256 // 2) // t256, ksteps // 8))
             if ops.gemm_wide_kind(A, B_, out, Mo, No, Kr, a_t=True, b_t=True, splitk=skw, c_split_stride=out.numel() if skw > 1 else 0, **kw):
                 sk = skw
@@ -375,19 +372,12 @@ class Encoder:
             ops.gemm(A, B_, out, Mo, No, Kr, a_t=True, b_t=True, **kw)
             return
         n = out.numel()
-        if BATCH_SLABS and slot is not None:
-            bufs = d.setdefault("slab_slots", {})
-            if slot not in bufs or bufs[slot].numel() < sk * n:
-                d.setdefault("slabs_keep", []).append(bufs.get(slot))   # recorded launch plans may still point into the old buffer
-                bufs[slot] = torch.empty(sk * n, dtype=torch.float32, device=self.dev)
-            ops.gemm(A, B_, bufs[slot], Mo, No, Kr, a_t=True, b_t=True, splitk=sk, c_split_stride=n, **kw)
-            d.setdefault("slab_jobs", []).append((bufs[slot], out, n, sk, n))
-            return
-        if d["slab"] is None or d["slab"].numel() < sk * n:
-            d.setdefault("slabs_keep", []).append(d["slab"])   # recorded launch plans may still point into the old slab
-            d["slab"] = torch.empty(sk * n, dtype=torch.float32, device=self.dev)
-        ops.gemm(A, B_, d["slab"], Mo, No, Kr, a_t=True, b_t=True, splitk=sk, c_split_stride=n, **kw)
-        ops.reduce_slabs(d["slab"], out, n, sk, n)
+        slab = self._slab(d, slot, sk * n)
+        ops.gemm(A, B_, slab, Mo, No, Kr, a_t=True, b_t=True, splitk=sk, c_split_stride=n, **kw)
+        if slot is not None:      # one combine launch per layer instead of one behind every gradient: 72 kernel boundaries per step less
+            d["slab_jobs"].append((slab, out, n, sk, n))
+        else:
+            ops.reduce_slabs(slab, out, n, sk, n)
 
     def _flush_slabs(self, d, final=True):
         """End of a layer's backward: its queued weight gradients join the pending tile work and whole rounds of 256 tiles are launched
@@ -396,38 +386,33 @@ class Encoder:
         into the NEXT layer's launch: 3 launches per 4 layers.  Everything of the previous layer is flushed here (its operands are re-used
         by the layer after this one); `final` flushes all.  SCL_WGRAD_CARRY=0: one launch of a layer's own tiles per layer.  If the list
         does not qualify the gradients run one by one on the split-K path.  Then the queued split-K combines, one launch."""
-        group = d.get("wgrad_group")
-        pend = d.setdefault("wgrad_pending", [])      # [problem, tiles, next tile, age in layers]
+        group, d["wgrad_group"] = d["wgrad_group"], []
+        pend = d["wgrad_pending"]
         for it in pend:
             it[3] += 1
         if group:
-            d["wgrad_group"] = []
             counts = [ops.gemm_group_tiles(*g[:6]) for g in group]
             if min(counts) > 0 and sum(counts) >= 96:
                 pend.extend([g[:6], c, 0, 0] for g, c in zip(group, counts))
             else:
-                global WGRAD_GROUP
-                saved, WGRAD_GROUP = WGRAD_GROUP, False
-                try:
-                    with self._side():
-                        for A, B_, out, Mo, No, Kr, slot in group:
-                            self._wgrad(d, A, B_, out, Mo, No, Kr, slot=slot)
-                finally:
-                    WGRAD_GROUP = saved
+                with self._side():
+                    for A, B_, out, Mo, No, Kr, slot in group:
+                        self._wgrad(d, A, B_, out, Mo, No, Kr, slot=slot, queue=False)
         for parts in plan_group_launches(pend, final, WGRAD_CARRY):
             with self._side():
                 ops.gemm_group_part(parts)
-        jobs = d.get("slab_jobs")
-        if jobs:
+        if d["slab_jobs"]:
             with self._side():
-                ops.reduce_slabs_multi(jobs)
+                ops.reduce_slabs_multi(d["slab_jobs"])
             d["slab_jobs"] = []
 
     def _bias_grad(self, d, dy, Mrows, N, gname):
         ops.colsum_reduce(dy, d["cs_part"], self.P.g(self.n(gname)), Mrows, N)
 
     def _ln_job(self, part, nparts, C, wname, bname, resid_bias=None):
-        """The reduction of _ln_grads as a job tuple for ops.colreduce_multi."""
+        """weight and bias of a LayerNorm are adjacent in the flat buffer: one reduction over the (dgamma | dbeta) partials, as a job
+        tuple for ops.colreduce_multi; with resid_bias also the third partial row, colsum(dres) = the bias gradient of the linear that
+        feeds the residual."""
         ow, ob = self.P.off(self.n(wname)), self.P.off(self.n(bname))
         assert ob == ow + C
         if resid_bias is None:
@@ -435,14 +420,9 @@ class Encoder:
         return (part, self.P.grad[ow:ow + 2 * C], nparts, 3 * C, self.P.g(self.n(resid_bias)), 2 * C)
 
     def _ln_grads(self, d, nparts, C, wname, bname, resid_bias=None):
-        """weight and bias of a LayerNorm are adjacent in the flat buffer: one reduction over the (dgamma | dbeta) partials;
-        with resid_bias also the third partial row, colsum(dres) = the bias gradient of the linear that feeds the residual."""
-        ow, ob = self.P.off(self.n(wname)), self.P.off(self.n(bname))
-        assert ob == ow + C
-        if resid_bias is None:
-            ops.colreduce_seg(d["ln_part"], self.P.grad[ow:ow + 2 * C], nparts, 2 * C)
-        else:
-            ops.colreduce_seg(d["ln_part"], self.P.grad[ow:ow + 2 * C], nparts, 3 * C, out2=self.P.g(self.n(resid_bias)), split=2 * C)
+        """The reduction of _ln_job over d["ln_part"] in a launch of its own (ops.colreduce_seg)."""
+        part, out, nparts, width, out2, split = (self._ln_job(d["ln_part"], nparts, C, wname, bname, resid_bias) + (None, 0))[:6]
+        ops.colreduce_seg(part, out, nparts, width, out2=out2, split=split)
 
     # ---- forward ---------------------------------------------------------------------------------
     def forward(self, x, training=True, refresh=True, step_seed=0):
@@ -477,7 +457,7 @@ class Encoder:
             self._slot(slots, dsc, None, -1, self.SITE_IN)
         # -- positional conv (grouped, weight-normed), GELU, residual (M2 head)
         ops.pad_rows(d["x0"], d["xpad"], B, T, E, T + K, K // 2)
-        if POSCONV_MFMA and ops.posconv_supported(T, K, G, Cg):      # utterance slab resident in LDS, weights streamed (csrc/posconv.hip)
+        if ops.posconv_supported(T, K, G, Cg):      # utterance slab resident in LDS, weights streamed (csrc/posconv.hip); else the grouped GEMM
             ops.posconv_mfma(d["xpad"], self.pos_wf, d["xin"][0], d["x0"], B, T, K, G, Cg, bias=self.b("encoder.pos_conv.0.bias"), c2=d["pc_pre"])
         else:
             ops.gemm(Op(d["xpad"], E, rpb=T, rbstride=(T + K) * E, cin=Cg, cout=E, bs2=Cg), Op(self.pos_wf, K * Cg, bs2=Cg * K * Cg),
@@ -525,8 +505,10 @@ class Encoder:
                 self._slot(slots, dsc, None, n, self.SITE_1)
             ops.layernorm_fwd(d["x1"][n], self.b(pn + "final_layer_norm.weight"), self.b(pn + "final_layer_norm.bias"),
                               d["h2"][n], None, d["m2"][n], d["r2"][n], M, E)
+            # fc1's epilogue stores gelu'(pre-activation) as its second output (one erf / exp evaluation serves gelu and its derivative);
+            # fc2's data-gradient epilogue multiplies by the stored number
             dsc = ops.gemm(Op(d["h2"][n], E), self.W(pn + "fc1.weight", E), d["a"][n], M, Fd, E, bias=self.b(pn + "fc1.bias"),
-                           act=ACT_GELU_DC2 if GELU_DC2 else ACT_GELU, c2=d["f"][n], drop_p=p_act, drop_seed=sseed(n, self.SITE_2))                         # dropout2 (activation)
+                           act=ACT_GELU_DC2, c2=d["f"][n], drop_p=p_act, drop_seed=sseed(n, self.SITE_2))                         # dropout2 (activation)
             if p_act > 0 and recording:
                 self._slot(slots, dsc, None, n, self.SITE_2)
             dsc = ops.gemm(Op(d["a"][n], Fd), self.W(pn + "fc2.weight", Fd), xout, M, E, Fd, bias=self.b(pn + "fc2.bias"),
@@ -577,7 +559,7 @@ class Encoder:
         Ts = cfg.conv_lens(L)
         T = Ts[-1]
         M, Tp = B * T, (T + 7) // 8 * 8
-        # above 512 frames the attention runs in chunks of `bc` utterances (the looped soft-max; S / Pm sized per chunk, <= F32_ATTN_CHUNK_BYTES)
+        # above 512 frames the attention runs in chunks of `bc` utterances (S / Pm sized per chunk, <= F32_ATTN_CHUNK_BYTES)
         long_attn = T > MAT_ATTN_MAX_T
         bc = max(1, min(B, F32_ATTN_CHUNK_BYTES // (4 * H * T * Tp))) if long_attn else B
         key = ("f32", B, L) if not long_attn else ("f32", B, L, bc)
@@ -635,21 +617,17 @@ class Encoder:
         ops.gemm(Op(d["xpad"], E, rpb=T, rbstride=(T + K) * E, cin=Cg, cout=E, bs2=Cg), Op(fw["pos"], K * Cg, bs2=Cg * K * Cg), xin, M, Cg, K * Cg,
                  nb2=G, ldc=E, c_bs2=Cg, bias=self.b("encoder.pos_conv.0.bias"), bias_bs2=Cg, act=ACT_GELU, R=d["x0"], rmode=1)
         qkv, S, Pm = d["qkv"], d["S"], d["Pm"]
+        # fp32 soft-max, as fairseq: one wave per row with the row in registers up to 512 frames, the looped kernel for longer rows
+        softmax = ops.softmax_fwd_f32_long if long_attn else ops.softmax_fwd_f32
         for n in range(cfg.layers):
             pn = "encoder.layers.%d." % n
             ln_then_lin(xin, pn + "self_attn_layer_norm.weight", pn + "self_attn_layer_norm.bias", E, pn + "self_attn.q_proj.weight", 3 * E, qkv,
                         bias=self.b(pn + "self_attn.q_proj.bias"))
-            if not long_attn:
-                ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=E), S, T, T, D, nb1=B, nb2=H, alpha=D ** -0.5,
-                         ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
-                ops.softmax_fwd_f32(S, Pm, B * H * T, T, Tp, Tp)                                               # fp32 soft-max, as fairseq (one wave per row)
-                ops.gemm(Op(Pm, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=2 * E), d["ctx"], T, D, T, b_t=True,
-                         nb1=B, nb2=H, ldc=E, c_bs1=T * E, c_bs2=D)
-            for c0 in range(0, B if long_attn else 0, bc):      # the same three steps per chunk of utterances, the looped soft-max
+            for c0 in range(0, B, bc):      # scores, soft-max, P V per chunk of utterances (up to 512 frames: one chunk of all B)
                 nb, o3 = min(bc, B - c0), c0 * T * 3 * E
                 ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + E), S, T, T, D, nb1=nb, nb2=H,
                          alpha=D ** -0.5, ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
-                ops.softmax_fwd_f32_long(S, Pm, nb * H * T, T, Tp, Tp)
+                softmax(S, Pm, nb * H * T, T, Tp, Tp)
                 ops.gemm(Op(Pm, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + 2 * E), d["ctx"], T, D, T, b_t=True,
                          nb1=nb, nb2=H, ldc=E, c_bs1=T * E, c_bs2=D, c_offset=c0 * T * E)
             lin(d["ctx"], E, pn + "self_attn.out_proj.weight", E, d["x1"], bias=self.b(pn + "self_attn.out_proj.bias"), R=xin, rmode=1)
@@ -688,8 +666,8 @@ class Encoder:
         def mask3_of(layer_list):      # dropout3 mask of the topmost active layer of the list: the bf16 gradient handed down to it carries it
             return ((sseed(layer_list[-1], self.SITE_3), p_res), layer_list[-1]) if (p_res > 0 and layer_list) else ((0, 0.0), None)
         # final LayerNorm
-        # residual-gradient buffers rotate over three (f32, bf16) pairs: a LayerNorm backward never writes the pair a weight-gradient
-        # GEMM of the same layer may still be reading on the second stream
+        # residual-gradient buffers rotate over five (f32, bf16) pairs (see bufs(): a weight gradient carried into the next layer's grouped
+        # launch reads its operands one layer late): a LayerNorm backward never writes a pair a weight-gradient GEMM may still be reading
         rot = d["dx_rot"]
         NR = len(rot)
         cur = 0
@@ -718,19 +696,16 @@ class Encoder:
             with self._side():
                 self._wgrad(d, Op(dxb, E), Op(d["a"][n], Fd), P.g(self.n(pn + "fc2.weight")), E, Fd, Mp, slot=0)
             # fc1.bias.grad = colsum(d_f): summed per tile by the GEMM that writes d_f (wide tiles), else by a pass over d_f
-            fc2_dgrad = dict(b_t=True, R=d["f"][n], rmode=2, ract=RACT_STORED if GELU_DC2 else ACT_GELU, drop_p=p_act, drop_seed=sseed(n, self.SITE_2))
-            nrows = ops.gemm_colsum_rows(Op(dxb, E), self.W(pn + "fc2.weight", Fd), d_f, M, Fd, E, **fc2_dgrad) if FUSED_BIAS_GRAD else 0
+            fc2_dgrad = dict(b_t=True, R=d["f"][n], rmode=2, ract=RACT_STORED, drop_p=p_act, drop_seed=sseed(n, self.SITE_2))
+            nrows = ops.gemm_colsum_rows(Op(dxb, E), self.W(pn + "fc2.weight", Fd), d_f, M, Fd, E, **fc2_dgrad)
             if nrows * Fd > d["cs_fused"].numel():
                 nrows = 0
             dsc = ops.gemm(Op(dxb, E), self.W(pn + "fc2.weight", Fd), d_f, M, Fd, E, colsum_part=d["cs_fused"] if nrows else None, **fc2_dgrad)
             if p_act > 0 and recording:
                 self._slot(slots, dsc, None, n, self.SITE_2)
-            jobs = []      # this layer's closing reductions (BATCH_REDUCE: one launch at the end of the layer)
+            jobs = []      # the (up to) four small column reductions that close this layer's backward: one launch at the end of the layer
             if nrows:
-                if BATCH_REDUCE:
-                    jobs.append((d["cs_fused"], P.g(self.n(pn + "fc1.bias")), nrows, Fd))
-                else:
-                    ops.colreduce(d["cs_fused"], P.g(self.n(pn + "fc1.bias")), nrows, Fd)
+                jobs.append((d["cs_fused"], P.g(self.n(pn + "fc1.bias")), nrows, Fd))
             with self._side():
                 if not nrows:
                     self._bias_grad(d, d_f, M, Fd, pn + "fc1.bias")
@@ -744,10 +719,7 @@ class Encoder:
             if p_res > 0:
                 self._slot(slots, e, ops.LN_BWD_DIN_SEED, n, self.SITE_3)
                 self._slot(slots, e, ops.LN_BWD_DOUT_SEED, n, self.SITE_1)
-            if BATCH_REDUCE:
-                jobs.append(self._ln_job(d["ln_part"], nlnM, E, pn + "final_layer_norm.weight", pn + "final_layer_norm.bias", resid_bias=pn + "fc2.bias"))
-            else:
-                self._ln_grads(d, nlnM, E, pn + "final_layer_norm.weight", pn + "final_layer_norm.bias", resid_bias=pn + "fc2.bias")
+            jobs.append(self._ln_job(d["ln_part"], nlnM, E, pn + "final_layer_norm.weight", pn + "final_layer_norm.bias", resid_bias=pn + "fc2.bias"))
             cur = (cur + 1) % NR
             (dx, dxb), (other, otherb) = rot[cur], rot[(cur + 1) % NR]      # dx = d x1
             # ---- attention:  x1 = xin + ctx Wo^T + bo
@@ -757,14 +729,11 @@ class Encoder:
             qkv, dqkv = d["qkv"][n], d["dqkv"][li & 1]
             if d["fused_attn"]:
                 e = ops.attn_bwd(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], dqkv, B, T, H, D, D ** -0.5,
-                                 bias_part=d["qkv_bias_part"] if FUSED_BIAS_GRAD else None, drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
+                                 bias_part=d["qkv_bias_part"], drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
                 if p_attn > 0:
                     self._slot(slots, e, ops.ATTN_BWD_SEED, n, self.SITE_ATTN)
-                if FUSED_BIAS_GRAD:       # q/k/v bias gradients: per-utterance column sums out of attn_bwd's accumulators, summed over B
-                    if BATCH_REDUCE:
-                        jobs.append((d["qkv_bias_part"], self._qkv_view(pn, "bias"), B, 3 * E))
-                    else:
-                        ops.colreduce(d["qkv_bias_part"], self._qkv_view(pn, "bias"), B, 3 * E)
+                # q/k/v bias gradients: per-utterance column sums out of attn_bwd's accumulators, summed over B
+                jobs.append((d["qkv_bias_part"], self._qkv_view(pn, "bias"), B, 3 * E))
             elif d["long_attn"]:      # q/k/v bias gradients: colsum_reduce below
                 e = ops.attn_bwd_long(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], dqkv, d["attn_ws"], B, T, H, D, D ** -0.5,
                                       drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
@@ -793,7 +762,7 @@ class Encoder:
                 ops.gemm(dS, Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=0), dqkv, T, D, T, a_t=True, b_t=True, alpha=sc, ldc=3 * E,
                          c_bs1=T * 3 * E, c_bs2=D, c_offset=E, **bq)                                   # dK = s dS^T Q
             with self._side():
-                if not (FUSED_BIAS_GRAD and d["fused_attn"]):
+                if not d["fused_attn"]:
                     ops.colsum_reduce(dqkv, d["cs_part"], self._qkv_view(pn, "bias"), M, 3 * E)
                 self._wgrad(d, Op(dqkv, 3 * E), Op(d["h1"][n], E), self._qkv_view(pn, "weight"), 3 * E, E, Mp, slot=3)
             ops.gemm(Op(dqkv, 3 * E), self.W(pn + "self_attn.q_proj.weight", E), d["d_h"], M, E, 3 * E, b_t=True)
@@ -802,19 +771,15 @@ class Encoder:
             # active layer below: its dropout3 mask
             dout, lyr = mask3_of([m_ for m_ in active if m_ < n])
             e = ops.layernorm_bwd(d["d_h"], xin, d["m1"][n], d["r1"][n], self.b(pn + "self_attn_layer_norm.weight"), None, dx,
-                                  other, otherb, d["ln_part2"] if BATCH_REDUCE else d["ln_part"], M, E, sum_dres=True,
+                                  other, otherb, d["ln_part2"], M, E, sum_dres=True,
                                   din=(sseed(n, self.SITE_1), p_res), dout=dout)
             if p_res > 0:
                 self._slot(slots, e, ops.LN_BWD_DIN_SEED, n, self.SITE_1)
                 if lyr is not None:
                     self._slot(slots, e, ops.LN_BWD_DOUT_SEED, lyr, self.SITE_3)
-            if BATCH_REDUCE:
-                jobs.append(self._ln_job(d["ln_part2"], nlnM, E, pn + "self_attn_layer_norm.weight", pn + "self_attn_layer_norm.bias",
-                                         resid_bias=pn + "self_attn.out_proj.bias"))
-                ops.colreduce_multi(jobs)
-            else:
-                self._ln_grads(d, nlnM, E, pn + "self_attn_layer_norm.weight", pn + "self_attn_layer_norm.bias",
-                               resid_bias=pn + "self_attn.out_proj.bias")
+            jobs.append(self._ln_job(d["ln_part2"], nlnM, E, pn + "self_attn_layer_norm.weight", pn + "self_attn_layer_norm.bias",
+                                     resid_bias=pn + "self_attn.out_proj.bias"))
+            ops.colreduce_multi(jobs)
             cur = (cur + 1) % NR
             (dx, dxb), (other, otherb) = rot[cur], rot[(cur + 1) % NR]      # dx = d xin
             self._flush_slabs(d, final=(n == active[0]))
@@ -822,7 +787,7 @@ class Encoder:
             # gradients that are final now: this layer's if nothing of it is still pending in the carried-over tile work, else the previous
             # processed layer's (everything older than one layer has been flushed)
             this_off = P.off(self.n(pn + "self_attn_layer_norm.weight"))
-            ready_off = this_off if not d.get("wgrad_pending") else prev_off
+            ready_off = this_off if not d["wgrad_pending"] else prev_off
             prev_off = this_off
             if self.on_grads_ready is not None and ready_off is not None:
                 ops.host_callback(self.on_grads_ready, ready_off)
@@ -833,7 +798,7 @@ class Encoder:
         ops.pad_rows(dx, d["dcpad"], B, T, E, T + K, pb, pre=d["pc_pre"], ract=ACT_GELU)
         ops.colsum_reduce(d["dcpad"], d["cs_part"], P.g(self.n("encoder.pos_conv.0.bias")), B * (T + K), E)
         dwf = d["dwf"]
-        if POSCONV_MFMA and ops.posconv_wgrad_supported(T, K, G, Cg):      # accumulators resident over the utterances, one wave per tap
+        if ops.posconv_wgrad_supported(T, K, G, Cg):      # accumulators resident over the utterances, one wave per tap
             ops.posconv_wgrad(d["dcpad"], pb, d["xpad"], dwf, B, T, K, G, Cg)
         else:
             self._wgrad(d, Op(d["dcpad"], E, rpb=T, rbstride=(T + K) * E, bs2=Cg, offset=pb * E),
@@ -842,7 +807,7 @@ class Encoder:
         ops.posconv_weight_bwd(dwf, self.b("encoder.pos_conv.0.weight_v"), self.b("encoder.pos_conv.0.weight_g"), self.pos_norm,
                                self.ws_small, P.g(self.n("encoder.pos_conv.0.weight_v")), P.g(self.n("encoder.pos_conv.0.weight_g")),
                                E, Cg, K)
-        if POSCONV_MFMA and ops.posconv_supported(T, K, G, Cg):
+        if ops.posconv_supported(T, K, G, Cg):
             ops.posconv_mfma(d["dcpad"], self.pos_wd, other, dx, B, T, K, G, Cg)
         else:
             ops.gemm(Op(d["dcpad"], E, rpb=T, rbstride=(T + K) * E, cin=Cg, cout=E, bs2=Cg), Op(self.pos_wd, K * Cg, bs2=Cg * K * Cg),
