@@ -385,6 +385,28 @@ int scl_attn_fwd_long(const void* qkv, void* ctx, float* lse, int B, int T, int 
 long long scl_attn_long_ws_bytes(int B, int T, int H);
 int scl_attn_bwd_long(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, void* ws, int B, int T, int H, int D,
                       float scale, float drop_p, uint32_t drop_seed, void* stream);
+/* Variable-length scoring batches (csrc/attention_varlen.hip): x [B, L] zero-padded, utterance b holds klen[b] valid frames of the T the
+ * padded length gives — the counterpart of fairseq's padding_mask (Wav2Vec2Model.forward(source, padding_mask)).  Forward only, no dropout.
+ * klen / len: int32 [B] ON THE DEVICE, 1 <= value <= T; the kernels clamp to that range for memory safety and
+ * scl_varlen_check_lengths(host copy, B, T) returns SCL_EINVAL (nothing is launched) when a value is outside it: call it before the upload.
+ * scl_attn_fwd_varlen: scl_attn_fwd_long without dropout whose key loop, K / V loads and last-block mask run to klen[b]: keys >= klen[b]
+ * are never read (they may hold NaN), blocks of 64 queries at or beyond klen[b] write zeros and leave at once (cost follows
+ * sum_b klen[b] * ceil(klen[b] / 64), not B * T^2).  ctx rows and lse of queries >= klen[b] are 0; rows < klen[b] carry the bits
+ * scl_attn_fwd_long gives for that utterance alone at T = klen[b]. */
+int scl_varlen_check_lengths(const int32_t* len_host, int B, int T);
+int scl_attn_fwd_varlen(const void* qkv, void* ctx, float* lse, const int32_t* klen, int B, int T, int H, int D, float scale, void* stream);
+/* scl_softmax_fwd_f32 / _long over the first klen[r / rows_per_utt] columns of row r (R % rows_per_utt == 0; rows_per_utt = H * T for
+ * scores [B, H, T, ldS]); columns klen..Tp-1 are written as 0 and never read.  Any T: the row stays in registers up to Tp = 512, looped
+ * (online max / sum, then the write pass) above. */
+int scl_softmax_fwd_f32_varlen(const float* S, float* P, const int32_t* klen, int64_t R, int rows_per_utt, int T, int ldS, int Tp,
+                               void* stream);
+/* x[b][t][:] = 0 for t >= len[b]; x: [B, T, C] f32 (is_f32 != 0) or bf16, 16-byte aligned, C % 8 == 0.  fairseq's
+ * index_put(features, padding_mask, 0) after post_extract_proj, and the padded rows of the head's feats. */
+int scl_zero_tail_rows(void* x, int is_f32, const int32_t* len, int B, int T, int C, void* stream);
+/* emb[b] = sum_{t < len[b]} h[b][t] / len[b] (h bf16 / f32 [B, T, C]): scl_meanpool_fwd / _f32 over the utterance's own frames, the same
+ * fixed summation order (frames t = g, g + 4, ... per partial sum g, partial sums added in order). */
+int scl_meanpool_fwd_varlen(const void* h, float* emb, const int32_t* len, int B, int T, int C, void* stream);
+int scl_meanpool_fwd_varlen_f32(const float* h, float* emb, const int32_t* len, int B, int T, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* feature-extractor layer 0 (Conv1d(1,C,10,5) + LayerNorm + GELU), fused fwd / bwd            */

@@ -134,6 +134,8 @@ def _score_loop(dataset, model, device, batch_size, fn, workers=None):
     if workers is None:
         workers = max(1, int(os.environ.get("SCL_EVAL_THREADS", "8")))
     model.eval()
+    if getattr(getattr(dataset, "dataset", dataset), "padding_type", None) == "none":      # the dataset itself, or the Subset of a rank
+        return _score_loop_varlen(dataset, model, device, batch_size, fn, workers)
     n = len(dataset)
     if workers <= 1 or n == 0:
         loader = DataLoader(dataset, batch_size, shuffle=False, drop_last=False)
@@ -212,6 +214,65 @@ def _score_loop(dataset, model, device, batch_size, fn, workers=None):
     sys.setswitchinterval(old_switch)
 
 
+def _score_loop_varlen(dataset, model, device, batch_size, fn, workers):
+    """--padding_type none: every utterance at its own length.  The list is walked in windows of VARLEN_WINDOW * batch_size utterances; the
+    thread pool decodes window i + 1 while window i is scored.  A decoded window is cut into length-sorted batches
+    (scl_amd.pack.plan_varlen_batches), each batch goes to the model as a zero-padded pinned [count, Lpad] tensor plus its sample
+    counts, results come back by asynchronous copies, and once a window is complete its rows are handed to `fn` in protocol order — after
+    the NEXT window's batches have been launched, so the GPU does not wait for the host's formatting.  `fn` receives what the model
+    returns with rows for the whole window: the log-probs, or (log-probs, None, emb) (no emitter reads feats)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from scl_amd.pack import VARLEN_MAX_SAMPLES, VARLEN_WINDOW, plan_varlen_batches
+    n = len(dataset)
+    use_gpu = torch.device(device).type == "cuda"
+    win = VARLEN_WINDOW * max(1, batch_size)
+    starts = list(range(0, n, win))
+    pending = None      # the previous window: ([(indices, results on the host)] per batch, last copy's event, ids, first index)
+
+    def emit(batches, ev, ids, w0):
+        if ev is not None:
+            ev.synchronize()
+        cnt = len(ids)
+        tup = isinstance(batches[0][1], tuple)
+        logp = torch.empty(cnt, batches[0][1][0].shape[1] if tup else batches[0][1].shape[1])
+        emb = torch.empty(cnt, batches[0][1][2].shape[1]) if tup else None
+        for idx, res in batches:
+            rows = torch.tensor([i - w0 for i in idx])
+            logp[rows] = res[0] if tup else res
+            if tup:
+                emb[rows] = res[2]
+        fn((logp, None, emb) if tup else logp, ids)
+
+    with ThreadPoolExecutor(max_workers=max(1, workers), thread_name_prefix="scl-eval") as pool, torch.no_grad():
+        submit = lambda w0: [pool.submit(dataset.__getitem__, i) for i in range(w0, min(w0 + win, n))]
+        futs = submit(starts[0]) if starts else []
+        for wi, w0 in enumerate(starts):
+            items = [f.result() for f in futs]
+            futs = submit(starts[wi + 1]) if wi + 1 < len(starts) else []
+            xs, ids = [it[0] for it in items], [it[1] for it in items]
+            done, ev = [], None
+            for idx, lpad in plan_varlen_batches([int(x.shape[0]) for x in xs], batch_size):
+                host = torch.zeros((len(idx), lpad), dtype=torch.float32, pin_memory=use_gpu)
+                lens = []
+                for r, i in enumerate(idx):
+                    host[r, : xs[i].shape[0]] = xs[i]
+                    lens.append(int(xs[i].shape[0]))
+                res = model(host.to(device, non_blocking=True), lengths=lens)
+                keep = lambda t: torch.empty(t.shape, dtype=t.dtype, pin_memory=use_gpu).copy_(t, non_blocking=True)
+                res = (keep(res[0]), None, keep(res[2])) if isinstance(res, (tuple, list)) else keep(res)
+                if use_gpu:
+                    ev = torch.cuda.Event()
+                    ev.record()
+                done.append(([w0 + i for i in idx], res))
+            if pending is not None:
+                emit(*pending)
+            pending = (done, ev, ids, w0)
+        if pending is not None:
+            emit(*pending)
+    print("variable-length scoring: %d utterances, %d cut to %d samples"
+          % (n, getattr(getattr(dataset, "dataset", dataset), "n_cut", 0), VARLEN_MAX_SAMPLES))
+
+
 def produce_evaluation_file(dataset, model, device, save_path, batch_size=10):
     """'<utt> <logp0> <logp1>' per line (reference main.py:161-180)."""
     def emit(res, ids):
@@ -281,7 +342,8 @@ def build_parser():
     p.add_argument("--weight_decay", type=float, default=0.0001)
     p.add_argument("--loss", type=str, default="weighted_CCE")
     p.add_argument("--config", type=str, default="configs/config.yaml")
-    p.add_argument("--padding_type", type=str, default="zero", help="zero or repeat")
+    p.add_argument("--padding_type", type=str, default="zero",
+                   help="zero or repeat: cut / pad every clip to its fixed length; none (--eval only): score every utterance at its own length")
     p.add_argument("--is_train", type=bool, default=True)
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--model_path", type=str, default=None)
@@ -301,6 +363,9 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.padding_type == "none" and not args.eval:
+        sys.exit("main.py: --padding_type none scores whole utterances and needs --eval (alone or with --predict / --emb); "
+                 "training packs clips of one fixed length: use zero or repeat")
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
@@ -333,6 +398,9 @@ def main(argv=None):
         sys.exit("main.py: model wav2vec2_btse needs the YAML key model.bio_tokenizer = '<module>:<callable>' (waveforms [bz, L] numpy, "
                  "sample_rate) -> equal-length token rows; the reference's biosegment package does not exist, so %s cannot run as shipped "
                  "(scl_amd/model_btse.py; bench.py --model wav2vec2_btse feeds synthetic tokens)" % args.config)
+    if args.padding_type == "none" and config["model"]["name"] != "wav2vec2_linear_nll":
+        sys.exit("main.py: --padding_type none needs a model that takes per-utterance lengths: wav2vec2_linear_nll only (%s has no padding "
+                 "mask in its back-end); use --padding_type zero or repeat" % config["model"]["name"])
     model = MODEL_REGISTRY[config["model"]["name"]](config["model"], device, seed=args.seed, rank=rank)
     print("nb_params:", sum(p.numel() for p in model.parameters()))
 

@@ -11,6 +11,7 @@ Layout decisions (MI355X-first, not fairseq's):
     P[B,H,T,Tp] (41 MB at B=32) and reused by the backward — HBM is 288 GB, recompute buys nothing here;
   * every buffer is allocated once per (B, L) and reused across steps (no allocator traffic).
 """
+import collections
 import contextlib
 import os
 
@@ -37,6 +38,30 @@ MAT_ATTN_MAX_T = 512      # the materialised path's soft-max keeps a whole score
 # fp32 scoring path above 512 frames: utterances per chunk of the materialised f32 attention such that S (and Pm) stay within this many bytes
 F32_ATTN_CHUNK_BYTES = 1 << 30
 SCORE_X3PLANES = os.environ.get("SCL_SCORE_X3PLANES", "1") != "0"      # fp32 scoring path: plain linears as one bf16 GEMM over [hi | hi | lo] x [hi | lo | hi] (forward_f32)
+
+
+VARLEN_SETS = 4      # buffer sets kept per path for variable-length scoring batches (every distinct padded shape is a set of its own)
+
+
+class VarlenSets(collections.OrderedDict):
+    """Least-recently-used store of the buffer sets of variable-length batches: at most VARLEN_SETS entries; an evicted set is dropped
+    (its device memory returns to the allocator once no launch plan refers to it).  `on_evict(key)` lets the owner drop what it keeps
+    per key besides."""
+
+    def __init__(self, on_evict=None):
+        super().__init__()
+        self.on_evict = on_evict
+
+    def get_or_make(self, key, make):
+        if key in self:
+            self.move_to_end(key)
+            return self[key]
+        while len(self) >= VARLEN_SETS:
+            old, _ = self.popitem(last=False)
+            if self.on_evict is not None:
+                self.on_evict(old)
+        self[key] = make()
+        return self[key]
 
 
 class W2VConfig:
@@ -67,6 +92,13 @@ class W2VConfig:
             L = (L - k) // s + 1
             out.append(L)
         return out
+
+    def min_samples(self):
+        """The shortest clip that yields one frame (400 samples for the XLS-R stack)."""
+        L = 1
+        for k, s in zip(reversed(self.conv_kernels), reversed(self.conv_strides)):
+            L = (L - 1) * s + k
+        return L
 
 
 def param_specs(cfg, prefix="ssl_model.model."):
@@ -145,6 +177,9 @@ class Encoder:
         self.cfg, self.P, self.pre = cfg, P, prefix
         self.dev = P.device
         self._bufs = {}
+        # variable-length scoring batches (forward / forward_f32 with `frames`): every padded shape is a buffer set of its own, so these
+        # live in two small LRUs (bf16 path, fp32 path) instead of the keep-forever table of the fixed shapes
+        self._vbufs, self._vbufs_f32 = VarlenSets(), VarlenSets()
         C, E, K, G = cfg.conv_dim, cfg.embed, cfg.pos_k, cfg.pos_groups
         Cg = E // G
         bf = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=self.dev)
@@ -193,10 +228,17 @@ class Encoder:
         return self.P.f32(self.n(name))
 
     # ---- buffers ---------------------------------------------------------------------------------
-    def bufs(self, B, L):
+    def bufs(self, B, L, varlen=False):
+        """The buffer set of a [B, L] batch.  varlen: the set of a variable-length scoring batch — streaming attention whatever T is
+        (lse, no T x T buffers), kept in the LRU."""
+        if varlen:
+            return self._vbufs.get_or_make((B, L), lambda: self._make_bufs(B, L, True))
         key = (B, L)
-        if key in self._bufs:
-            return self._bufs[key]
+        if key not in self._bufs:
+            self._bufs[key] = self._make_bufs(B, L, False)
+        return self._bufs[key]
+
+    def _make_bufs(self, B, L, varlen):
         cfg, dev = self.cfg, self.dev
         C, E, H, Fd, K = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k
         Ts = cfg.conv_lens(L)
@@ -227,6 +269,11 @@ class Encoder:
         d["fused_attn"] = (E // H == 64) and T <= 224      # scores stay on chip (csrc/attention.hip); else materialised path
         # streaming attention (csrc/attention_long.hip): above 512 frames, or from 225 frames with SCL_ATTN_LONG=1
         d["long_attn"] = (E // H == 64) and not d["fused_attn"] and (T > MAT_ATTN_MAX_T or ATTN_LONG)
+        if varlen:
+            if E // H != 64:
+                raise SclError("encoder: variable-length batches on the bf16 path run the streaming attention, which takes head dim 64 "
+                               "(got %d); the fp32 scoring path takes any head dim" % (E // H))
+            d["fused_attn"], d["long_attn"] = False, True
         if T > MAT_ATTN_MAX_T and not d["long_attn"]:
             raise SclError("encoder: %d frames need the streaming attention, which takes head dim 64 (got %d); other head dims are limited "
                            "to %d frames (%d samples)" % (T, E // H, MAT_ATTN_MAX_T, L))
@@ -283,7 +330,6 @@ class Encoder:
         kmax = max(cfg.conv_kernels[1:]) if len(cfg.conv_kernels) > 1 else 1
         d["dwk"] = f32(C * kmax * C)
         d["dwf"] = f32(E * (E // cfg.pos_groups) * K)
-        self._bufs[key] = d
         return d
 
     # ---- element dropout: seeds --------------------------------------------------------------------
@@ -425,17 +471,22 @@ class Encoder:
         ops.colreduce_seg(part, out, nparts, width, out2=out2, split=split)
 
     # ---- forward ---------------------------------------------------------------------------------
-    def forward(self, x, training=True, refresh=True, step_seed=0):
-        """x [B, L] fp32 contiguous on the GPU -> (enc_out bf16 [B*T, E], ctx).  step_seed: seed of this step's element-dropout masks."""
+    def forward(self, x, training=True, refresh=True, step_seed=0, frames=None):
+        """x [B, L] fp32 contiguous on the GPU -> (enc_out bf16 [B*T, E], ctx).  step_seed: seed of this step's element-dropout masks.
+        frames (no-grad scoring only): int32 [B] on the GPU, the valid frames of each zero-padded utterance — rows beyond them are zeroed
+        before the positional convolution and take no part in any soft-max (scl_attn_fwd_varlen in every layer); output rows beyond them
+        are finite and meaningless.  A recorded plan keeps the tensor's address: overwrite it in place before a replay."""
         cfg, P = self.cfg, self.P
         B, L = x.shape
+        if frames is not None and (training or torch.is_grad_enabled()):
+            raise NotImplementedError("encoder: per-utterance frame counts are a scoring mode (eval, torch.no_grad()); there is no backward")
         p_res, p_attn, p_act, p_in = self.drop_probs(training)
         slots = []
         sseed = lambda layer, site: self.site_seed(step_seed, layer, site)
         recording = ops._rec() is not None
         if refresh:
             self.refresh_weights()
-        d = self.bufs(B, L)
+        d = self.bufs(B, L, varlen=frames is not None)
         C, E, H, Fd, K, G = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k, cfg.pos_groups
         D, Cg = E // H, E // G
         Ts, T, M, Tp = d["Ts"], d["T"], d["M"], d["Tp"]
@@ -456,6 +507,8 @@ class Encoder:
         if p_in > 0 and recording:
             self._slot(slots, dsc, None, -1, self.SITE_IN)
         # -- positional conv (grouped, weight-normed), GELU, residual (M2 head)
+        if frames is not None:
+            ops.zero_tail_rows(d["x0"], frames, B, T, E)      # fairseq: features[padding_mask] = 0
         ops.pad_rows(d["x0"], d["xpad"], B, T, E, T + K, K // 2)
         if ops.posconv_supported(T, K, G, Cg):      # utterance slab resident in LDS, weights streamed (csrc/posconv.hip); else the grouped GEMM
             ops.posconv_mfma(d["xpad"], self.pos_wf, d["xin"][0], d["x0"], B, T, K, G, Cg, bias=self.b("encoder.pos_conv.0.bias"), c2=d["pc_pre"])
@@ -479,7 +532,9 @@ class Encoder:
             ops.gemm(Op(d["h1"][n], E), self.W(pn + "self_attn.q_proj.weight", E), d["qkv"][n], M, 3 * E, E,
                      bias=self.b(pn + "self_attn.q_proj.bias"))  # q,k,v biases are adjacent in the flat buffer
             qkv = d["qkv"][n]
-            if d["fused_attn"] and ATTN_FP8 and not training and T <= 256:
+            if frames is not None:
+                ops.attn_fwd_varlen(qkv, d["ctx"][n], d["lse"][n], frames, B, T, H, D, D ** -0.5)
+            elif d["fused_attn"] and ATTN_FP8 and not training and T <= 256:
                 ops.attn_fwd_fp8(qkv, d["ctx"][n], d["lse"][n], B, T, H, D, D ** -0.5)      # configs[4]'s fp8 attention (opt-in, no-grad forward)
             elif d["fused_attn"]:
                 e = ops.attn_fwd(qkv, d["ctx"][n], d["lse"][n], B, T, H, D, D ** -0.5, drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
@@ -547,11 +602,12 @@ class Encoder:
             fw["w3"][name] = w3
         return w3
 
-    def forward_f32(self, x):
+    def forward_f32(self, x, frames=None):
         """The encoder forward with fp32 activations and the fp32 master weights, every contraction on the exact-fp32 matrix-core
         kernel (csrc/gemm_f32.hip) — what main.py --eval / --predict / --emb score with: the reference runs fp32 end to end
         (main.py:161-214, no autocast) and north_star asks for scores within 1e-3 of it, which bf16 operands cannot give.
-        Forward only, one layer's activations live at a time.  x [B, L] fp32 on the GPU -> enc_out f32 [B*T, E]."""
+        Forward only, one layer's activations live at a time.  x [B, L] fp32 on the GPU -> enc_out f32 [B*T, E].
+        frames: as in forward() — int32 [B] on the GPU, valid frames per zero-padded utterance (any head dim)."""
         cfg, P = self.cfg, self.P
         B, L = x.shape
         C, E, H, Fd, K, G = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k, cfg.pos_groups
@@ -563,16 +619,22 @@ class Encoder:
         long_attn = T > MAT_ATTN_MAX_T
         bc = max(1, min(B, F32_ATTN_CHUNK_BYTES // (4 * H * T * Tp))) if long_attn else B
         key = ("f32", B, L) if not long_attn else ("f32", B, L, bc)
-        if key not in self._bufs:
+
+        def make():
             f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.dev)
             slack = 128 * max(C, E)
-            self._bufs[key] = dict(z=[f32(B * t * C + slack) for t in Ts], y=f32(B * Ts[1] * C), stat=f32(2 * B * Ts[1]), h=f32(M * max(C, E) + slack),
+            return dict(z=[f32(B * t * C + slack) for t in Ts], y=f32(B * Ts[1] * C), stat=f32(2 * B * Ts[1]), h=f32(M * max(C, E) + slack),
                                    x0=f32(M * E), xpad=torch.zeros(B * (T + K) * E + slack, device=self.dev), xa=f32(M * E), xb=f32(M * E),
                                    x1=f32(M * E), qkv=f32(M * 3 * E + slack), S=f32(bc * H * T * Tp), Pm=torch.zeros(bc * H * T * Tp + 1024, device=self.dev),
                                    ctx=f32(M * E + slack), a=f32(M * Fd + slack), out=f32(M * E),
                                    a3=torch.empty(M * 3 * max(C, E, Fd) + 2 * slack, dtype=torch.bfloat16, device=self.dev),
                                    a3b=torch.empty(M * 3 * Fd + 2 * slack, dtype=torch.bfloat16, device=self.dev))
-        d = self._bufs[key]
+        if frames is not None:
+            d = self._vbufs_f32.get_or_make(key, make)
+        else:
+            if key not in self._bufs:
+                self._bufs[key] = make()
+            d = self._bufs[key]
         fw = self._f32_weights()
         Wf = lambda name, ld: Op(P.flat, ld, offset=P.off(self.n(name)))
         # Round 6: the plain linears (flat K) as ONE bf16 GEMM over 3 K on the wide-tile kernel — left operand [hi | hi | lo] written by a
@@ -612,6 +674,8 @@ class Encoder:
             ops.layernorm_fwd(d["y"], self.b(fe % i + "2.1.weight"), self.b(fe % i + "2.1.bias"), None, d["z"][i], mean, rstd, B * Tout, C, act=1)
         ln_then_lin(d["z"][-1], "layer_norm.weight", "layer_norm.bias", C, "post_extract_proj.weight", E, d["x0"], bias=self.b("post_extract_proj.bias"))
         # positional conv: zero-padded rows (the pad rows of xpad are never written), GELU, residual
+        if frames is not None:
+            ops.zero_tail_rows(d["x0"], frames, B, T, E)      # fairseq: features[padding_mask] = 0
         d["xpad"][: B * (T + K) * E].view(B, T + K, E)[:, K // 2: K // 2 + T].copy_(d["x0"].view(B, T, E))
         xin, xout = d["xa"], d["xb"]
         ops.gemm(Op(d["xpad"], E, rpb=T, rbstride=(T + K) * E, cin=Cg, cout=E, bs2=Cg), Op(fw["pos"], K * Cg, bs2=Cg * K * Cg), xin, M, Cg, K * Cg,
@@ -627,7 +691,10 @@ class Encoder:
                 nb, o3 = min(bc, B - c0), c0 * T * 3 * E
                 ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + E), S, T, T, D, nb1=nb, nb2=H,
                          alpha=D ** -0.5, ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
-                softmax(S, Pm, nb * H * T, T, Tp, Tp)
+                if frames is not None:      # keys beyond the utterance's frames take no part (any T: one entry point)
+                    ops.softmax_fwd_f32_varlen(S, Pm, frames, nb * H * T, H * T, T, Tp, Tp, klen_offset=c0)
+                else:
+                    softmax(S, Pm, nb * H * T, T, Tp, Tp)
                 ops.gemm(Op(Pm, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + 2 * E), d["ctx"], T, D, T, b_t=True,
                          nb1=nb, nb2=H, ldc=E, c_bs1=T * E, c_bs2=D, c_offset=c0 * T * E)
             lin(d["ctx"], E, pn + "self_attn.out_proj.weight", E, d["x1"], bias=self.b(pn + "self_attn.out_proj.bias"), R=xin, rmode=1)

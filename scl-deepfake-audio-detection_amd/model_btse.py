@@ -66,7 +66,9 @@ class Model(FrontHeadModel):
         lens = torch.tensor([len(t) for t in toks], dtype=torch.int32)
         return torch.from_numpy(np.asarray(toks, dtype=np.int32)), lens          # ragged lists fail here, as torch.IntTensor(bio) does
 
-    def forward(self, x, bio=None, bio_lengths=None, y=None):
+    def forward(self, x, bio=None, bio_lengths=None, y=None, lengths=None):
+        if lengths is not None:
+            raise NotImplementedError("model_btse: " + self.VARLEN_REFUSAL)
         if bio is None:
             bio, bio_lengths = self.get_Bio(x if x.dim() == 2 else x[:, :, 0], 16000)
         self.__dict__["_bio"] = (bio, bio_lengths)

@@ -225,7 +225,13 @@ class FrontHeadModel(nn.Module):
             st["plans"][pk] = dict(calls=ops.stop_recording(), enc_slots=enc_slots)
 
     # forward / loss --------------------------------------------------------------------------------
-    def forward(self, x):
+    VARLEN_REFUSAL = ("variable-length batches (forward(x, lengths), main.py --padding_type none) are implemented for the "
+                      "wav2vec2_linear_nll plugin only: this back-end has no padding mask; score fixed-length clips (--padding_type "
+                      "zero / repeat) or one utterance per call")
+
+    def forward(self, x, lengths=None):
+        if lengths is not None:
+            raise NotImplementedError("%s: %s" % (type(self).__module__.split(".")[-1], self.VARLEN_REFUSAL))
         if x.dim() == 3:
             x = x[:, :, 0]
         x = x.to(device=self.device, dtype=torch.float32).contiguous()

@@ -4,6 +4,8 @@ numeric step executed by the HIP kernels behind the C ABI.
 
     Model(args: dict, device, is_train=True)
     forward(x [bz, L] fp32) -> (log_probs [bz,2], feats [bz,T,128], emb [bz,128])   (or log_probs when not is_train)
+    forward(x, lengths=[n_0, ...])   scoring only (eval, no_grad): row b holds n_b samples followed by zeros and gets the result it gets
+                                     when scored alone at its own length; feats rows beyond its frames are 0
     loss(output, feats, emb, labels, config, info=None) -> dict of 0-d tensors, summed and .backward()-ed by the caller
 
 State-dict keys equal the reference's (ssl_model.model.<fairseq keys>, LL.*, first_bn.*, first_bn1.*,
@@ -17,7 +19,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .encoder import Encoder, W2VConfig, param_specs
+from .encoder import Encoder, VarlenSets, W2VConfig, param_specs
 from .lib import ACT_LEAKY, ACT_RELU
 from .ops import Op
 from .params import FlatParams, register_by_name
@@ -140,6 +142,9 @@ class Model(nn.Module):
         self._anchor = torch.zeros((), device=self.device, requires_grad=True)
         self._hbufs = {}
         self._states = {}
+        # variable-length scoring batches (forward(x, lengths)): state, head buffers and launch plans per padded shape, least recently
+        # used of at most four; an evicted shape takes its encoder buffer set with it
+        self._vstates = VarlenSets(on_evict=lambda key: self.encoder._vbufs.pop(key, None))
         self._step_seed = dropout_stream_seed(seed, rank)   # head dropout masks differ per --seed and per data-parallel rank
         self.out_dim = self.cfg.embed
         self.grad_sync = None   # scl_amd.parallel.GradSync when data-parallel (set by FusedAdamW)
@@ -169,22 +174,27 @@ class Model(nn.Module):
             self.P.bf16_version = self.P.version
 
     # forward ---------------------------------------------------------------------------------------
-    def _head_bufs(self, B, T):
+    def _head_bufs(self, B, T, keep=True):
         key = (B, T)
+        if not keep:      # a variable-length state owns its head buffers (freed with it)
+            return self._make_head_bufs(B, T)
         if key not in self._hbufs:
-            M, dev = B * T, self.device
-            bf = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
-            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-            # the frame-level head (three 128 x 128 linears) runs in f32 on the exact-fp32 GEMM with the fp32 master weights, forward and
-            # backward: 3.8 GFLOP per step at batch 64, and its gradients then meet the same bound as every other tensor (the
-            # mean-pool backward hands every frame of an utterance the SAME row — rounded to bf16 its error is systematic over T)
-            hd = f32 if HEAD_F32 else bf
-            self._hbufs[key] = dict(r0=hd(M * HEAD_DIM + 1024), pre=[hd(M * HEAD_DIM) for _ in range(3)],
-                                    h=[hd(M * HEAD_DIM + 1024) for _ in range(3)], dpre=[hd(M * HEAD_DIM + 1024) for _ in range(3)],
-                                    dfe=f32(M * HEAD_DIM), dfe_bf=bf(M * HEAD_DIM + 1024), denc=bf(M * self.cfg.embed),
-                                    demb=f32(B * HEAD_DIM), ws=f32(B * N_CLASS + 16),
-                                    cs=f32(ops.colsum_reduce_nparts(M, 8) * max(HEAD_DIM, 8)), dW=f32(HEAD_DIM * max(HEAD_DIM, self.cfg.embed)))
+            self._hbufs[key] = self._make_head_bufs(B, T)
         return self._hbufs[key]
+
+    def _make_head_bufs(self, B, T):
+        M, dev = B * T, self.device
+        bf = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        # the frame-level head (three 128 x 128 linears) runs in f32 on the exact-fp32 GEMM with the fp32 master weights, forward and
+        # backward: 3.8 GFLOP per step at batch 64, and its gradients then meet the same bound as every other tensor (the
+        # mean-pool backward hands every frame of an utterance the SAME row — rounded to bf16 its error is systematic over T)
+        hd = f32 if HEAD_F32 else bf
+        return dict(r0=hd(M * HEAD_DIM + 1024), pre=[hd(M * HEAD_DIM) for _ in range(3)],
+                    h=[hd(M * HEAD_DIM + 1024) for _ in range(3)], dpre=[hd(M * HEAD_DIM + 1024) for _ in range(3)],
+                    dfe=f32(M * HEAD_DIM), dfe_bf=bf(M * HEAD_DIM + 1024), denc=bf(M * self.cfg.embed),
+                    demb=f32(B * HEAD_DIM), ws=f32(B * N_CLASS + 16),
+                    cs=f32(ops.colsum_reduce_nparts(M, 8) * max(HEAD_DIM, 8)), dW=f32(HEAD_DIM * max(HEAD_DIM, self.cfg.embed)))
 
     def _state(self, B, L):
         """Static per-(B, L) buffers at the autograd boundary, so recorded launch plans stay valid."""
@@ -196,11 +206,37 @@ class Model(nn.Module):
                                      d_logp=f32(B, N_CLASS), d_feats=f32(B, T, HEAD_DIM), d_emb=f32(B, HEAD_DIM), plans={})
         return self._states[key]
 
-    def _run_forward(self, x):
+    def _varlen_state(self, B, L):
+        """_state for a variable-length scoring batch: forward-only buffers, the frame counts (a device buffer of fixed address, overwritten
+        before every replay of the shape's plan) and the shape's own head buffers."""
+        def make():
+            T = self.cfg.conv_lens(L)[-1]
+            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
+            return dict(T=T, x=f32(B, L), feats=f32(B, T, HEAD_DIM), emb=f32(B, HEAD_DIM), logp=f32(B, N_CLASS),
+                        frames=torch.ones(B, dtype=torch.int32, device=self.device), hb=self._head_bufs(B, T, keep=False), plans={})
+        return self._vstates.get_or_make((B, L), make)
+
+    def _frames(self, lengths, B, L):
+        """Sample counts of a zero-padded batch -> frame counts as an int32 device tensor (validated on the host first).  Counts below the
+        shortest clip that yields a frame count as that clip: its zero padding is part of the signal, as for a file padded on disk."""
+        lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        lo = self.cfg.min_samples()
+        if len(lengths) != B or L < lo or any(n < 1 or n > L for n in lengths):
+            raise ValueError("lengths: need one sample count in 1..%d per row of the [%d, %d] batch (at least %d samples per row), got %r"
+                             % (L, B, L, lo, lengths))
+        frames = ops.check_lengths([self.cfg.conv_lens(max(n, lo))[-1] for n in lengths], self.cfg.conv_lens(L)[-1])
+        host = torch.tensor(frames, dtype=torch.int32)
+        return (host.pin_memory() if self.device.type == "cuda" else host).to(self.device, non_blocking=True)
+
+    def _run_forward(self, x, frames=None):
         B, L = x.shape
         training = bool(self.training)
         ssl_train = False if self.flag_fix_ssl else bool(self.is_train and training)   # SURVEY.md §3.2 quirk
-        st = self._state(B, L)
+        if frames is not None:
+            st = self._varlen_state(B, L)
+            st["frames"].copy_(frames)
+        else:
+            st = self._state(B, L)
         st["x"].copy_(x)
         drop = DROP_P if training else 0.0
         self._step_seed = (self._step_seed * 1664525 + 1013904223) & 0x7FFFFFFF
@@ -226,10 +262,11 @@ class Model(nn.Module):
 
     def _forward_kernels(self, st, B, L, ssl_train, drop, seeds):
         P, E = self.P, self.cfg.embed
-        enc_out, ectx = self.encoder.forward(st["x"], training=ssl_train, refresh=False, step_seed=self._step_seed)
+        frames = st.get("frames")      # a variable-length state (scoring only)
+        enc_out, ectx = self.encoder.forward(st["x"], training=ssl_train, refresh=False, step_seed=self._step_seed, frames=frames)
         T = ectx["d"]["T"]
         M = B * T
-        hb = self._head_bufs(B, T)
+        hb = st["hb"] if frames is not None else self._head_bufs(B, T)
         feats, emb, logp = st["feats"], st["emb"], st["logp"]
         W = lambda name, ld: Op(P.bf16, ld, offset=P.off(name))
         # feats = LL(x) (pre-ReLU tensor is what SupCon sees, linear_nll:127-129), r0 = relu(feats)
@@ -242,7 +279,11 @@ class Model(nn.Module):
                            drop_seed=seeds[j], x3=False)
             drop_descs.append(dsc)
             prev = hb["h"][j]
-        ops.meanpool_fwd(prev, emb, B, T, HEAD_DIM)
+        if frames is not None:
+            ops.zero_tail_rows(feats, frames, B, T, HEAD_DIM)
+            ops.meanpool_fwd_varlen(prev, emb, frames, B, T, HEAD_DIM)
+        else:
+            ops.meanpool_fwd(prev, emb, B, T, HEAD_DIM)
         ops.utt_head_fwd(emb, P.f32("backend.m_utt_level.weight"), P.f32("backend.m_utt_level.bias"), logp, B, HEAD_DIM, N_CLASS)
         saved = dict(ectx=ectx, hb=hb, B=B, L=L, T=T, drop=drop, feats=feats, emb=emb, logp=logp, enc_out=enc_out, st=st)
         return saved, drop_descs
@@ -307,12 +348,12 @@ class Model(nn.Module):
             enc_slots = self.encoder.backward(sv["ectx"], hb["denc"])
         return dict(drop_descs=drop_descs, meanpool_entry=mp_entry, enc_slots=enc_slots)
 
-    def _score_fp32(self, x):
+    def _score_fp32(self, x, frames=None):
         """Scoring forward (no grad, eval mode): fp32 activations, fp32 master weights, exact-fp32 GEMMs end to end — the
         reference's precision (main.py:161-214), for scores / embeddings within 1e-3 of it."""
         P, E = self.P, self.cfg.embed
         B = x.shape[0]
-        enc, T = self.encoder.forward_f32(x)
+        enc, T = self.encoder.forward_f32(x, frames)
         M = B * T
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
         Wf = lambda name, ld: Op(P.flat, ld, offset=P.off(name))
@@ -322,30 +363,41 @@ class Model(nn.Module):
             ops.gemm(Op(h0, HEAD_DIM), Wf("backend.m_frame_level.%d.weight" % idx, HEAD_DIM), h1, M, HEAD_DIM, HEAD_DIM,
                      bias=P.f32("backend.m_frame_level.%d.bias" % idx), act=ACT_LEAKY)
             h0, h1 = h1, h0
-        emb = h0.view(B, T, HEAD_DIM).mean(dim=1)
+        if frames is not None:      # the utterance's own frames: feats rows beyond them are 0, the mean runs over them alone
+            ops.zero_tail_rows(feats, frames, B, T, HEAD_DIM)
+            emb = f32(B, HEAD_DIM)
+            ops.meanpool_fwd_varlen(h0, emb, frames, B, T, HEAD_DIM)
+        else:
+            emb = h0.view(B, T, HEAD_DIM).mean(dim=1)
         logp = f32(B, N_CLASS)
         ops.utt_head_fwd(emb.contiguous(), P.f32("backend.m_utt_level.weight"), P.f32("backend.m_utt_level.bias"), logp, B, HEAD_DIM, N_CLASS)
         return logp, feats, emb
 
-    def _forward(self, x):
+    def _forward(self, x, lengths=None):
         if x.dim() == 3:
             x = x[:, :, 0]
         x = x.to(device=self.device, dtype=torch.float32).contiguous()   # main.py:60 hands over a transposed view
+        frames = None
+        if lengths is not None:
+            if torch.is_grad_enabled() or self.training:
+                raise NotImplementedError("forward(x, lengths) is a scoring mode: call it on model.eval() under torch.no_grad() "
+                                          "(the variable-length kernels have no backward)")
+            frames = self._frames(lengths, x.shape[0], x.shape[1])
         if torch.is_grad_enabled() and any(p.requires_grad for p in (self._anchor,)):
             out, feats, emb = _ModelFn.apply(self, x, self._anchor)
         elif not self.training and SCORE_FP32:
-            out, feats, emb = self._score_fp32(x)
+            out, feats, emb = self._score_fp32(x, frames)
         else:
-            out, feats, emb, _ = self._run_forward(x)
+            out, feats, emb, _ = self._run_forward(x, frames)
             out, feats, emb = out.clone(), feats.clone(), emb.clone()
         if self.is_train:
             return out, feats, emb
         return out
 
-    def forward(self, x_big):
+    def forward(self, x_big, lengths=None):
         if not self.is_train:
             print("Inference mode")  # linear_nll:152
-        return self._forward(x_big)
+        return self._forward(x_big, lengths)
 
     # loss ------------------------------------------------------------------------------------------
     def loss(self, output, feats, emb, labels, config, info=None):

@@ -494,6 +494,45 @@ def attn_fwd_long(qkv, ctx, lse, B, T, H, D, scale, drop_p=0.0, drop_seed=0):
     return _call("scl_attn_fwd_long", _p(qkv), _p(ctx), _p(lse), B, T, H, D, float(scale), float(drop_p), int(drop_seed), _stream())
 
 
+def check_lengths(lens, T):
+    """Variable-length batches: raise SclError unless every host-side frame count is in 1..T (call before the counts are uploaded: the
+    kernels only clamp).  Returns the counts as a list of ints."""
+    lens = [int(v) for v in lens]
+    rc = L.load().scl_varlen_check_lengths((ctypes.c_int32 * max(len(lens), 1))(*lens), len(lens), int(T))
+    if rc != 0:
+        L.check(rc, "scl_varlen_check_lengths")
+    return lens
+
+
+def _klen(klen):
+    assert klen.dtype == torch.int32 and klen.is_cuda and klen.is_contiguous(), "frame counts: a contiguous int32 tensor on the GPU"
+    return klen
+
+
+def attn_fwd_varlen(qkv, ctx, lse, klen, B, T, H, D, scale):
+    """attn_fwd_long (no dropout) over klen[b] keys / queries per utterance (device int32 [B]); ctx rows and lse beyond klen[b] are 0."""
+    assert klen.numel() >= B
+    return _call("scl_attn_fwd_varlen", _p(qkv), _p(ctx), _p(lse), _p(_klen(klen)), B, T, H, D, float(scale), _stream())
+
+
+def softmax_fwd_f32_varlen(S, P, klen, R, rows_per_utt, T, ldS, Tp, klen_offset=0):
+    """softmax_fwd_f32 / _long over the first klen[klen_offset + r // rows_per_utt] columns of row r; the other columns up to Tp are 0."""
+    assert R % rows_per_utt == 0 and klen.numel() >= klen_offset + R // rows_per_utt
+    _call("scl_softmax_fwd_f32_varlen", _p(S), _p(P), _p(_klen(klen), klen_offset), R, rows_per_utt, T, ldS, Tp, _stream())
+
+
+def zero_tail_rows(x, lens, B, T, C):
+    """x [B, T, C] (f32 or bf16): rows t >= lens[b] := 0."""
+    assert lens.numel() >= B
+    _call("scl_zero_tail_rows", _p(x), _isf32(x), _p(_klen(lens)), B, T, C, _stream())
+
+
+def meanpool_fwd_varlen(h, emb, lens, B, T, C):
+    """emb[b] = mean of the first lens[b] frames of h [B, T, C] (bf16 or f32)."""
+    assert lens.numel() >= B
+    _call("scl_meanpool_fwd_varlen_f32" if _isf32(h) else "scl_meanpool_fwd_varlen", _p(h), _p(emb), _p(_klen(lens)), B, T, C, _stream())
+
+
 def attn_long_ws_bytes(B, T, H):
     return int(L.load().scl_attn_long_ws_bytes(B, T, H))
 

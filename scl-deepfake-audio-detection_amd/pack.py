@@ -345,6 +345,38 @@ def pad_eval(x, padding_type, max_len=64600):
     return out
 
 
+# Variable-length scoring (main.py --eval --padding_type none): whole utterances, batched by length.
+VARLEN_MIN_SAMPLES = 400          # the shortest clip the XLS-R conv stack turns into a frame; shorter files are zero-padded to it
+VARLEN_MAX_SAMPLES = 960000       # 60 s at 16 kHz; longer files are cut
+VARLEN_QUANTUM = 16000            # padded batch lengths are multiples of this: few distinct shapes, at most 1 s of padding on the longest row
+VARLEN_WINDOW = 16                # utterances are sorted by length inside windows of VARLEN_WINDOW * batch_size consecutive ones
+
+
+def plan_varlen_batches(lengths, batch_size, budget=None, quantum=VARLEN_QUANTUM):
+    """Batches for utterances of `lengths` samples (protocol order) -> list of (indices, Lpad) that covers every index once.
+    Inside each window of VARLEN_WINDOW * batch_size consecutive utterances the utterances are sorted by length (stable) and cut into
+    batches of at most batch_size whose padded size count * Lpad stays within `budget` samples (default batch_size * 64600, what a
+    fixed-length batch holds); Lpad = the batch's longest length rounded up to a multiple of `quantum`.  An utterance that exceeds the
+    budget alone is a batch of one.  Sorting inside a window bounds how long a result waits for its turn in protocol order."""
+    batch_size = max(1, int(batch_size))
+    if budget is None:
+        budget = batch_size * 64600
+    lpad = lambda n: max(1, -(-int(n) // quantum)) * quantum
+    out = []
+    win = VARLEN_WINDOW * batch_size
+    for w0 in range(0, len(lengths), win):
+        order = sorted(range(w0, min(w0 + win, len(lengths))), key=lambda i: lengths[i])      # sorted() is stable
+        cur = []
+        for i in order:      # ascending: the newcomer is the longest of its batch
+            if cur and (len(cur) == batch_size or (len(cur) + 1) * lpad(lengths[i]) > budget):
+                out.append((cur, lpad(lengths[cur[-1]])))
+                cur = []
+            cur.append(i)
+        if cur:
+            out.append((cur, lpad(lengths[cur[-1]])))
+    return out
+
+
 class PackDataset(Dataset):
     """recipe: 'augall_3' | 'aug_2' | 'scl_normal' | 'augall_5' — the view composition of the four reference plugins."""
 
@@ -462,7 +494,9 @@ class EvalDataset(Dataset):
         require_decoder_for(list_IDs, "evaluation list")
         self.base_dir = os.path.join(base_dir, subdir) if subdir else base_dir
         self.cut = 64600
-        self.padding_type = padding_type
+        self.padding_type = padding_type      # "zero" / "repeat": cut or pad to self.cut; "none": the waveform at its own length
+        self.n_cut = 0                        # "none": files longer than VARLEN_MAX_SAMPLES that were cut
+        self._cut_lock = threading.Lock()
 
     def __len__(self):
         return len(self.list_IDs)
@@ -470,6 +504,15 @@ class EvalDataset(Dataset):
     def __getitem__(self, index):
         utt_id = self.list_IDs[index]
         x = load_audio(os.path.join(self.base_dir, utt_id), 16000)
+        if self.padding_type == "none":
+            x = np.asarray(x, dtype=np.float32)
+            if x.shape[0] > VARLEN_MAX_SAMPLES:
+                x = x[:VARLEN_MAX_SAMPLES]
+                with self._cut_lock:
+                    self.n_cut += 1
+            elif x.shape[0] < VARLEN_MIN_SAMPLES:
+                x = np.concatenate([x, np.zeros(VARLEN_MIN_SAMPLES - x.shape[0], dtype=np.float32)])
+            return torch.from_numpy(np.ascontiguousarray(x)), utt_id
         return torch.from_numpy(np.ascontiguousarray(pad_eval(x, self.padding_type, self.cut), dtype=np.float32)), utt_id
 
     def load_into(self, index, out):
