@@ -385,8 +385,8 @@ int scl_attn_fwd_long(const void* qkv, void* ctx, float* lse, int B, int T, int 
 long long scl_attn_long_ws_bytes(int B, int T, int H);
 int scl_attn_bwd_long(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, void* ws, int B, int T, int H, int D,
                       float scale, float drop_p, uint32_t drop_seed, void* stream);
-/* Variable-length scoring batches (csrc/attention_varlen.hip): x [B, L] zero-padded, utterance b holds klen[b] valid frames of the T the
- * padded length gives — the counterpart of fairseq's padding_mask (Wav2Vec2Model.forward(source, padding_mask)).  Forward only, no dropout.
+/* Variable-length batches (csrc/attention_varlen.hip): x [B, L] zero-padded, utterance b holds klen[b] valid frames of the T the
+ * padded length gives — the counterpart of fairseq's padding_mask (Wav2Vec2Model.forward(source, padding_mask)), for scoring and training.
  * klen / len: int32 [B] ON THE DEVICE, 1 <= value <= T; the kernels clamp to that range for memory safety and
  * scl_varlen_check_lengths(host copy, B, T) returns SCL_EINVAL (nothing is launched) when a value is outside it: call it before the upload.
  * scl_attn_fwd_varlen: scl_attn_fwd_long without dropout whose key loop, K / V loads and last-block mask run to klen[b]: keys >= klen[b]
@@ -395,6 +395,17 @@ int scl_attn_bwd_long(const void* qkv, const void* ctx, const void* dctx, const 
  * scl_attn_fwd_long gives for that utterance alone at T = klen[b]. */
 int scl_varlen_check_lengths(const int32_t* len_host, int B, int T);
 int scl_attn_fwd_varlen(const void* qkv, void* ctx, float* lse, const int32_t* klen, int B, int T, int H, int D, float scale, void* stream);
+/* scl_attn_fwd_varlen with attention dropout (drop_p = 0: the same kernel as above): keep-mask hash(drop_seed, ((b*H + h)*T + q)*T + k)
+ * with the padded T, the index of scl_attn_fwd_long; scl_attn_bwd_varlen redraws it from the same seed. */
+int scl_attn_fwd_varlen_drop(const void* qkv, void* ctx, float* lse, const int32_t* klen, int B, int T, int H, int D, float scale,
+                             float drop_p, uint32_t drop_seed, void* stream);
+/* scl_attn_bwd_long with per-utterance key counts: delta, dK / dV per block of 128 keys, dQ per block of 64 queries, no atomics, bitwise
+ * reproducible.  Query tiles and key blocks run to klen[b]; a block that starts at or beyond klen[b] writes zeros and leaves at once.  EVERY
+ * row of dqkv [B, T, 3, H, 64] is written: rows >= klen[b] are exactly 0, and those rows of qkv / ctx / dctx / lse are never read (they may
+ * hold NaN).  With drop_p = 0, rows < klen[b] carry the bits scl_attn_bwd_long gives for that utterance alone at T = klen[b].  Head dim 64
+ * only; ws: scl_attn_long_ws_bytes(B, T, H) bytes. */
+int scl_attn_bwd_varlen(const void* qkv, const void* ctx, const void* dctx, const float* lse, const int32_t* klen, void* dqkv, void* ws, int B,
+                        int T, int H, int D, float scale, float drop_p, uint32_t drop_seed, void* stream);
 /* scl_softmax_fwd_f32 / _long over the first klen[r / rows_per_utt] columns of row r (R % rows_per_utt == 0; rows_per_utt = H * T for
  * scores [B, H, T, ldS]); columns klen..Tp-1 are written as 0 and never read.  Any T: the row stays in registers up to Tp = 512, looped
  * (online max / sum, then the write pass) above. */
@@ -407,6 +418,12 @@ int scl_zero_tail_rows(void* x, int is_f32, const int32_t* len, int B, int T, in
  * fixed summation order (frames t = g, g + 4, ... per partial sum g, partial sums added in order). */
 int scl_meanpool_fwd_varlen(const void* h, float* emb, const int32_t* len, int B, int T, int C, void* stream);
 int scl_meanpool_fwd_varlen_f32(const float* h, float* emb, const int32_t* len, int B, int T, int C, void* stream);
+/* scl_meanpool_bwd / _f32 for the mean above: dpre[b][t] = demb[b] / len[b] x dropout mask(seed, element index) x act'(pre[b][t]) for
+ * t < len[b]; rows t >= len[b] are written as 0 (pre is not read there). */
+int scl_meanpool_bwd_varlen(const float* demb, const void* pre, void* dpre, const int32_t* len, int B, int T, int C, int ract, float drop_p,
+                            uint32_t seed, void* stream);
+int scl_meanpool_bwd_varlen_f32(const float* demb, const float* pre, float* dpre, const int32_t* len, int B, int T, int C, int ract,
+                                float drop_p, uint32_t seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* feature-extractor layer 0 (Conv1d(1,C,10,5) + LayerNorm + GELU), fused fwd / bwd            */

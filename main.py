@@ -89,11 +89,15 @@ def run_epoch(loader, model, optimizer, device, config, train):
     sums, total_sum, correct, n_total = {}, torch.zeros((), device=device), torch.zeros((), device=device), 0.0
     ctx = torch.enable_grad() if train else torch.no_grad()
     with ctx:
-        for info, batch_x, batch_y in loader:
+        for batch in loader:
+            info, batch_x, batch_y = batch[:3]
             x, n, n_packs = _as_model_input(batch_x, device)
             n_total += n
             y = batch_y.view(-1).type(torch.int64).to(device)
-            out, feat, emb = model(x)
+            if len(batch) > 3:      # zero-padded packs (PackDataset pad_to_trim): [k, V] sample counts -> one per row of the [k*V, L] batch
+                out, feat, emb = model(x, lengths=batch[3].reshape(-1).tolist())
+            else:
+                out, feat, emb = model(x)
             step_loss = None
             V = n // n_packs
             for pk in range(n_packs):        # SupCon positives / negatives stay inside a pack, as with --batch_size 1
@@ -457,6 +461,17 @@ def main(argv=None):
         return 0
 
     repeat = args.padding_type == "repeat"
+    # --padding_type zero with several packs per step: the default collate cannot stack packs of different lengths, so every pack is
+    # zero-padded to trim_length and comes with per-view sample counts; run_epoch hands them to the model, which masks the padding in the
+    # forward and the backward (training) or scores under the mask (validation).  The linear plugin only: the others take no lengths and
+    # keep their behaviour.  One pack per step needs no mask (a pack at its own length), --padding_type repeat has no padding.
+    pad_kw = {}
+    if args.padding_type == "zero" and args.batch_size > 1 and config["model"]["name"] == "wav2vec2_linear_nll":
+        if model.cfg.embed // model.cfg.heads != 64:
+            sys.exit("main.py: --padding_type zero with --batch_size %d masks the padding in the streaming attention, which takes 64-wide "
+                     "heads (this encoder's are %d wide); use --padding_type repeat or --batch_size 1"
+                     % (args.batch_size, model.cfg.embed // model.cfg.heads))
+        pad_kw = dict(pad_to_trim=True, min_samples=model.cfg.min_samples())
     # RawBoost parameter draws of the pack builder: "fast" = every builder thread's own numpy Generator, batched closed-form filter design,
     # ISD positions without a 64000-element permutation per clip (same distributions; scl_amd/augment.py); SCL_PACK_SAMPLER=reference =
     # the reference's draw-for-draw order on the global np.random stream (what the pack goldens pin; 0.5 ms more host time per clip), i.e.
@@ -468,12 +483,12 @@ def main(argv=None):
     d_label_trn, file_train = genList(dir_meta=proto, is_train=True, is_eval=False, is_dev=False)
     print("no. of training trials", len(file_train))
     train_set = Dataset_for(args, list_IDs=file_train, labels=d_label_trn, base_dir=args.database_path + "/", algo=args.algo,
-                            repeat_pad=repeat, **config["data"]["kwargs"])
+                            repeat_pad=repeat, **pad_kw, **config["data"]["kwargs"])
     d_label_dev, file_dev = genList(dir_meta=proto, is_train=False, is_eval=False, is_dev=True)
     print("no. of validation trials", len(file_dev))
     args.is_train = False
     dev_set = Dataset_for(args, list_IDs=file_dev, labels=d_label_dev, base_dir=args.database_path + "/", algo=args.algo,
-                          repeat_pad=repeat, **config["data"]["kwargs"])
+                          repeat_pad=repeat, **pad_kw, **config["data"]["kwargs"])
     if world > 1:
         dev_set = Subset(dev_set, shard_indices(len(dev_set), rank, world, drop_last=False))
     dev_loader = DataLoader(dev_set, batch_size=args.batch_size, num_workers=0, shuffle=False)

@@ -710,21 +710,35 @@ def pitch_shift(x, n_steps, sr=16000):
     return to_int16(fixed).to(torch.float32)
 
 
-def multiview_crop(views, length, repeat_pad, random_trim=True):
-    """batch_pad_for_multiview (wav_augmentation.py:209-282) for a list of 1-D device tensors;
-    returns [V, out_len].  Draws one np.random.rand() under the reference's condition."""
-    dev = views[0].device
-    lens = [int(v.numel()) for v in views]
+def crop_plan(lens, length, repeat_pad, random_trim=True, pad=False):
+    """The crop window of batch_pad_for_multiview for views of `lens` samples (the first is the anchor) -> (start, out_len, counts).
+    Draws one np.random.rand() under the reference's condition.  pad (with repeat_pad off): an anchor shorter than `length` still gives
+    out_len = length — the crop kernel writes zeros beyond a view's samples — and counts[v] is the number of view v's own samples the
+    window holds (0 for a view that ends before `start`); None without pad."""
     firstlen = lens[0]
     if firstlen < length:
-        start, out_len = 0, (length if repeat_pad else firstlen)
+        start, out_len = 0, (length if (repeat_pad or pad) else firstlen)
     elif random_trim:
         start, out_len = int(np.random.rand() * (firstlen - length)), length
     else:
         start, out_len = 0, length
+    counts = [max(0, min(min(firstlen, lv) - start, out_len)) for lv in lens] if pad else None
+    return start, out_len, counts
+
+
+def multiview_crop(views, length, repeat_pad, random_trim=True, pad=False):
+    """batch_pad_for_multiview (wav_augmentation.py:209-282) for a list of 1-D device tensors;
+    returns [V, out_len].  Draws one np.random.rand() under the reference's condition.
+    pad (zero padding only): every pack is [V, length] whatever the anchor's length, and the return value is (pack, counts) with the
+    per-view sample counts of crop_plan — the `lengths` a model needs to mask the padding."""
+    dev = views[0].device
+    lens = [int(v.numel()) for v in views]
+    firstlen = lens[0]
+    assert not (pad and repeat_pad), "multiview_crop: pad is the zero-padded mode"
+    start, out_len, counts = crop_plan(lens, length, repeat_pad, random_trim, pad)
     src = torch.cat([v.reshape(-1).float() for v in views])
     # offsets and lengths through one pinned, asynchronous copy (a torch.tensor(..., device=) is a blocking copy behind the whole pack's chain)
     off, lens_d = _h2d_pack([np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64), np.asarray(lens, dtype=np.int32)], dev)
     out = torch.empty(len(views), out_len, device=dev)
     ops.multiview_crop(src, off, lens_d, len(views), firstlen, start, out_len, repeat_pad, out, out_len)
-    return out
+    return (out, counts) if pad else out

@@ -23,7 +23,7 @@
 //   dQ:      one workgroup per (utterance, head, block of 64 queries), as the forward: S^T = K Q^T, dP^T = V dO^T, dS^T as above,
 //            dQ^T += K^T dS^T with K's transposed image.
 // Each output element is summed by one wave in a fixed order: no atomics, bitwise reproducible.
-#include "attn_tiles.h"      // lk_off / lt_off tile images, l_frag_* / l_pack8 / l_load_rows operands, kv_fetch / kv_store staging
+#include "attn_tiles.h"      // lk_off / lt_off tile images, l_frag_* / l_pack8 / l_load_rows operands, kv_fetch / kv_store / qt_fetch / qt_store staging
 
 namespace {
 
@@ -31,7 +31,6 @@ constexpr int LD = 64;        // head dim
 constexpr int LKB = 64;       // keys per streamed block (forward, dQ)
 constexpr int LQB = 64;       // queries per workgroup (forward, dQ)
 constexpr int LKW = 128;      // keys per workgroup (dK / dV)
-constexpr float LOG2E = 1.4426950408889634f;
 
 // =====================================================================================================================================
 // Forward
@@ -156,33 +155,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restric
 }
 
 // ---- dK / dV ------------------------------------------------------------------------------------------------------------------------
-// Query tile of 32 rows per step: Q rows, Q tr, dO rows, dO tr images (4 KiB each), then lse (x log2 e) and delta of the 32 rows.
-constexpr int QT_BYTES = 4 * 4096 + 2 * 32 * 4;
-
-struct QRegs { uint4 q, o; float ls, dl; };
-// thread i: query row i >> 3 of the tile, 16-byte chunk i & 7 (256 threads = 32 rows x 8 chunks); rows past T: zeros, lse = +huge (P = 0)
-__device__ __forceinline__ void qt_fetch(QRegs& r, const bf16_t* __restrict__ base, int64_t pitch, const bf16_t* __restrict__ dob, int E,
-                                         const float* __restrict__ lse_bh, const float* __restrict__ del_bh, int q0, int T) {
-    const int row = threadIdx.x >> 3, c = threadIdx.x & 7, q = q0 + row;
-    r.q = make_uint4(0, 0, 0, 0); r.o = make_uint4(0, 0, 0, 0); r.ls = 1e30f; r.dl = 0.f;
-    if (q < T) {
-        r.q = *reinterpret_cast<const uint4*>(base + (int64_t)q * pitch + 8 * c);
-        r.o = *reinterpret_cast<const uint4*>(dob + (int64_t)q * E + 8 * c);
-        if (c == 0) { r.ls = lse_bh[q] * LOG2E; r.dl = del_bh[q]; }
-    }
-}
-__device__ __forceinline__ void qt_store(const QRegs& r, char* tile) {
-    const int row = threadIdx.x >> 3, c = threadIdx.x & 7;
-    *reinterpret_cast<uint4*>(tile + lk_off(row, c)) = r.q;
-    *reinterpret_cast<uint4*>(tile + 4096 + lt_off(row, 8 * c)) = r.q;
-    *reinterpret_cast<uint4*>(tile + 8192 + lk_off(row, c)) = r.o;
-    *reinterpret_cast<uint4*>(tile + 12288 + lt_off(row, 8 * c)) = r.o;
-    if (c == 0) {
-        float* ld = reinterpret_cast<float*>(tile + 16384);
-        ld[row] = r.ls; ld[32 + row] = r.dl;
-    }
-}
-
+// Query tiles of 32 rows per step: QRegs / qt_fetch / qt_store of attn_tiles.h (Q rows, Q tr, dO rows, dO tr images, lse x log2 e, delta)
 template <bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dkdv_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
                                                                  const float* __restrict__ lse, const float* __restrict__ delta,

@@ -1,10 +1,12 @@
 // attn_tiles.h — LDS tile images, MFMA operand fragments and the K / V block staging shared by the streaming attention kernels
-// (attention_long.hip: fixed-length forward / backward; attention_varlen.hip: the forward with per-utterance key counts).
+// (attention_long.hip: fixed-length forward / backward; attention_varlen.hip: the same with per-utterance key counts).
 // Everything is internal to the including file (anonymous namespace, force-inlined).
 #pragma once
 #include "common.h"
 
 namespace {
+
+constexpr float LOG2E = 1.4426950408889634f;
 
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4_l;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4l;
@@ -69,6 +71,33 @@ __device__ __forceinline__ void kv_store(const KVRegs& r, char* Kr, char* Kt, ch
         if (Kt) *reinterpret_cast<uint4*>(Kt + lt_off(key, 8 * c)) = r.k[it];
         if (Vr) *reinterpret_cast<uint4*>(Vr + lk_off(key, c)) = r.v[it];
         if (Vt) *reinterpret_cast<uint4*>(Vt + lt_off(key, 8 * c)) = r.v[it];
+    }
+}
+
+// Query tile staging for the dK / dV kernels, 32 rows per step: Q rows, Q tr, dO rows, dO tr images (4 KiB each), then lse (x log2 e) and delta of the 32 rows.
+constexpr int QT_BYTES = 4 * 4096 + 2 * 32 * 4;
+
+struct QRegs { uint4 q, o; float ls, dl; };
+// thread i: query row i >> 3 of the tile, 16-byte chunk i & 7 (256 threads = 32 rows x 8 chunks); rows past T: zeros, lse = +huge (P = 0)
+__device__ __forceinline__ void qt_fetch(QRegs& r, const bf16_t* __restrict__ base, int64_t pitch, const bf16_t* __restrict__ dob, int E,
+                                         const float* __restrict__ lse_bh, const float* __restrict__ del_bh, int q0, int T) {
+    const int row = threadIdx.x >> 3, c = threadIdx.x & 7, q = q0 + row;
+    r.q = make_uint4(0, 0, 0, 0); r.o = make_uint4(0, 0, 0, 0); r.ls = 1e30f; r.dl = 0.f;
+    if (q < T) {
+        r.q = *reinterpret_cast<const uint4*>(base + (int64_t)q * pitch + 8 * c);
+        r.o = *reinterpret_cast<const uint4*>(dob + (int64_t)q * E + 8 * c);
+        if (c == 0) { r.ls = lse_bh[q] * LOG2E; r.dl = del_bh[q]; }
+    }
+}
+__device__ __forceinline__ void qt_store(const QRegs& r, char* tile) {
+    const int row = threadIdx.x >> 3, c = threadIdx.x & 7;
+    *reinterpret_cast<uint4*>(tile + lk_off(row, c)) = r.q;
+    *reinterpret_cast<uint4*>(tile + 4096 + lt_off(row, 8 * c)) = r.q;
+    *reinterpret_cast<uint4*>(tile + 8192 + lk_off(row, c)) = r.o;
+    *reinterpret_cast<uint4*>(tile + 12288 + lt_off(row, 8 * c)) = r.o;
+    if (c == 0) {
+        float* ld = reinterpret_cast<float*>(tile + 16384);
+        ld[row] = r.ls; ld[32 + row] = r.dl;
     }
 }
 

@@ -178,8 +178,10 @@ class Encoder:
         self.dev = P.device
         self._bufs = {}
         # variable-length scoring batches (forward / forward_f32 with `frames`): every padded shape is a buffer set of its own, so these
-        # live in two small LRUs (bf16 path, fp32 path) instead of the keep-forever table of the fixed shapes
+        # live in two small LRUs (bf16 path, fp32 path) instead of the keep-forever table of the fixed shapes.  Variable-length TRAINING
+        # batches share one padded shape (the data path pads every pack to trim_length): their sets are kept like the fixed shapes'
         self._vbufs, self._vbufs_f32 = VarlenSets(), VarlenSets()
+        self._vbufs_train = {}
         C, E, K, G = cfg.conv_dim, cfg.embed, cfg.pos_k, cfg.pos_groups
         Cg = E // G
         bf = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=self.dev)
@@ -228,9 +230,14 @@ class Encoder:
         return self.P.f32(self.n(name))
 
     # ---- buffers ---------------------------------------------------------------------------------
-    def bufs(self, B, L, varlen=False):
-        """The buffer set of a [B, L] batch.  varlen: the set of a variable-length scoring batch — streaming attention whatever T is
-        (lse, no T x T buffers), kept in the LRU."""
+    def bufs(self, B, L, varlen=False, train=False):
+        """The buffer set of a [B, L] batch.  varlen: the set of a variable-length batch — streaming attention whatever T is (lse,
+        attn_ws, no T x T buffers); a scoring batch's lives in the LRU, a training batch's (train: its saved activations wait for the
+        backward) is kept."""
+        if varlen and train:
+            if (B, L) not in self._vbufs_train:
+                self._vbufs_train[(B, L)] = self._make_bufs(B, L, True)
+            return self._vbufs_train[(B, L)]
         if varlen:
             return self._vbufs.get_or_make((B, L), lambda: self._make_bufs(B, L, True))
         key = (B, L)
@@ -471,22 +478,27 @@ class Encoder:
         ops.colreduce_seg(part, out, nparts, width, out2=out2, split=split)
 
     # ---- forward ---------------------------------------------------------------------------------
-    def forward(self, x, training=True, refresh=True, step_seed=0, frames=None):
+    def forward(self, x, training=True, refresh=True, step_seed=0, frames=None, grad=None):
         """x [B, L] fp32 contiguous on the GPU -> (enc_out bf16 [B*T, E], ctx).  step_seed: seed of this step's element-dropout masks.
-        frames (no-grad scoring only): int32 [B] on the GPU, the valid frames of each zero-padded utterance — rows beyond them are zeroed
-        before the positional convolution and take no part in any soft-max (scl_attn_fwd_varlen in every layer); output rows beyond them
-        are finite and meaningless.  A recorded plan keeps the tensor's address: overwrite it in place before a replay."""
+        frames: int32 [B] on the GPU, the valid frames of each zero-padded utterance — rows beyond them are zeroed before the positional
+        convolution and take no part in any soft-max (scl_attn_fwd_varlen / _drop in every layer); output rows beyond them are finite
+        and meaningless.  A recorded plan keeps the tensor's address: overwrite it in place before a replay.
+        grad: a backward(ctx, ...) will follow (default: autograd is on; a caller inside an autograd.Function, where it is off, says so).
+        With frames, a forward that a backward follows takes the shape's training buffer set and the backward masks the same rows;
+        without one it is the scoring mode (training=False), whose sets live in the small LRU."""
         cfg, P = self.cfg, self.P
         B, L = x.shape
-        if frames is not None and (training or torch.is_grad_enabled()):
-            raise NotImplementedError("encoder: per-utterance frame counts are a scoring mode (eval, torch.no_grad()); there is no backward")
+        grad = torch.is_grad_enabled() if grad is None else bool(grad)
+        if frames is not None and training and not grad:
+            raise NotImplementedError("encoder: per-utterance frame counts without a backward are a scoring mode (training=False, "
+                                      "torch.no_grad()); with training=True they need autograd on")
         p_res, p_attn, p_act, p_in = self.drop_probs(training)
         slots = []
         sseed = lambda layer, site: self.site_seed(step_seed, layer, site)
         recording = ops._rec() is not None
         if refresh:
             self.refresh_weights()
-        d = self.bufs(B, L, varlen=frames is not None)
+        d = self.bufs(B, L, varlen=frames is not None, train=grad)
         C, E, H, Fd, K, G = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k, cfg.pos_groups
         D, Cg = E // H, E // G
         Ts, T, M, Tp = d["Ts"], d["T"], d["M"], d["Tp"]
@@ -532,7 +544,11 @@ class Encoder:
             ops.gemm(Op(d["h1"][n], E), self.W(pn + "self_attn.q_proj.weight", E), d["qkv"][n], M, 3 * E, E,
                      bias=self.b(pn + "self_attn.q_proj.bias"))  # q,k,v biases are adjacent in the flat buffer
             qkv = d["qkv"][n]
-            if frames is not None:
+            if frames is not None and p_attn > 0:
+                e = ops.attn_fwd_varlen_drop(qkv, d["ctx"][n], d["lse"][n], frames, B, T, H, D, D ** -0.5, drop_p=p_attn,
+                                             drop_seed=sseed(n, self.SITE_ATTN))
+                self._slot(slots, e, ops.ATTN_FWD_VARLEN_SEED, n, self.SITE_ATTN)
+            elif frames is not None:
                 ops.attn_fwd_varlen(qkv, d["ctx"][n], d["lse"][n], frames, B, T, H, D, D ** -0.5)
             elif d["fused_attn"] and ATTN_FP8 and not training and T <= 256:
                 ops.attn_fwd_fp8(qkv, d["ctx"][n], d["lse"][n], B, T, H, D, D ** -0.5)      # configs[4]'s fp8 attention (opt-in, no-grad forward)
@@ -573,7 +589,7 @@ class Encoder:
         ops.layernorm_fwd(d["xin"][cfg.layers], self.b("encoder.layer_norm.weight"), self.b("encoder.layer_norm.bias"),
                           d["out"], None, d["omean"], d["orstd"], M, E)
         return d["out"], {"d": d, "x": x, "B": B, "L": L, "skipped": skipped, "drop": (p_res, p_attn, p_act, p_in), "step_seed": step_seed,
-                          "drop_slots": slots}
+                          "drop_slots": slots, "frames": frames}
 
     # ---- fp32 scoring forward ----------------------------------------------------------------------
     def _f32_weights(self):
@@ -715,9 +731,15 @@ class Encoder:
     # ---- backward --------------------------------------------------------------------------------
     def backward(self, ctx, d_out):
         """d_out: bf16 or f32 [M, E] gradient w.r.t. forward()'s output.  Writes every parameter
-        gradient of the encoder into the flat gradient buffer (overwrite semantics)."""
+        gradient of the encoder into the flat gradient buffer (overwrite semantics).
+        A forward with `frames` (ctx["frames"]): d_out's rows beyond an utterance's frames must be 0 (the head's masked mean pool and feats
+        give that).  Two kernels then carry the mask: scl_attn_bwd_varlen writes zero dqkv rows there, and the rows of d(x0) are zeroed
+        behind the positional convolution's data gradient (the backward of the forward's zero_tail_rows(x0)).  Every other kernel of the
+        chain works row by row, so the gradient of a padded row is exactly 0 from the head down to the conv stack, and padded rows add
+        nothing to any weight, bias or LayerNorm gradient."""
         cfg, P = self.cfg, self.P
         d, x, B, L = ctx["d"], ctx["x"], ctx["B"], ctx["L"]
+        frames = ctx.get("frames")
         C, E, H, Fd, K, G = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k, cfg.pos_groups
         D, Cg = E // H, E // G
         Ts, T, M, Tp, Mp = d["Ts"], d["T"], d["M"], d["Tp"], d["Mp"]
@@ -794,7 +816,12 @@ class Encoder:
                 self._wgrad(d, Op(dxb, E), Op(d["ctx"][n], E), P.g(self.n(pn + "self_attn.out_proj.weight")), E, E, Mp, slot=2)
             ops.gemm(Op(dxb, E), self.W(pn + "self_attn.out_proj.weight", E), d["d_ctx"], M, E, E, b_t=True)
             qkv, dqkv = d["qkv"][n], d["dqkv"][li & 1]
-            if d["fused_attn"]:
+            if frames is not None:      # every row of dqkv written, rows beyond the utterance's frames as 0; q/k/v bias gradients: colsum_reduce below
+                e = ops.attn_bwd_varlen(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], frames, dqkv, d["attn_ws"], B, T, H, D, D ** -0.5,
+                                        drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
+                if p_attn > 0:
+                    self._slot(slots, e, ops.ATTN_BWD_VARLEN_SEED, n, self.SITE_ATTN)
+            elif d["fused_attn"]:
                 e = ops.attn_bwd(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], dqkv, B, T, H, D, D ** -0.5,
                                  bias_part=d["qkv_bias_part"], drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
                 if p_attn > 0:
@@ -880,6 +907,8 @@ class Encoder:
             ops.gemm(Op(d["dcpad"], E, rpb=T, rbstride=(T + K) * E, cin=Cg, cout=E, bs2=Cg), Op(self.pos_wd, K * Cg, bs2=Cg * K * Cg),
                      other, M, Cg, K * Cg, nb2=G, ldc=E, c_bs2=Cg, R=dx, rmode=1)
         dx0 = other
+        if frames is not None:      # the forward zeroed x0's padded rows: no gradient flows into them (the convolution's reaches them)
+            ops.zero_tail_rows(dx0, frames, B, T, E)
         if p_in > 0:       # backward of dropout_input: d(post_extract_proj output) = dx0 x mask (f32 for the bias sum, bf16 for the GEMMs)
             self._slot(slots, ops.dropout(dx0, dx0, otherb, M * E, sseed(-1, self.SITE_IN), p_in), ops.DROPOUT_SEED, -1, self.SITE_IN)
         else:

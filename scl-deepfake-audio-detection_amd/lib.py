@@ -184,10 +184,14 @@ def _protos():
         # attention_varlen.hip
         "scl_varlen_check_lengths": ([P(_i32), _i32, _i32], _i32),
         "scl_attn_fwd_varlen": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp], _i32),
+        "scl_attn_fwd_varlen_drop": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _u32, _vp], _i32),
+        "scl_attn_bwd_varlen": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _u32, _vp], _i32),
         "scl_softmax_fwd_f32_varlen": ([_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp], _i32),
         "scl_zero_tail_rows": ([_vp, _i32, _vp, _i32, _i32, _i32, _vp], _i32),
         "scl_meanpool_fwd_varlen": ([_vp, _vp, _vp, _i32, _i32, _i32, _vp], _i32),
         "scl_meanpool_fwd_varlen_f32": ([_vp, _vp, _vp, _i32, _i32, _i32, _vp], _i32),
+        "scl_meanpool_bwd_varlen": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _u32, _vp], _i32),
+        "scl_meanpool_bwd_varlen_f32": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _u32, _vp], _i32),
         # conv0.hip
         "scl_conv0_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp], _i32),
         "scl_conv0_fwd_f32": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp], _i32),

@@ -4,8 +4,9 @@ numeric step executed by the HIP kernels behind the C ABI.
 
     Model(args: dict, device, is_train=True)
     forward(x [bz, L] fp32) -> (log_probs [bz,2], feats [bz,T,128], emb [bz,128])   (or log_probs when not is_train)
-    forward(x, lengths=[n_0, ...])   scoring only (eval, no_grad): row b holds n_b samples followed by zeros and gets the result it gets
-                                     when scored alone at its own length; feats rows beyond its frames are 0
+    forward(x, lengths=[n_0, ...])   row b holds n_b samples followed by padding and gets the result it gets alone at its own length; feats
+                                     rows beyond its frames are 0.  Scoring (eval, no_grad) or training (train mode, autograd on: the
+                                     backward carries the same mask, padded frames add nothing to any gradient)
     loss(output, feats, emb, labels, config, info=None) -> dict of 0-d tensors, summed and .backward()-ed by the caller
 
 State-dict keys equal the reference's (ssl_model.model.<fairseq keys>, LL.*, first_bn.*, first_bn1.*,
@@ -99,8 +100,8 @@ class _ModelFn(torch.autograd.Function):
     buffers; backward consumes (d_logp, d_feats, d_emb) and fills the flat gradient buffer."""
 
     @staticmethod
-    def forward(ctx, model, x, anchor):
-        out, feats, emb, saved = model._run_forward(x)
+    def forward(ctx, model, x, anchor, frames=None):
+        out, feats, emb, saved = model._run_forward(x, frames, train=frames is not None)
         ctx.model, ctx.saved = model, saved
         # the outputs live in static per-(B, L) buffers (launch plans point at them): hand out copies, so results
         # of successive forward calls do not alias (3 small device copies)
@@ -109,7 +110,7 @@ class _ModelFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_out, d_feats, d_emb):
         ctx.model._run_backward(ctx.saved, d_out, d_feats, d_emb)
-        return None, None, None
+        return None, None, None, None
 
 
 class Model(nn.Module):
@@ -145,6 +146,7 @@ class Model(nn.Module):
         # variable-length scoring batches (forward(x, lengths)): state, head buffers and launch plans per padded shape, least recently
         # used of at most four; an evicted shape takes its encoder buffer set with it
         self._vstates = VarlenSets(on_evict=lambda key: self.encoder._vbufs.pop(key, None))
+        self._vstates_train = {}      # variable-length training batches: one padded shape per run (the data path pads to trim_length), kept
         self._step_seed = dropout_stream_seed(seed, rank)   # head dropout masks differ per --seed and per data-parallel rank
         self.out_dim = self.cfg.embed
         self.grad_sync = None   # scl_amd.parallel.GradSync when data-parallel (set by FusedAdamW)
@@ -216,6 +218,19 @@ class Model(nn.Module):
                         frames=torch.ones(B, dtype=torch.int32, device=self.device), hb=self._head_bufs(B, T, keep=False), plans={})
         return self._vstates.get_or_make((B, L), make)
 
+    def _varlen_train_state(self, B, L):
+        """_state for a variable-length training batch: the boundary buffers of both directions, the frame counts (fixed address, read by
+        the forward's and the backward's plans) and the shape's own head buffers."""
+        key = (B, L)
+        if key not in self._vstates_train:
+            T = self.cfg.conv_lens(L)[-1]
+            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
+            self._vstates_train[key] = dict(T=T, x=f32(B, L), feats=f32(B, T, HEAD_DIM), emb=f32(B, HEAD_DIM), logp=f32(B, N_CLASS),
+                                            d_logp=f32(B, N_CLASS), d_feats=f32(B, T, HEAD_DIM), d_emb=f32(B, HEAD_DIM), train=True,
+                                            frames=torch.ones(B, dtype=torch.int32, device=self.device),
+                                            hb=self._head_bufs(B, T, keep=False), plans={})
+        return self._vstates_train[key]
+
     def _frames(self, lengths, B, L):
         """Sample counts of a zero-padded batch -> frame counts as an int32 device tensor (validated on the host first).  Counts below the
         shortest clip that yields a frame count as that clip: its zero padding is part of the signal, as for a file padded on disk."""
@@ -228,12 +243,12 @@ class Model(nn.Module):
         host = torch.tensor(frames, dtype=torch.int32)
         return (host.pin_memory() if self.device.type == "cuda" else host).to(self.device, non_blocking=True)
 
-    def _run_forward(self, x, frames=None):
+    def _run_forward(self, x, frames=None, train=False):
         B, L = x.shape
         training = bool(self.training)
         ssl_train = False if self.flag_fix_ssl else bool(self.is_train and training)
         if frames is not None:
-            st = self._varlen_state(B, L)
+            st = self._varlen_train_state(B, L) if train else self._varlen_state(B, L)
             st["frames"].copy_(frames)
         else:
             st = self._state(B, L)
@@ -262,8 +277,9 @@ class Model(nn.Module):
 
     def _forward_kernels(self, st, B, L, ssl_train, drop, seeds):
         P, E = self.P, self.cfg.embed
-        frames = st.get("frames")      # a variable-length state (scoring only)
-        enc_out, ectx = self.encoder.forward(st["x"], training=ssl_train, refresh=False, step_seed=self._step_seed, frames=frames)
+        frames = st.get("frames")      # a variable-length state (scoring, or training: st["train"])
+        enc_out, ectx = self.encoder.forward(st["x"], training=ssl_train, refresh=False, step_seed=self._step_seed, frames=frames,
+                                             grad=bool(st.get("train")) if frames is not None else None)
         T = ectx["d"]["T"]
         M = B * T
         hb = st["hb"] if frames is not None else self._head_bufs(B, T)
@@ -305,7 +321,7 @@ class Model(nn.Module):
         if plan is not None:
             plan["drop_descs"][0].drop_seed = seeds[1]
             plan["drop_descs"][1].drop_seed = seeds[0]
-            plan["meanpool_entry"][1][8] = seeds[2]
+            plan["meanpool_entry"][1][plan["meanpool_seed_pos"]] = seeds[2]
             self.encoder.apply_seeds(plan["enc_slots"], sv["ectx"]["step_seed"])
             ops.replay(plan["calls"])
             return
@@ -322,7 +338,15 @@ class Model(nn.Module):
         W = lambda name, ld: Op(P.bf16, ld, offset=P.off(name))
         ops.utt_head_bwd(st["d_logp"], sv["logp"], sv["emb"], P.f32("backend.m_utt_level.weight"), st["d_emb"], hb["demb"],
                          P.g("backend.m_utt_level.weight"), P.g("backend.m_utt_level.bias"), hb["ws"], B, HEAD_DIM, N_CLASS)
-        mp_entry = ops.meanpool_bwd(hb["demb"], hb["pre"][2], hb["dpre"][2], B, T, HEAD_DIM, ACT_LEAKY, sv["drop"], seeds[2])
+        frames = st.get("frames")      # a variable-length training batch: the mean ran over each utterance's own frames
+        if frames is not None:
+            # the forward zeroed feats beyond them, so whatever the loss hands back there (SupCon's gradient is not 0) stops here
+            ops.zero_tail_rows(st["d_feats"], frames, B, T, HEAD_DIM)
+            mp_entry = ops.meanpool_bwd_varlen(hb["demb"], hb["pre"][2], hb["dpre"][2], frames, B, T, HEAD_DIM, ACT_LEAKY, sv["drop"], seeds[2])
+            mp_pos = ops.MEANPOOL_BWD_VARLEN_SEED
+        else:
+            mp_entry = ops.meanpool_bwd(hb["demb"], hb["pre"][2], hb["dpre"][2], B, T, HEAD_DIM, ACT_LEAKY, sv["drop"], seeds[2])
+            mp_pos = ops.MEANPOOL_BWD_SEED
         drop_descs, enc_slots = [], []
         for j, idx in reversed(list(enumerate((0, 3, 6)))):
             dpre = hb["dpre"][j]
@@ -346,7 +370,7 @@ class Model(nn.Module):
             if self.grad_sync is not None:      # head gradients (the END of the flat buffer) are final: start their all-reduce
                 ops.host_callback(self.grad_sync.ready_above, P.off("LL.weight"))
             enc_slots = self.encoder.backward(sv["ectx"], hb["denc"])
-        return dict(drop_descs=drop_descs, meanpool_entry=mp_entry, enc_slots=enc_slots)
+        return dict(drop_descs=drop_descs, meanpool_entry=mp_entry, meanpool_seed_pos=mp_pos, enc_slots=enc_slots)
 
     def _score_fp32(self, x, frames=None):
         """Scoring forward (no grad, eval mode): fp32 activations, fp32 master weights, exact-fp32 GEMMs end to end — the
@@ -379,12 +403,12 @@ class Model(nn.Module):
         x = x.to(device=self.device, dtype=torch.float32).contiguous()   # main.py:60 hands over a transposed view
         frames = None
         if lengths is not None:
-            if torch.is_grad_enabled() or self.training:
-                raise NotImplementedError("forward(x, lengths) is a scoring mode: call it on model.eval() under torch.no_grad() "
-                                          "(the variable-length kernels have no backward)")
+            if torch.is_grad_enabled() != bool(self.training):
+                raise NotImplementedError("forward(x, lengths) is a scoring mode on model.eval() under torch.no_grad() and a training "
+                                          "mode on model.train() with autograd on; eval with autograd, or train under no_grad, is neither")
             frames = self._frames(lengths, x.shape[0], x.shape[1])
         if torch.is_grad_enabled() and any(p.requires_grad for p in (self._anchor,)):
-            out, feats, emb = _ModelFn.apply(self, x, self._anchor)
+            out, feats, emb = _ModelFn.apply(self, x, self._anchor, frames)
         elif not self.training and SCORE_FP32:
             out, feats, emb = self._score_fp32(x, frames)
         else:

@@ -315,6 +315,8 @@ def layernorm_bwd_nparts(M):
 LN_BWD_DIN_SEED, LN_BWD_DOUT_SEED = 22, 24      # positions of the two mask seeds in a recorded scl_layernorm_bwd call
 ATTN_FWD_SEED, ATTN_BWD_SEED, DROPOUT_SEED = 9, 12, 4
 ATTN_FWD_LONG_SEED, ATTN_BWD_LONG_SEED = 9, 12      # positions of the mask seed in recorded scl_attn_fwd_long / scl_attn_bwd_long calls
+ATTN_FWD_VARLEN_SEED, ATTN_BWD_VARLEN_SEED = 10, 13      # the same in recorded scl_attn_fwd_varlen_drop / scl_attn_bwd_varlen calls
+MEANPOOL_BWD_SEED, MEANPOOL_BWD_VARLEN_SEED = 8, 9      # the head-dropout seed in recorded scl_meanpool_bwd / scl_meanpool_bwd_varlen calls
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, beta, dres, dx_f32, dx_bf16, part, M, C, act=0, sum_dres=False, out_rpb=0,
@@ -515,6 +517,21 @@ def attn_fwd_varlen(qkv, ctx, lse, klen, B, T, H, D, scale):
     return _call("scl_attn_fwd_varlen", _p(qkv), _p(ctx), _p(lse), _p(_klen(klen)), B, T, H, D, float(scale), _stream())
 
 
+def attn_fwd_varlen_drop(qkv, ctx, lse, klen, B, T, H, D, scale, drop_p=0.0, drop_seed=0):
+    """attn_fwd_varlen with attention dropout (mask index ((b*H + h)*T + q)*T + k, the padded T); returns the recorded call."""
+    assert klen.numel() >= B
+    return _call("scl_attn_fwd_varlen_drop", _p(qkv), _p(ctx), _p(lse), _p(_klen(klen)), B, T, H, D, float(scale), float(drop_p), int(drop_seed),
+                 _stream())
+
+
+def attn_bwd_varlen(qkv, ctx, dctx, lse, klen, dqkv, ws, B, T, H, D, scale, drop_p=0.0, drop_seed=0):
+    """attn_bwd_long over klen[b] keys / queries per utterance: every row of dqkv is written, rows >= klen[b] as 0."""
+    assert klen.numel() >= B
+    assert ws.numel() * ws.element_size() >= attn_long_ws_bytes(B, T, H), "attn_bwd_varlen: workspace too small"
+    return _call("scl_attn_bwd_varlen", _p(qkv), _p(ctx), _p(dctx), _p(lse), _p(_klen(klen)), _p(dqkv), _p(ws), B, T, H, D, float(scale),
+                 float(drop_p), int(drop_seed), _stream())
+
+
 def softmax_fwd_f32_varlen(S, P, klen, R, rows_per_utt, T, ldS, Tp, klen_offset=0):
     """softmax_fwd_f32 / _long over the first klen[klen_offset + r // rows_per_utt] columns of row r; the other columns up to Tp are 0."""
     assert R % rows_per_utt == 0 and klen.numel() >= klen_offset + R // rows_per_utt
@@ -531,6 +548,13 @@ def meanpool_fwd_varlen(h, emb, lens, B, T, C):
     """emb[b] = mean of the first lens[b] frames of h [B, T, C] (bf16 or f32)."""
     assert lens.numel() >= B
     _call("scl_meanpool_fwd_varlen_f32" if _isf32(h) else "scl_meanpool_fwd_varlen", _p(h), _p(emb), _p(_klen(lens)), B, T, C, _stream())
+
+
+def meanpool_bwd_varlen(demb, pre, dpre, lens, B, T, C, ract, drop_p=0.0, seed=0):
+    """meanpool_bwd for meanpool_fwd_varlen: scaled by 1 / lens[b], rows t >= lens[b] written as 0; returns the recorded call."""
+    assert pre.dtype == dpre.dtype and lens.numel() >= B
+    return _call("scl_meanpool_bwd_varlen_f32" if _isf32(pre) else "scl_meanpool_bwd_varlen", _p(demb), _p(pre), _p(dpre), _p(_klen(lens)),
+                 B, T, C, ract, float(drop_p), int(seed), _stream())
 
 
 def attn_long_ws_bytes(B, T, H):

@@ -3,7 +3,7 @@
 waveform transformation executed on the GPU (scl_amd.augment) instead of in DataLoader workers.
 
 Contract kept (SURVEY.md §8b "Data plugin"):
-  Dataset_for(args, list_IDs=, labels=, base_dir=, algo=, repeat_pad=, **yaml_kwargs)[i]
+  Dataset_for(args, list_IDs=, labels=, base_dir=, algo=, repeat_pad=, pad_to_trim=, min_samples=, **yaml_kwargs)[i]
       -> (id: str, Tensor[L, V] fp32, Tensor[V] fp32 labels)         view order and labels as the reference
   Dataset_for_eval(list_IDs=, base_dir=, padding_type=)[i] -> (Tensor[64600], id)
   augmenters are looked up BY NAME with signature (x, args, sr, audio_path=...) -> waveform
@@ -382,7 +382,7 @@ class PackDataset(Dataset):
 
     def __init__(self, recipe, args, list_IDs, labels, base_dir, algo=5, vocoders=(), augmentation_methods=(), num_additional_real=2,
                  num_additional_spoof=2, trim_length=64000, wav_samp_rate=16000, noise_path=None, rir_path=None, aug_dir=None,
-                 online_aug=False, repeat_pad=True, is_train=True):
+                 online_aug=False, repeat_pad=True, is_train=True, pad_to_trim=False, min_samples=400):
         self.recipe, self.args = recipe, args
         args.noise_path, args.rir_path, args.aug_dir, args.online_aug = noise_path, rir_path, aug_dir, online_aug
         self.list_IDs = list_IDs
@@ -390,6 +390,10 @@ class PackDataset(Dataset):
         self.bonafide_dir = os.path.join(base_dir, "bonafide")
         self.vocoded_dir = os.path.join(base_dir, "vocoded")
         self.trim_length, self.sample_rate, self.repeat_pad = trim_length, wav_samp_rate, repeat_pad
+        # zero padding with several packs per step (main.py --padding_type zero --batch_size k > 1): every pack is [trim_length, V] with
+        # zeros beyond a view's samples, and a fourth item carries the per-view sample counts (clamped to [min_samples, trim_length]: the
+        # shortest clip the encoder gives a frame for) — one batch shape, and the model masks the padding (forward(x, lengths))
+        self.pad_to_trim, self.min_samples = bool(pad_to_trim) and not repeat_pad, int(min_samples)
         self.vocoders = list(vocoders)
         self.num_additional_real, self.num_additional_spoof = num_additional_real, num_additional_spoof
         self.methods = list(augmentation_methods) if len(augmentation_methods) >= 1 else ["RawBoost12"]
@@ -476,7 +480,12 @@ class PackDataset(Dataset):
         else:
             views, n_pos = [real] + aug_real + add_real + voc + aug_voc + add_spoof, 1 + len(aug_real) + len(add_real)
         dev_views = [_to_dev(v, self.args).reshape(-1) for v in views]
-        pack = augment.multiview_crop(dev_views, self.trim_length, self.repeat_pad, random_trim=True)   # [V, L]
+        counts = None
+        if self.pad_to_trim:
+            pack, counts = augment.multiview_crop(dev_views, self.trim_length, False, random_trim=True, pad=True)   # [V, trim_length]
+            counts = torch.tensor([min(max(c, self.min_samples), self.trim_length) for c in counts], dtype=torch.int32)
+        else:
+            pack = augment.multiview_crop(dev_views, self.trim_length, self.repeat_pad, random_trim=True)   # [V, L]
         lab = np.asarray([1.0] * n_pos + [0.0] * (len(views) - n_pos), dtype=np.float32)
         if pack.is_cuda:
             # the labels travel with the pack (pinned + asynchronous, on the builder's stream): as a host tensor they cost the TRAINING loop a
@@ -485,6 +494,8 @@ class PackDataset(Dataset):
             label = augment._h2d_pack([lab], pack.device)[0]
         else:
             label = torch.from_numpy(lab)
+        if counts is not None:
+            return uid, pack.t(), label, counts      # counts stay on the host: the model validates them there before its upload
         return uid, pack.t(), label
 
 
