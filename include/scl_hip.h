@@ -424,6 +424,32 @@ int scl_meanpool_bwd_varlen(const float* demb, const void* pre, void* dpre, cons
                             uint32_t seed, void* stream);
 int scl_meanpool_bwd_varlen_f32(const float* demb, const float* pre, float* dpre, const int32_t* len, int B, int T, int C, int ract,
                                 float drop_p, uint32_t seed, void* stream);
+/* Packed ("ragged") variable-length batches (csrc/attention_packed.hip): the valid frames of all utterances back to back, so that the
+ * row-wise kernels around the attention run over sum(frames) rows instead of B * T.
+ * row0: int32 [B + 1] ON THE DEVICE, row0[0] = 0, row0[b + 1] = row0[b] + frames[b]; utterance b owns rows row0[b] .. row0[b + 1] - 1 and
+ * row0[B] = Mv is the number of valid rows.  Mq (B <= Mq <= roundup(B * T, 64)): the rows of the launch, Mv <= Mq; rows [Mv, Mq) belong to
+ * no utterance.  The kernels read Mv from row0[B] and clamp every utterance to 1..T frames inside the Mq rows for memory safety;
+ * scl_packed_check_rows(host copy, B, T, Mq) returns SCL_EINVAL (nothing is launched) unless row0[0] = 0, every utterance holds 1..T rows
+ * and row0[B] <= Mq: call it before the upload.
+ * scl_attn_fwd_packed / _drop: scl_attn_fwd_varlen / _drop on qkv [Mq, 3 H D] -> ctx [Mq, H D] with utterance b's rows at row0[b] instead of
+ * b * T.  lse [B, H, T] and the dropout mask index ((b*H + h)*T + q)*T + k stay in the padded space: row row0[b] + t of ctx carries the bits
+ * of row b * T + t of the padded kernel, and lse is the same array.  Nothing is stored into a row at or beyond an utterance's end (it is the
+ * next utterance's); rows [Mv, Mq) of ctx are written as 0; rows >= Mq are not touched.  Head dim 64 only. */
+int scl_packed_check_rows(const int32_t* row0_host, int B, int T, int Mq);
+int scl_attn_fwd_packed(const void* qkv, void* ctx, float* lse, const int32_t* row0, int B, int T, int H, int D, int Mq, float scale,
+                        void* stream);
+int scl_attn_fwd_packed_drop(const void* qkv, void* ctx, float* lse, const int32_t* row0, int B, int T, int H, int D, int Mq, float scale,
+                             float drop_p, uint32_t drop_seed, void* stream);
+/* scl_attn_bwd_varlen on the packed rows (qkv / dqkv [Mq, 3 H D], ctx / dctx [Mq, H D]; lse and the delta workspace padded, ws:
+ * scl_attn_long_ws_bytes(B, T, H) bytes): rows of dqkv inside an utterance carry the bits of scl_attn_bwd_varlen, rows [Mv, Mq) are written as
+ * 0, rows >= Mq are not touched. */
+int scl_attn_bwd_packed(const void* qkv, const void* ctx, const void* dctx, const float* lse, const int32_t* row0, void* dqkv, void* ws, int B,
+                        int T, int H, int D, int Mq, float scale, float drop_p, uint32_t drop_seed, void* stream);
+/* scl_pack_rows: dst[row0[b] + t][:] = src[b * T + t][:] for t < frames[b], dst rows [Mv, Mq) = 0 (padded source rows are not read).
+ * scl_unpack_rows: dst[b * T + t][:] = t < frames[b] ? src[row0[b] + t][:] : 0.  Rows of C elements, f32 (is_f32 != 0) or bf16, C % 8 == 0,
+ * 16-byte aligned; the padded side holds B * T rows, the packed side Mq.  Every row of dst is written. */
+int scl_pack_rows(const void* src, void* dst, int is_f32, const int32_t* row0, int B, int T, int C, int Mq, void* stream);
+int scl_unpack_rows(const void* src, void* dst, int is_f32, const int32_t* row0, int B, int T, int C, int Mq, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* feature-extractor layer 0 (Conv1d(1,C,10,5) + LayerNorm + GELU), fused fwd / bwd            */

@@ -1,5 +1,6 @@
 // attn_tiles.h — LDS tile images, MFMA operand fragments and the K / V block staging shared by the streaming attention kernels
-// (attention_long.hip: fixed-length forward / backward; attention_varlen.hip: the same with per-utterance key counts).
+// (attention_long.hip: fixed-length forward / backward; attn_varlen_body.h: the same with per-utterance key counts, for the padded layout of
+// attention_varlen.hip and the packed one of attention_packed.hip).
 // Everything is internal to the including file (anonymous namespace, force-inlined).
 #pragma once
 #include "common.h"

@@ -40,6 +40,15 @@ F32_ATTN_CHUNK_BYTES = 1 << 30
 SCORE_X3PLANES = os.environ.get("SCL_SCORE_X3PLANES", "1") != "0"      # fp32 scoring path: plain linears as one bf16 GEMM over [hi | hi | lo] x [hi | lo | hi] (forward_f32)
 
 
+# Variable-length batches on the bf16 path (training, and scoring with SCL_SCORE_FP32=0): run the transformer layers on the valid frames
+# only, packed back to back (csrc/attention_packed.hip).  Opt-in (SCL_VARLEN_PACK=1); the callers read the attribute at call time.
+VARLEN_PACK = os.environ.get("SCL_VARLEN_PACK", "0") == "1"
+# The packed row count of a step is rounded up to a multiple of PACK_ROWS (ops.packed_rows): launch plans are recorded per row count, so
+# the bucket width trades rows wasted per step (< PACK_ROWS) against the number of plans (at most roundup(B * T, 64) / PACK_ROWS + 1 per
+# direction: 25 at 64 x 199 frames).  A multiple of 64: the weight-gradient reductions walk 64 rows per K step.
+PACK_ROWS = 512
+
+
 VARLEN_SETS = 4      # buffer sets kept per path for variable-length scoring batches (every distinct padded shape is a set of its own)
 
 
@@ -230,22 +239,24 @@ class Encoder:
         return self.P.f32(self.n(name))
 
     # ---- buffers ---------------------------------------------------------------------------------
-    def bufs(self, B, L, varlen=False, train=False):
+    def bufs(self, B, L, varlen=False, train=False, packed=False):
         """The buffer set of a [B, L] batch.  varlen: the set of a variable-length batch — streaming attention whatever T is (lse,
         attn_ws, no T x T buffers); a scoring batch's lives in the LRU, a training batch's (train: its saved activations wait for the
-        backward) is kept."""
+        backward) is kept.  packed: the set of the packed layout, a set of its own under the key (B, L, "packed") — one per padded shape,
+        sized for roundup(B * T, 64) rows whatever the step's lengths are."""
+        key = (B, L, "packed") if packed else (B, L)
         if varlen and train:
-            if (B, L) not in self._vbufs_train:
-                self._vbufs_train[(B, L)] = self._make_bufs(B, L, True)
-            return self._vbufs_train[(B, L)]
+            if key not in self._vbufs_train:
+                self._vbufs_train[key] = self._make_bufs(B, L, True, packed)
+            return self._vbufs_train[key]
         if varlen:
-            return self._vbufs.get_or_make((B, L), lambda: self._make_bufs(B, L, True))
+            return self._vbufs.get_or_make(key, lambda: self._make_bufs(B, L, True, packed))
         key = (B, L)
         if key not in self._bufs:
             self._bufs[key] = self._make_bufs(B, L, False)
         return self._bufs[key]
 
-    def _make_bufs(self, B, L, varlen):
+    def _make_bufs(self, B, L, varlen, packed=False):
         cfg, dev = self.cfg, self.dev
         C, E, H, Fd, K = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k
         Ts = cfg.conv_lens(L)
@@ -259,6 +270,8 @@ class Encoder:
         # puts them on the wide tiles / the grouped launch (K % 64 == 0) at batch sizes like 32 x 199 = 6368 rows too.
         Mp = (M + 63) // 64 * 64
         d = {"Ts": Ts, "T": T, "M": M, "Tp": Tp, "Mp": Mp}
+        # packed layout: the transformer layers run over up to Mp rows (every frame valid: roundup(B * T, 64)), so their buffers hold Mp rows
+        Mr = Mp if packed else M
         bfz = lambda rows, width, extra=0: torch.zeros(rows * width + extra, dtype=torch.bfloat16, device=dev)
         slack = 128 * max(C, E)  # tail slack: tile rows past the last frame are clamped/masked, never dereferenced past this
         d["z"] = [bf(B * t * C + slack) for t in Ts]
@@ -269,10 +282,10 @@ class Encoder:
         d["x0"] = f32(M * E)
         d["xpad"] = bf(B * (T + K) * E + slack)
         d["pc_pre"] = bf(M * E)
-        d["xin"] = [f32(M * E) for _ in range(cfg.layers + 1)]
+        d["xin"] = [f32(Mr * E) for _ in range(cfg.layers + 1)]
         d["h1"] = [bfz(Mp, E) for _ in range(cfg.layers)]
-        d["m1"], d["r1"] = [f32(M) for _ in range(cfg.layers)], [f32(M) for _ in range(cfg.layers)]
-        d["qkv"] = [bf(M * 3 * E + slack) for _ in range(cfg.layers)]
+        d["m1"], d["r1"] = [f32(Mr) for _ in range(cfg.layers)], [f32(Mr) for _ in range(cfg.layers)]
+        d["qkv"] = [bf(Mr * 3 * E + slack) for _ in range(cfg.layers)]
         d["fused_attn"] = (E // H == 64) and T <= 224      # scores stay on chip (csrc/attention.hip); else materialised path
         # streaming attention (csrc/attention_long.hip): above 512 frames, or from 225 frames with SCL_ATTN_LONG=1
         d["long_attn"] = (E // H == 64) and not d["fused_attn"] and (T > MAT_ATTN_MAX_T or ATTN_LONG)
@@ -292,19 +305,23 @@ class Encoder:
             d["S"] = f32(B * H * T * Tp)   # row stride Tp keeps the 4-wide epilogue stores aligned
             d["P"] = [bf(B * H * T * Tp + 1024) for _ in range(cfg.layers)]
         d["ctx"] = [bfz(Mp, E) for _ in range(cfg.layers)]
-        d["x1"] = [f32(M * E) for _ in range(cfg.layers)]
-        d["m2"], d["r2"] = [f32(M) for _ in range(cfg.layers)], [f32(M) for _ in range(cfg.layers)]
+        d["x1"] = [f32(Mr * E) for _ in range(cfg.layers)]
+        d["m2"], d["r2"] = [f32(Mr) for _ in range(cfg.layers)], [f32(Mr) for _ in range(cfg.layers)]
         d["h2"] = [bfz(Mp, E) for _ in range(cfg.layers)]
-        d["f"] = [bf(M * Fd) for _ in range(cfg.layers)]
+        d["f"] = [bf(Mr * Fd) for _ in range(cfg.layers)]
         d["a"] = [bfz(Mp, Fd) for _ in range(cfg.layers)]
-        d["out"], d["omean"], d["orstd"] = bf(M * E), f32(M), f32(M)
+        d["out"], d["omean"], d["orstd"] = bf(Mr * E), f32(Mr), f32(Mr)
+        if packed:      # the padded ends of the packed stretch: xin[0] before the pack, the output behind the unpack, d(xin[0]) behind its unpack
+            d["xin_pad"], d["out_pad"], d["dxin_pad"] = f32(M * E), bf(M * E), f32(M * E)
         # backward scratch (shared by all layers)
         # residual-gradient pairs (f32, bf16) rotate over FIVE buffers and d_f / dqkv alternate between TWO: the weight gradients of a layer may
         # be carried over into the grouped launch at the end of the NEXT layer (see _flush_slabs), so their operands outlive their layer by one
-        d["dx_rot"] = [(f32(M * E), bfz(Mp, E, slack)) for _ in range(5)]
+        d["dx_rot"] = [(f32(Mr * E), bfz(Mp, E, slack)) for _ in range(5)]
+        if packed:      # d(x0) behind the positional convolution is padded again: a pair of its own, the rotating ones stay packed
+            d["dx0_pad"] = (f32(M * E), bfz(Mp, E, slack))
         d["d_f"] = [bfz(Mp, Fd, slack), bfz(Mp, Fd, slack)]
-        d["d_h"] = bf(M * E + slack)
-        d["d_ctx"] = bf(M * E + slack)
+        d["d_h"] = bf(Mr * E + slack)
+        d["d_ctx"] = bf(Mr * E + slack)
         d["dqkv"] = [bfz(Mp, 3 * E, slack), bfz(Mp, 3 * E, slack)]
         d["dS"] = None if (d["fused_attn"] or d["long_attn"]) else bf(B * H * T * Tp + 1024)
         d["dcpad"] = bf(B * (T + K) * E + slack)
@@ -325,7 +342,7 @@ class Encoder:
         ncs = max(ops.colsum_nparts(B * (max(Ts[1:] + [T + K]) + 4)), 1) + 1      # conv bias sums run over the zero-padded dyp rows
         d["cs_part"] = f32(ncs * max(3 * E, Fd, C))
         d["qkv_bias_part"] = f32(B * 3 * E)
-        d["cs_fused"] = f32(4 * (M // 200 + 2) * Fd)      # per-tile column sums written by the fc2 data-gradient GEMM (main stream only)
+        d["cs_fused"] = f32(4 * (Mr // 200 + 2) * Fd)      # per-tile column sums written by the fc2 data-gradient GEMM (main stream only)
         d["conv0_ws"] = f32(ops.conv0_bwd_nparts(B, L, cfg.conv_kernels[0], cfg.conv_strides[0]) * C * (cfg.conv_kernels[0] + 3))
         d["conv0_stats"] = f32(B * Ts[0] * 2)   # per-frame (mean, rstd) of layer 0's LayerNorm
         # the weight-gradient queue (_wgrad fills it, _flush_slabs drains it at the end of a layer's backward):
@@ -478,14 +495,20 @@ class Encoder:
         ops.colreduce_seg(part, out, nparts, width, out2=out2, split=split)
 
     # ---- forward ---------------------------------------------------------------------------------
-    def forward(self, x, training=True, refresh=True, step_seed=0, frames=None, grad=None):
+    def forward(self, x, training=True, refresh=True, step_seed=0, frames=None, grad=None, packed=None):
         """x [B, L] fp32 contiguous on the GPU -> (enc_out bf16 [B*T, E], ctx).  step_seed: seed of this step's element-dropout masks.
         frames: int32 [B] on the GPU, the valid frames of each zero-padded utterance — rows beyond them are zeroed before the positional
         convolution and take no part in any soft-max (scl_attn_fwd_varlen / _drop in every layer); output rows beyond them are finite
         and meaningless.  A recorded plan keeps the tensor's address: overwrite it in place before a replay.
         grad: a backward(ctx, ...) will follow (default: autograd is on; a caller inside an autograd.Function, where it is off, says so).
         With frames, a forward that a backward follows takes the shape's training buffer set and the backward masks the same rows;
-        without one it is the scoring mode (training=False), whose sets live in the small LRU."""
+        without one it is the scoring mode (training=False), whose sets live in the small LRU.
+        packed: (row0, Mq) with frames — the transformer layers and the final LayerNorm run on the valid frames only, packed back to back
+        (ops.packed_rows: row0 int32 [B + 1] on the GPU, a fixed address like frames; Mq rows per launch, a multiple of 64).  The conv
+        stack, zero_tail_rows(x0), the positional convolution and its dropout stay padded (the convolution needs the utterance's slab);
+        then xin[0] is packed, the layers run over Mq rows with the packed attention, and the output is unpacked into the padded
+        [B*T, E] buffer with zero rows beyond each utterance.  The rows [row0[B], Mq) belong to no utterance: they start as zeros (the
+        pack writes them), every kernel but the attention works row by row and keeps them finite, and the attention writes zeros there."""
         cfg, P = self.cfg, self.P
         B, L = x.shape
         grad = torch.is_grad_enabled() if grad is None else bool(grad)
@@ -498,10 +521,18 @@ class Encoder:
         recording = ops._rec() is not None
         if refresh:
             self.refresh_weights()
-        d = self.bufs(B, L, varlen=frames is not None, train=grad)
+        if packed is not None and frames is None:
+            raise ValueError("encoder: packed=(row0, Mq) needs the frame counts of the batch (frames)")
+        d = self.bufs(B, L, varlen=frames is not None, train=grad, packed=packed is not None)
         C, E, H, Fd, K, G = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k, cfg.pos_groups
         D, Cg = E // H, E // G
         Ts, T, M, Tp = d["Ts"], d["T"], d["M"], d["Tp"]
+        Mt, xin0 = M, d["xin"][0]      # rows of the transformer layers; the positional convolution's (padded) output
+        if packed is not None:
+            row0, Mt = packed
+            if Mt % 64 or not B <= Mt <= d["Mp"]:
+                raise ValueError("encoder: packed row count %d: need a multiple of 64 in %d..%d" % (Mt, B, d["Mp"]))
+            xin0 = d["xin_pad"]
         fe = "feature_extractor.conv_layers.%d."
         # -- conv stack (M1)
         ops.conv0_fwd(x, self.b(fe % 0 + "0.weight"), self.b(fe % 0 + "0.bias"), self.b(fe % 0 + "2.1.weight"),
@@ -523,13 +554,15 @@ class Encoder:
             ops.zero_tail_rows(d["x0"], frames, B, T, E)      # fairseq: features[padding_mask] = 0
         ops.pad_rows(d["x0"], d["xpad"], B, T, E, T + K, K // 2)
         if ops.posconv_supported(T, K, G, Cg):      # utterance slab resident in LDS, weights streamed (csrc/posconv.hip); else the grouped GEMM
-            ops.posconv_mfma(d["xpad"], self.pos_wf, d["xin"][0], d["x0"], B, T, K, G, Cg, bias=self.b("encoder.pos_conv.0.bias"), c2=d["pc_pre"])
+            ops.posconv_mfma(d["xpad"], self.pos_wf, xin0, d["x0"], B, T, K, G, Cg, bias=self.b("encoder.pos_conv.0.bias"), c2=d["pc_pre"])
         else:
             ops.gemm(Op(d["xpad"], E, rpb=T, rbstride=(T + K) * E, cin=Cg, cout=E, bs2=Cg), Op(self.pos_wf, K * Cg, bs2=Cg * K * Cg),
-                     d["xin"][0], M, Cg, K * Cg, nb2=G, ldc=E, c_bs2=Cg, bias=self.b("encoder.pos_conv.0.bias"), bias_bs2=Cg,
+                     xin0, M, Cg, K * Cg, nb2=G, ldc=E, c_bs2=Cg, bias=self.b("encoder.pos_conv.0.bias"), bias_bs2=Cg,
                      act=ACT_GELU, c2=d["pc_pre"], R=d["x0"], rmode=1)
         if p_res > 0:      # F.dropout(x + pos_conv(x), p = cfg.dropout): after the residual add, so not a GEMM epilogue
-            self._slot(slots, ops.dropout(d["xin"][0], d["xin"][0], None, M * E, sseed(-1, self.SITE_ENC), p_res), ops.DROPOUT_SEED, -1, self.SITE_ENC)
+            self._slot(slots, ops.dropout(xin0, xin0, None, M * E, sseed(-1, self.SITE_ENC), p_res), ops.DROPOUT_SEED, -1, self.SITE_ENC)
+        if packed is not None:      # valid frames back to back, rows [row0[B], Mt) zero
+            ops.pack_rows(xin0, d["xin"][0], row0, B, T, E, Mt)
         # -- transformer layers
         skipped = []
         for n in range(cfg.layers):
@@ -540,11 +573,17 @@ class Encoder:
                 skipped.append(n)
                 continue
             ops.layernorm_fwd(xin, self.b(pn + "self_attn_layer_norm.weight"), self.b(pn + "self_attn_layer_norm.bias"),
-                              d["h1"][n], None, d["m1"][n], d["r1"][n], M, E)
-            ops.gemm(Op(d["h1"][n], E), self.W(pn + "self_attn.q_proj.weight", E), d["qkv"][n], M, 3 * E, E,
+                              d["h1"][n], None, d["m1"][n], d["r1"][n], Mt, E)
+            ops.gemm(Op(d["h1"][n], E), self.W(pn + "self_attn.q_proj.weight", E), d["qkv"][n], Mt, 3 * E, E,
                      bias=self.b(pn + "self_attn.q_proj.bias"))  # q,k,v biases are adjacent in the flat buffer
             qkv = d["qkv"][n]
-            if frames is not None and p_attn > 0:
+            if packed is not None and p_attn > 0:
+                e = ops.attn_fwd_packed_drop(qkv, d["ctx"][n], d["lse"][n], row0, B, T, H, D, Mt, D ** -0.5, drop_p=p_attn,
+                                             drop_seed=sseed(n, self.SITE_ATTN))
+                self._slot(slots, e, ops.ATTN_FWD_PACKED_SEED, n, self.SITE_ATTN)
+            elif packed is not None:
+                ops.attn_fwd_packed(qkv, d["ctx"][n], d["lse"][n], row0, B, T, H, D, Mt, D ** -0.5)
+            elif frames is not None and p_attn > 0:
                 e = ops.attn_fwd_varlen_drop(qkv, d["ctx"][n], d["lse"][n], frames, B, T, H, D, D ** -0.5, drop_p=p_attn,
                                              drop_seed=sseed(n, self.SITE_ATTN))
                 self._slot(slots, e, ops.ATTN_FWD_VARLEN_SEED, n, self.SITE_ATTN)
@@ -570,26 +609,30 @@ class Encoder:
                     self._slot(slots, ops.dropout_rows(d["P"][n], Pv, B * H * T, T, Tp, sseed(n, self.SITE_ATTN), p_attn), ops.DROPOUT_ROWS_SEED, n, self.SITE_ATTN)
                 ops.gemm(Op(Pv, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=2 * E),
                          d["ctx"][n], T, D, T, b_t=True, nb1=B, nb2=H, ldc=E, c_bs1=T * E, c_bs2=D)
-            dsc = ops.gemm(Op(d["ctx"][n], E), self.W(pn + "self_attn.out_proj.weight", E), d["x1"][n], M, E, E,
+            dsc = ops.gemm(Op(d["ctx"][n], E), self.W(pn + "self_attn.out_proj.weight", E), d["x1"][n], Mt, E, E,
                            bias=self.b(pn + "self_attn.out_proj.bias"), R=xin, rmode=1, drop_p=p_res, drop_seed=sseed(n, self.SITE_1))    # dropout1
             if p_res > 0 and recording:
                 self._slot(slots, dsc, None, n, self.SITE_1)
             ops.layernorm_fwd(d["x1"][n], self.b(pn + "final_layer_norm.weight"), self.b(pn + "final_layer_norm.bias"),
-                              d["h2"][n], None, d["m2"][n], d["r2"][n], M, E)
+                              d["h2"][n], None, d["m2"][n], d["r2"][n], Mt, E)
             # fc1's epilogue stores gelu'(pre-activation) as its second output (one erf / exp evaluation serves gelu and its derivative);
             # fc2's data-gradient epilogue multiplies by the stored number
-            dsc = ops.gemm(Op(d["h2"][n], E), self.W(pn + "fc1.weight", E), d["a"][n], M, Fd, E, bias=self.b(pn + "fc1.bias"),
+            dsc = ops.gemm(Op(d["h2"][n], E), self.W(pn + "fc1.weight", E), d["a"][n], Mt, Fd, E, bias=self.b(pn + "fc1.bias"),
                            act=ACT_GELU_DC2, c2=d["f"][n], drop_p=p_act, drop_seed=sseed(n, self.SITE_2))                         # dropout2 (activation)
             if p_act > 0 and recording:
                 self._slot(slots, dsc, None, n, self.SITE_2)
-            dsc = ops.gemm(Op(d["a"][n], Fd), self.W(pn + "fc2.weight", Fd), xout, M, E, Fd, bias=self.b(pn + "fc2.bias"),
+            dsc = ops.gemm(Op(d["a"][n], Fd), self.W(pn + "fc2.weight", Fd), xout, Mt, E, Fd, bias=self.b(pn + "fc2.bias"),
                            R=d["x1"][n], rmode=1, drop_p=p_res, drop_seed=sseed(n, self.SITE_3))                                # dropout3
             if p_res > 0 and recording:
                 self._slot(slots, dsc, None, n, self.SITE_3)
         ops.layernorm_fwd(d["xin"][cfg.layers], self.b("encoder.layer_norm.weight"), self.b("encoder.layer_norm.bias"),
-                          d["out"], None, d["omean"], d["orstd"], M, E)
-        return d["out"], {"d": d, "x": x, "B": B, "L": L, "skipped": skipped, "drop": (p_res, p_attn, p_act, p_in), "step_seed": step_seed,
-                          "drop_slots": slots, "frames": frames}
+                          d["out"], None, d["omean"], d["orstd"], Mt, E)
+        out = d["out"]
+        if packed is not None:      # back to the padded [B*T, E] rectangle, zero rows beyond each utterance
+            out = d["out_pad"]
+            ops.unpack_rows(d["out"], out, row0, B, T, E, Mt)
+        return out, {"d": d, "x": x, "B": B, "L": L, "skipped": skipped, "drop": (p_res, p_attn, p_act, p_in), "step_seed": step_seed,
+                     "drop_slots": slots, "frames": frames, "packed": packed}
 
     # ---- fp32 scoring forward ----------------------------------------------------------------------
     def _f32_weights(self):
@@ -736,16 +779,32 @@ class Encoder:
         give that).  Two kernels then carry the mask: scl_attn_bwd_varlen writes zero dqkv rows there, and the rows of d(x0) are zeroed
         behind the positional convolution's data gradient (the backward of the forward's zero_tail_rows(x0)).  Every other kernel of the
         chain works row by row, so the gradient of a padded row is exactly 0 from the head down to the conv stack, and padded rows add
-        nothing to any weight, bias or LayerNorm gradient."""
+        nothing to any weight, bias or LayerNorm gradient.
+        A packed forward (ctx["packed"] = (row0, Mq)): d_out is packed, the layers run over M = Mp = Mq rows with scl_attn_bwd_packed,
+        and d(xin[0]) is unpacked into the padded buffer; everything behind it runs as above.  Inside the packed stretch there are no padded
+        rows, only the tail [row0[B], Mq) that belongs to no utterance.  Going forward those rows start as zeros and stay finite through the
+        row-wise kernels.  Going backward they start as exact zeros — the pack of d_out writes zeros there, scl_attn_bwd_packed writes zero
+        dqkv rows there — and a row-wise kernel turns a zero gradient row into a zero gradient row (finite activations, masks only scale),
+        so every gradient buffer is exactly 0 there.  The weight, bias and LayerNorm reductions run over the Mq rows only (Mq is a multiple
+        of 64: no K step reaches a stale row), and a zero gradient row times a finite activation row adds nothing to them."""
         cfg, P = self.cfg, self.P
         d, x, B, L = ctx["d"], ctx["x"], ctx["B"], ctx["L"]
-        frames = ctx.get("frames")
+        frames, packed = ctx.get("frames"), ctx.get("packed")
         C, E, H, Fd, K, G = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k, cfg.pos_groups
         D, Cg = E // H, E // G
         Ts, T, M, Tp, Mp = d["Ts"], d["T"], d["M"], d["Tp"], d["Mp"]
-        if not (WGRAD_GROUP and Mp // 64 >= WGRAD_GROUP_MIN_KSTEPS):
+        Mt = M      # rows of the transformer layers
+        if packed is not None:
+            row0, Mt = packed
+            Mp = Mt      # a multiple of 64
+            key = "d_out_pk_f32" if d_out.dtype == torch.float32 else "d_out_pk"
+            if key not in d:
+                d[key] = torch.empty(d["Mp"] * E, dtype=d_out.dtype, device=self.dev)
+            ops.pack_rows(d_out, d[key], row0, B, T, E, Mt)      # rows [row0[B], Mt): zeros
+            d_out = d[key]
+        elif not (WGRAD_GROUP and Mp // 64 >= WGRAD_GROUP_MIN_KSTEPS):
             Mp = M      # short reductions stay on the split-K path, which is faster on the exact row count (pack of 11: 16.2 vs 17.6 ms per step)
-        nlnM = ops.layernorm_bwd_nparts(M)
+        nlnM = ops.layernorm_bwd_nparts(Mt)
         p_res, p_attn, p_act, p_in = ctx.get("drop", (0.0, 0.0, 0.0, 0.0))
         step_seed = ctx.get("step_seed", 0)
         slots = []
@@ -763,7 +822,7 @@ class Encoder:
         dx, dxb = rot[cur]
         dout, lyr = mask3_of(active)
         e = ops.layernorm_bwd(d_out, d["xin"][cfg.layers], d["omean"], d["orstd"], self.b("encoder.layer_norm.weight"), None, None,
-                              dx, dxb, d["ln_part"], M, E, dout=dout)
+                              dx, dxb, d["ln_part"], Mt, E, dout=dout)
         if lyr is not None:
             self._slot(slots, e, ops.LN_BWD_DOUT_SEED, lyr, self.SITE_3)
         self._ln_grads(d, nlnM, E, "encoder.layer_norm.weight", "encoder.layer_norm.bias")
@@ -786,10 +845,10 @@ class Encoder:
                 self._wgrad(d, Op(dxb, E), Op(d["a"][n], Fd), P.g(self.n(pn + "fc2.weight")), E, Fd, Mp, slot=0)
             # fc1.bias.grad = colsum(d_f): summed per tile by the GEMM that writes d_f (wide tiles), else by a pass over d_f
             fc2_dgrad = dict(b_t=True, R=d["f"][n], rmode=2, ract=RACT_STORED, drop_p=p_act, drop_seed=sseed(n, self.SITE_2))
-            nrows = ops.gemm_colsum_rows(Op(dxb, E), self.W(pn + "fc2.weight", Fd), d_f, M, Fd, E, **fc2_dgrad)
+            nrows = ops.gemm_colsum_rows(Op(dxb, E), self.W(pn + "fc2.weight", Fd), d_f, Mt, Fd, E, **fc2_dgrad)
             if nrows * Fd > d["cs_fused"].numel():
                 nrows = 0
-            dsc = ops.gemm(Op(dxb, E), self.W(pn + "fc2.weight", Fd), d_f, M, Fd, E, colsum_part=d["cs_fused"] if nrows else None, **fc2_dgrad)
+            dsc = ops.gemm(Op(dxb, E), self.W(pn + "fc2.weight", Fd), d_f, Mt, Fd, E, colsum_part=d["cs_fused"] if nrows else None, **fc2_dgrad)
             if p_act > 0 and recording:
                 self._slot(slots, dsc, None, n, self.SITE_2)
             jobs = []      # the (up to) four small column reductions that close this layer's backward: one launch at the end of the layer
@@ -797,13 +856,13 @@ class Encoder:
                 jobs.append((d["cs_fused"], P.g(self.n(pn + "fc1.bias")), nrows, Fd))
             with self._side():
                 if not nrows:
-                    self._bias_grad(d, d_f, M, Fd, pn + "fc1.bias")
+                    self._bias_grad(d, d_f, Mt, Fd, pn + "fc1.bias")
                 self._wgrad(d, Op(d_f, Fd), Op(d["h2"][n], E), P.g(self.n(pn + "fc1.weight")), Fd, E, Mp, slot=1)
-            ops.gemm(Op(d_f, Fd), self.W(pn + "fc1.weight", E), d["d_h"], M, E, Fd, b_t=True)
+            ops.gemm(Op(d_f, Fd), self.W(pn + "fc1.weight", E), d["d_h"], Mt, E, Fd, b_t=True)
             # dx (= d xout) is the gradient of fc2's output: its column sum (fc2.bias.grad) rides on this LayerNorm backward
             # dres = d(xout): fc2.bias.grad = colsum(dres x dropout3 mask); the bf16 output d(x1) feeds out_proj's gradients: dropout1 mask
             e = ops.layernorm_bwd(d["d_h"], d["x1"][n], d["m2"][n], d["r2"][n], self.b(pn + "final_layer_norm.weight"), None, dx,
-                                  other, otherb, d["ln_part"], M, E, sum_dres=True,
+                                  other, otherb, d["ln_part"], Mt, E, sum_dres=True,
                                   din=(sseed(n, self.SITE_3), p_res), dout=(sseed(n, self.SITE_1), p_res))
             if p_res > 0:
                 self._slot(slots, e, ops.LN_BWD_DIN_SEED, n, self.SITE_3)
@@ -814,9 +873,14 @@ class Encoder:
             # ---- attention:  x1 = xin + ctx Wo^T + bo
             with self._side():
                 self._wgrad(d, Op(dxb, E), Op(d["ctx"][n], E), P.g(self.n(pn + "self_attn.out_proj.weight")), E, E, Mp, slot=2)
-            ops.gemm(Op(dxb, E), self.W(pn + "self_attn.out_proj.weight", E), d["d_ctx"], M, E, E, b_t=True)
+            ops.gemm(Op(dxb, E), self.W(pn + "self_attn.out_proj.weight", E), d["d_ctx"], Mt, E, E, b_t=True)
             qkv, dqkv = d["qkv"][n], d["dqkv"][li & 1]
-            if frames is not None:      # every row of dqkv written, rows beyond the utterance's frames as 0; q/k/v bias gradients: colsum_reduce below
+            if packed is not None:      # rows of an utterance and the zero tail [row0[B], Mt) written; q/k/v bias gradients: colsum_reduce below
+                e = ops.attn_bwd_packed(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], row0, dqkv, d["attn_ws"], B, T, H, D, Mt, D ** -0.5,
+                                        drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
+                if p_attn > 0:
+                    self._slot(slots, e, ops.ATTN_BWD_PACKED_SEED, n, self.SITE_ATTN)
+            elif frames is not None:      # every row of dqkv written, rows beyond the utterance's frames as 0; q/k/v bias gradients: colsum_reduce below
                 e = ops.attn_bwd_varlen(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], frames, dqkv, d["attn_ws"], B, T, H, D, D ** -0.5,
                                         drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
                 if p_attn > 0:
@@ -857,15 +921,15 @@ class Encoder:
                          c_bs1=T * 3 * E, c_bs2=D, c_offset=E, **bq)                                   # dK = s dS^T Q
             with self._side():
                 if not d["fused_attn"]:
-                    ops.colsum_reduce(dqkv, d["cs_part"], self._qkv_view(pn, "bias"), M, 3 * E)
+                    ops.colsum_reduce(dqkv, d["cs_part"], self._qkv_view(pn, "bias"), Mt, 3 * E)
                 self._wgrad(d, Op(dqkv, 3 * E), Op(d["h1"][n], E), self._qkv_view(pn, "weight"), 3 * E, E, Mp, slot=3)
-            ops.gemm(Op(dqkv, 3 * E), self.W(pn + "self_attn.q_proj.weight", E), d["d_h"], M, E, 3 * E, b_t=True)
+            ops.gemm(Op(dqkv, 3 * E), self.W(pn + "self_attn.q_proj.weight", E), d["d_h"], Mt, E, 3 * E, b_t=True)
             # dx (= d x1) is the gradient of out_proj's output: out_proj.bias.grad rides on this LayerNorm backward
             # dres = d(x1): out_proj.bias.grad = colsum(dres x dropout1 mask); the bf16 output d(xin) feeds the fc2 gradients of the next
             # active layer below: its dropout3 mask
             dout, lyr = mask3_of([m_ for m_ in active if m_ < n])
             e = ops.layernorm_bwd(d["d_h"], xin, d["m1"][n], d["r1"][n], self.b(pn + "self_attn_layer_norm.weight"), None, dx,
-                                  other, otherb, d["ln_part2"], M, E, sum_dres=True,
+                                  other, otherb, d["ln_part2"], Mt, E, sum_dres=True,
                                   din=(sseed(n, self.SITE_1), p_res), dout=dout)
             if p_res > 0:
                 self._slot(slots, e, ops.LN_BWD_DIN_SEED, n, self.SITE_1)
@@ -885,6 +949,9 @@ class Encoder:
             prev_off = this_off
             if self.on_grads_ready is not None and ready_off is not None:
                 ops.host_callback(self.on_grads_ready, ready_off)
+        if packed is not None:      # d(xin[0]) back to the padded rectangle (zero rows beyond each utterance): the convolution needs the slab
+            ops.unpack_rows(dx, d["dxin_pad"], row0, B, T, E, Mt)
+            dx, (other, otherb) = d["dxin_pad"], d["dx0_pad"]
         # ---- positional conv:  xin0 = x0 + gelu(conv(x0) + b)
         pb = K // 2 - 1
         if p_res > 0:      # backward of F.dropout(x0 + pos_conv(x0)): dx = d(xin[0]) x mask, in place (nothing reads the unmasked value again)
@@ -919,7 +986,7 @@ class Encoder:
         ops.gemm(Op(otherb, E), self.W("post_extract_proj.weight", C), d["d_h"], M, C, E, b_t=True)
         ops.layernorm_bwd(d["d_h"], d["z"][-1], d["fmean"], d["frstd"], self.b("layer_norm.weight"), None, None, None, d["dz"][-1],
                           d["ln_part"], M, C)
-        self._ln_grads(d, nlnM, C, "layer_norm.weight", "layer_norm.bias")
+        self._ln_grads(d, ops.layernorm_bwd_nparts(M), C, "layer_norm.weight", "layer_norm.bias")      # the padded rows again (nlnM: the layers')
         # ---- conv stack, layers 6..1
         fe = "feature_extractor.conv_layers.%d."
         for i in reversed(range(1, len(Ts))):

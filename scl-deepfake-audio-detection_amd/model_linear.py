@@ -19,6 +19,7 @@ import math
 import torch
 from torch import nn
 
+from . import encoder as ENC
 from . import ops
 from .encoder import Encoder, VarlenSets, W2VConfig, param_specs
 from .lib import ACT_LEAKY, ACT_RELU
@@ -100,8 +101,8 @@ class _ModelFn(torch.autograd.Function):
     buffers; backward consumes (d_logp, d_feats, d_emb) and fills the flat gradient buffer."""
 
     @staticmethod
-    def forward(ctx, model, x, anchor, frames=None):
-        out, feats, emb, saved = model._run_forward(x, frames, train=frames is not None)
+    def forward(ctx, model, x, anchor, frames=None, rows=None):
+        out, feats, emb, saved = model._run_forward(x, frames, train=frames is not None, rows=rows)
         ctx.model, ctx.saved = model, saved
         # the outputs live in static per-(B, L) buffers (launch plans point at them): hand out copies, so results
         # of successive forward calls do not alias (3 small device copies)
@@ -110,7 +111,7 @@ class _ModelFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_out, d_feats, d_emb):
         ctx.model._run_backward(ctx.saved, d_out, d_feats, d_emb)
-        return None, None, None, None
+        return None, None, None, None, None
 
 
 class Model(nn.Module):
@@ -208,48 +209,68 @@ class Model(nn.Module):
                                      d_logp=f32(B, N_CLASS), d_feats=f32(B, T, HEAD_DIM), d_emb=f32(B, HEAD_DIM), plans={})
         return self._states[key]
 
-    def _varlen_state(self, B, L):
+    def _row0_buf(self, B, packed):
+        """The packed layout's row offsets [B + 1] of a variable-length state: a device buffer of fixed address like the frame counts,
+        overwritten before every replay (None for the padded layout)."""
+        return torch.arange(B + 1, dtype=torch.int32, device=self.device) if packed else None
+
+    def _varlen_state(self, B, L, packed=False):
         """_state for a variable-length scoring batch: forward-only buffers, the frame counts (a device buffer of fixed address, overwritten
-        before every replay of the shape's plan) and the shape's own head buffers."""
+        before every replay of the shape's plan) and the shape's own head buffers.  packed: the state of the packed layout (a state of its
+        own, keyed like the encoder's buffer set), with the row offsets besides; its plans are kept per packed row count."""
         def make():
             T = self.cfg.conv_lens(L)[-1]
             f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
             return dict(T=T, x=f32(B, L), feats=f32(B, T, HEAD_DIM), emb=f32(B, HEAD_DIM), logp=f32(B, N_CLASS),
-                        frames=torch.ones(B, dtype=torch.int32, device=self.device), hb=self._head_bufs(B, T, keep=False), plans={})
-        return self._vstates.get_or_make((B, L), make)
+                        frames=torch.ones(B, dtype=torch.int32, device=self.device), row0=self._row0_buf(B, packed),
+                        hb=self._head_bufs(B, T, keep=False), plans={})
+        return self._vstates.get_or_make((B, L, "packed") if packed else (B, L), make)
 
-    def _varlen_train_state(self, B, L):
+    def _varlen_train_state(self, B, L, packed=False):
         """_state for a variable-length training batch: the boundary buffers of both directions, the frame counts (fixed address, read by
-        the forward's and the backward's plans) and the shape's own head buffers."""
-        key = (B, L)
+        the forward's and the backward's plans) and the shape's own head buffers.  packed: as in _varlen_state."""
+        key = (B, L, "packed") if packed else (B, L)
         if key not in self._vstates_train:
             T = self.cfg.conv_lens(L)[-1]
             f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
             self._vstates_train[key] = dict(T=T, x=f32(B, L), feats=f32(B, T, HEAD_DIM), emb=f32(B, HEAD_DIM), logp=f32(B, N_CLASS),
                                             d_logp=f32(B, N_CLASS), d_feats=f32(B, T, HEAD_DIM), d_emb=f32(B, HEAD_DIM), train=True,
-                                            frames=torch.ones(B, dtype=torch.int32, device=self.device),
+                                            frames=torch.ones(B, dtype=torch.int32, device=self.device), row0=self._row0_buf(B, packed),
                                             hb=self._head_bufs(B, T, keep=False), plans={})
         return self._vstates_train[key]
 
-    def _frames(self, lengths, B, L):
-        """Sample counts of a zero-padded batch -> frame counts as an int32 device tensor (validated on the host first).  Counts below the
-        shortest clip that yields a frame count as that clip: its zero padding is part of the signal, as for a file padded on disk."""
+    def _frame_counts(self, lengths, B, L):
+        """Sample counts of a zero-padded batch -> frame counts, a list of ints validated on the host.  Counts below the shortest clip that
+        yields a frame count as that clip: its zero padding is part of the signal, as for a file padded on disk."""
         lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
         lo = self.cfg.min_samples()
         if len(lengths) != B or L < lo or any(n < 1 or n > L for n in lengths):
             raise ValueError("lengths: need one sample count in 1..%d per row of the [%d, %d] batch (at least %d samples per row), got %r"
                              % (L, B, L, lo, lengths))
-        frames = ops.check_lengths([self.cfg.conv_lens(max(n, lo))[-1] for n in lengths], self.cfg.conv_lens(L)[-1])
-        host = torch.tensor(frames, dtype=torch.int32)
+        return ops.check_lengths([self.cfg.conv_lens(max(n, lo))[-1] for n in lengths], self.cfg.conv_lens(L)[-1])
+
+    def _upload_i32(self, values):
+        host = torch.tensor(values, dtype=torch.int32)
         return (host.pin_memory() if self.device.type == "cuda" else host).to(self.device, non_blocking=True)
 
-    def _run_forward(self, x, frames=None, train=False):
+    def _packed_rows(self, counts, L):
+        """The packed layout of a batch with these frame counts: (row offsets [B + 1] as an int32 device tensor, Mq rows per launch), both
+        from the host-side counts (ops.packed_rows with the encoder's PACK_ROWS)."""
+        row0, Mq = ops.packed_rows(counts, self.cfg.conv_lens(L)[-1], ENC.PACK_ROWS)
+        return self._upload_i32(row0), Mq
+
+    def _run_forward(self, x, frames=None, train=False, rows=None):
+        """rows: (row0, Mq) of _packed_rows — the encoder's transformer layers run on the packed valid frames (with frames only)."""
         B, L = x.shape
         training = bool(self.training)
         ssl_train = False if self.flag_fix_ssl else bool(self.is_train and training)   # SURVEY.md §3.2 quirk
+        Mq = None
         if frames is not None:
-            st = self._varlen_train_state(B, L) if train else self._varlen_state(B, L)
+            st = self._varlen_train_state(B, L, rows is not None) if train else self._varlen_state(B, L, rows is not None)
             st["frames"].copy_(frames)
+            if rows is not None:
+                st["row0"].copy_(rows[0])
+                Mq = int(rows[1])
         else:
             st = self._state(B, L)
         st["x"].copy_(x)
@@ -258,7 +279,7 @@ class Model(nn.Module):
         seeds = [(self._step_seed + 7919 * j) & 0x7FFFFFFF for j in range(3)]
         self.encoder.refresh_weights()
         use_plan = self.cfg.encoder_layerdrop == 0 or not ssl_train
-        pk = ("fwd", training, ssl_train)
+        pk = ("fwd", training, ssl_train) if Mq is None else ("fwd", training, ssl_train, Mq)      # packed: a plan per row count
         plan = st["plans"].get(pk) if use_plan else None
         if plan is not None:
             for dsc, sd in zip(plan["drop_descs"], seeds):
@@ -270,16 +291,17 @@ class Model(nn.Module):
             return st["logp"], st["feats"], st["emb"], saved
         if use_plan:
             ops.start_recording()
-        saved, drop_descs = self._forward_kernels(st, B, L, ssl_train, drop, seeds)
+        saved, drop_descs = self._forward_kernels(st, B, L, ssl_train, drop, seeds, Mq)
         if use_plan:
             st["plans"][pk] = dict(calls=ops.stop_recording(), drop_descs=drop_descs, saved=saved)
         return st["logp"], st["feats"], st["emb"], dict(saved, seeds=seeds)
 
-    def _forward_kernels(self, st, B, L, ssl_train, drop, seeds):
+    def _forward_kernels(self, st, B, L, ssl_train, drop, seeds, Mq=None):
         P, E = self.P, self.cfg.embed
         frames = st.get("frames")      # a variable-length state (scoring, or training: st["train"])
         enc_out, ectx = self.encoder.forward(st["x"], training=ssl_train, refresh=False, step_seed=self._step_seed, frames=frames,
-                                             grad=bool(st.get("train")) if frames is not None else None)
+                                             grad=bool(st.get("train")) if frames is not None else None,
+                                             packed=None if Mq is None else (st["row0"], Mq))
         T = ectx["d"]["T"]
         M = B * T
         hb = st["hb"] if frames is not None else self._head_bufs(B, T)
@@ -317,6 +339,8 @@ class Model(nn.Module):
             self.encoder.on_grads_ready = self.grad_sync.ready_above
         use_plan = not sv["ectx"]["skipped"] and self.cfg.encoder_layerdrop == 0
         pk = ("bwd", sv["drop"] > 0, self.grad_sync is not None)
+        if sv["ectx"].get("packed") is not None:      # packed: a plan per row count (the row offsets are the state's, already in place)
+            pk += (sv["ectx"]["packed"][1],)
         plan = st["plans"].get(pk) if use_plan else None
         if plan is not None:
             plan["drop_descs"][0].drop_seed = seeds[1]
@@ -401,18 +425,22 @@ class Model(nn.Module):
         if x.dim() == 3:
             x = x[:, :, 0]
         x = x.to(device=self.device, dtype=torch.float32).contiguous()   # main.py:60 hands over a transposed view
-        frames = None
+        frames = rows = None
         if lengths is not None:
             if torch.is_grad_enabled() != bool(self.training):
                 raise NotImplementedError("forward(x, lengths) is a scoring mode on model.eval() under torch.no_grad() and a training "
                                           "mode on model.train() with autograd on; eval with autograd, or train under no_grad, is neither")
-            frames = self._frames(lengths, x.shape[0], x.shape[1])
+            counts = self._frame_counts(lengths, x.shape[0], x.shape[1])
+            frames = self._upload_i32(counts)
+            # the packed layout (encoder.VARLEN_PACK) serves the bf16 encoder path; the fp32 scoring path's attention is strided per utterance
+            if ENC.VARLEN_PACK and (self.training or not SCORE_FP32):
+                rows = self._packed_rows(counts, x.shape[1])
         if torch.is_grad_enabled() and any(p.requires_grad for p in (self._anchor,)):
-            out, feats, emb = _ModelFn.apply(self, x, self._anchor, frames)
+            out, feats, emb = _ModelFn.apply(self, x, self._anchor, frames, rows)
         elif not self.training and SCORE_FP32:
             out, feats, emb = self._score_fp32(x, frames)
         else:
-            out, feats, emb, _ = self._run_forward(x, frames)
+            out, feats, emb, _ = self._run_forward(x, frames, rows=rows)
             out, feats, emb = out.clone(), feats.clone(), emb.clone()
         if self.is_train:
             return out, feats, emb

@@ -316,6 +316,7 @@ LN_BWD_DIN_SEED, LN_BWD_DOUT_SEED = 22, 24      # positions of the two mask seed
 ATTN_FWD_SEED, ATTN_BWD_SEED, DROPOUT_SEED = 9, 12, 4
 ATTN_FWD_LONG_SEED, ATTN_BWD_LONG_SEED = 9, 12      # positions of the mask seed in recorded scl_attn_fwd_long / scl_attn_bwd_long calls
 ATTN_FWD_VARLEN_SEED, ATTN_BWD_VARLEN_SEED = 10, 13      # the same in recorded scl_attn_fwd_varlen_drop / scl_attn_bwd_varlen calls
+ATTN_FWD_PACKED_SEED, ATTN_BWD_PACKED_SEED = 11, 14      # the same in recorded scl_attn_fwd_packed_drop / scl_attn_bwd_packed calls
 MEANPOOL_BWD_SEED, MEANPOOL_BWD_VARLEN_SEED = 8, 9      # the head-dropout seed in recorded scl_meanpool_bwd / scl_meanpool_bwd_varlen calls
 
 
@@ -555,6 +556,67 @@ def meanpool_bwd_varlen(demb, pre, dpre, lens, B, T, C, ract, drop_p=0.0, seed=0
     assert pre.dtype == dpre.dtype and lens.numel() >= B
     return _call("scl_meanpool_bwd_varlen_f32" if _isf32(pre) else "scl_meanpool_bwd_varlen", _p(demb), _p(pre), _p(dpre), _p(_klen(lens)),
                  B, T, C, ract, float(drop_p), int(seed), _stream())
+
+
+# ---- packed variable-length batches (csrc/attention_packed.hip) ------------------------------------------------------------------------
+def packed_rows(frames, T, pack_rows=512):
+    """Host side of the packed layout: frame counts (already validated, 1..T each) -> (row0, Mq).  row0: the B + 1 row offsets
+    (row0[b + 1] = row0[b] + frames[b], row0[B] = Mv valid rows); Mq = min(roundup(Mv, pack_rows), roundup(B * T, 64)), the row count the
+    launches run over — the bucket rule: plans are recorded per Mq, so `pack_rows` (a multiple of 64: the weight-gradient reductions step
+    by 64 rows) trades rows wasted per step (< pack_rows) for the number of plans (roundup(B * T, 64) / pack_rows + 1 at most)."""
+    frames = [int(v) for v in frames]
+    if pack_rows < 64 or pack_rows % 64:
+        raise ValueError("packed_rows: pack_rows must be a positive multiple of 64, got %r" % (pack_rows,))
+    row0 = [0]
+    for n in frames:
+        row0.append(row0[-1] + n)
+    cap = (len(frames) * int(T) + 63) // 64 * 64
+    Mq = min((row0[-1] + pack_rows - 1) // pack_rows * pack_rows, cap)
+    return check_packed_rows(row0, T, Mq), Mq
+
+
+def check_packed_rows(row0, T, Mq):
+    """Raise SclError unless the host-side row offsets start at 0, give every utterance 1..T rows and end within Mq (call before the
+    upload: the kernels only clamp).  Returns the offsets as a list of ints."""
+    row0 = [int(v) for v in row0]
+    rc = L.load().scl_packed_check_rows((ctypes.c_int32 * max(len(row0), 1))(*row0), len(row0) - 1, int(T), int(Mq))
+    if rc != 0:
+        L.check(rc, "scl_packed_check_rows")
+    return row0
+
+
+def attn_fwd_packed(qkv, ctx, lse, row0, B, T, H, D, Mq, scale):
+    """attn_fwd_varlen on packed rows: utterance b at rows row0[b] .. row0[b + 1] - 1 of qkv / ctx (device int32 [B + 1]); lse stays
+    [B, H, T]; nothing is stored past an utterance's end, ctx rows [row0[B], Mq) are written as 0."""
+    assert row0.numel() >= B + 1
+    return _call("scl_attn_fwd_packed", _p(qkv), _p(ctx), _p(lse), _p(_klen(row0)), B, T, H, D, int(Mq), float(scale), _stream())
+
+
+def attn_fwd_packed_drop(qkv, ctx, lse, row0, B, T, H, D, Mq, scale, drop_p=0.0, drop_seed=0):
+    """attn_fwd_packed with attention dropout (the padded layout's mask index, so the same masks); returns the recorded call."""
+    assert row0.numel() >= B + 1
+    return _call("scl_attn_fwd_packed_drop", _p(qkv), _p(ctx), _p(lse), _p(_klen(row0)), B, T, H, D, int(Mq), float(scale), float(drop_p),
+                 int(drop_seed), _stream())
+
+
+def attn_bwd_packed(qkv, ctx, dctx, lse, row0, dqkv, ws, B, T, H, D, Mq, scale, drop_p=0.0, drop_seed=0):
+    """attn_bwd_varlen on packed rows: dqkv rows inside an utterance are written, rows [row0[B], Mq) as 0, nothing else."""
+    assert row0.numel() >= B + 1
+    assert ws.numel() * ws.element_size() >= attn_long_ws_bytes(B, T, H), "attn_bwd_packed: workspace too small"
+    return _call("scl_attn_bwd_packed", _p(qkv), _p(ctx), _p(dctx), _p(lse), _p(_klen(row0)), _p(dqkv), _p(ws), B, T, H, D, int(Mq),
+                 float(scale), float(drop_p), int(drop_seed), _stream())
+
+
+def pack_rows(src, dst, row0, B, T, C, Mq):
+    """dst[row0[b] + t] = src[b*T + t] for t < frames[b]; dst rows [row0[B], Mq) = 0.  f32 or bf16 rows of C elements (C % 8 == 0)."""
+    assert src.dtype == dst.dtype and row0.numel() >= B + 1 and src.numel() >= B * T * C and dst.numel() >= Mq * C
+    _call("scl_pack_rows", _p(src), _p(dst), _isf32(src), _p(_klen(row0)), B, T, C, int(Mq), _stream())
+
+
+def unpack_rows(src, dst, row0, B, T, C, Mq):
+    """dst[b*T + t] = src[row0[b] + t] for t < frames[b], 0 beyond: every row of the padded dst is written."""
+    assert src.dtype == dst.dtype and row0.numel() >= B + 1 and src.numel() >= Mq * C and dst.numel() >= B * T * C
+    _call("scl_unpack_rows", _p(src), _p(dst), _isf32(src), _p(_klen(row0)), B, T, C, int(Mq), _stream())
 
 
 def attn_long_ws_bytes(B, T, H):
