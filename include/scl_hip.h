@@ -450,6 +450,15 @@ int scl_attn_bwd_packed(const void* qkv, const void* ctx, const void* dctx, cons
  * 16-byte aligned; the padded side holds B * T rows, the packed side Mq.  Every row of dst is written. */
 int scl_pack_rows(const void* src, void* dst, int is_f32, const int32_t* row0, int B, int T, int C, int Mq, void* stream);
 int scl_unpack_rows(const void* src, void* dst, int is_f32, const int32_t* row0, int B, int T, int C, int Mq, void* stream);
+/* scl_attn_fwd_packed_f32 (csrc/attention_f32.hip): the scoring path's attention on packed rows — qkv f32 [Mq, 3 H D] -> ctx f32 [Mq, H D],
+ * row0 / Mq as for scl_attn_fwd_packed (Mv = row0[B] read on the device, every utterance clamped to 1..T frames inside the Mq rows), Mq a
+ * multiple of 64.  Streaming (nothing of size T^2 reaches memory), forward only: no lse, no dropout.  fp32 accuracy on the bf16 matrix
+ * cores: every operand (Q, K, V and the exponentials) is the pair hi = bf16(x), lo = bf16(x - hi) and every product hi hi + hi lo + lo hi
+ * with f32 accumulation — always the pair form, whatever SCL_GEMM_F32X3 the caller's GEMMs carry.  Deterministic; an utterance gets the
+ * bits it gets alone.  Nothing is loaded from or stored into a row at or beyond an utterance's end; rows [Mv, Mq) of ctx are written as
+ * 0; rows >= Mq are not touched.  Head dim 64 only; qkv and ctx 16-byte aligned. */
+int scl_attn_fwd_packed_f32(const float* qkv, float* ctx, const int32_t* row0, int B, int T, int H, int D, int Mq, float scale,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* feature-extractor layer 0 (Conv1d(1,C,10,5) + LayerNorm + GELU), fused fwd / bwd            */

@@ -47,6 +47,10 @@ VARLEN_PACK = os.environ.get("SCL_VARLEN_PACK", "0") == "1"
 # the bucket width trades rows wasted per step (< PACK_ROWS) against the number of plans (at most roundup(B * T, 64) / PACK_ROWS + 1 per
 # direction: 25 at 64 x 199 frames).  A multiple of 64: the weight-gradient reductions walk 64 rows per K step.
 PACK_ROWS = 512
+# The same layout for the fp32 scoring path (forward_f32 with packed=(row0, Mq)): its attention is then the streaming pair-form kernel of
+# csrc/attention_f32.hip — no T x T score buffers, no chunk loop, no padded rows in the layers.  Opt-in (SCL_SCORE_PACK=1), read at call
+# time; SCL_VARLEN_PACK does not reach the fp32 path.  64-wide heads only.
+SCORE_PACK = os.environ.get("SCL_SCORE_PACK", "0") == "1"
 
 
 VARLEN_SETS = 4      # buffer sets kept per path for variable-length scoring batches (every distinct padded shape is a set of its own)
@@ -661,12 +665,16 @@ class Encoder:
             fw["w3"][name] = w3
         return w3
 
-    def forward_f32(self, x, frames=None):
+    def forward_f32(self, x, frames=None, packed=None):
         """The encoder forward with fp32 activations and the fp32 master weights, every contraction on the exact-fp32 matrix-core
         kernel (csrc/gemm_f32.hip) — what main.py --eval / --predict / --emb score with: the reference runs fp32 end to end
         (main.py:161-214, no autocast) and north_star asks for scores within 1e-3 of it, which bf16 operands cannot give.
         Forward only, one layer's activations live at a time.  x [B, L] fp32 on the GPU -> enc_out f32 [B*T, E].
-        frames: as in forward() — int32 [B] on the GPU, valid frames per zero-padded utterance (any head dim)."""
+        frames: as in forward() — int32 [B] on the GPU, valid frames per zero-padded utterance (any head dim).
+        packed: (row0, Mq) with frames, as in forward() — the conv stack, zero_tail_rows(x0) and the positional convolution stay padded;
+        its f32 result is packed into the other ping-pong buffer, the layers and the final LayerNorm run over Mq rows with the streaming
+        fp32 attention of csrc/attention_f32.hip (no S / Pm buffers, no chunk loop above 512 frames), and the output is unpacked into
+        the padded [B*T, E] buffer with zero rows beyond each utterance.  64-wide heads only."""
         cfg, P = self.cfg, self.P
         B, L = x.shape
         C, E, H, Fd, K, G = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k, cfg.pos_groups
@@ -674,14 +682,34 @@ class Encoder:
         Ts = cfg.conv_lens(L)
         T = Ts[-1]
         M, Tp = B * T, (T + 7) // 8 * 8
-        # above 512 frames the attention runs in chunks of `bc` utterances (S / Pm sized per chunk, <= F32_ATTN_CHUNK_BYTES)
-        long_attn = T > MAT_ATTN_MAX_T
-        bc = max(1, min(B, F32_ATTN_CHUNK_BYTES // (4 * H * T * Tp))) if long_attn else B
-        key = ("f32", B, L) if not long_attn else ("f32", B, L, bc)
+        Mt, Mp = M, (M + 63) // 64 * 64      # rows of the transformer layers; the packed set's capacity
+        if packed is None:
+            # above 512 frames the attention runs in chunks of `bc` utterances (S / Pm sized per chunk, <= F32_ATTN_CHUNK_BYTES)
+            long_attn = T > MAT_ATTN_MAX_T
+            bc = max(1, min(B, F32_ATTN_CHUNK_BYTES // (4 * H * T * Tp))) if long_attn else B
+            key = ("f32", B, L) if not long_attn else ("f32", B, L, bc)
+        else:
+            if frames is None:
+                raise ValueError("encoder: packed=(row0, Mq) needs the frame counts of the batch (frames)")
+            if D != 64:
+                raise NotImplementedError("encoder: SCL_SCORE_PACK=1 needs 64-wide attention heads (this encoder's are %d wide): the "
+                                          "packed fp32 attention kernel takes head dim 64 only" % D)
+            row0, Mt = packed
+            if Mt % 64 or not B <= Mt <= Mp:
+                raise ValueError("encoder: packed row count %d: need a multiple of 64 in %d..%d" % (Mt, B, Mp))
+            key = ("f32", B, L, "packed")
+        nstat = max(B * Ts[1], Mp if packed is not None else 0)      # LayerNorm statistics: the widest row count of the path
 
         def make():
             f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.dev)
             slack = 128 * max(C, E)
+            if packed is not None:      # layer buffers of Mp rows (every packed row count of the shape), no score buffers
+                return dict(z=[f32(B * t * C + slack) for t in Ts], y=f32(B * Ts[1] * C), stat=f32(2 * nstat), h=f32(Mp * max(C, E) + slack),
+                            x0=f32(M * E), xpad=torch.zeros(B * (T + K) * E + slack, device=self.dev), xa=f32(Mp * E), xb=f32(Mp * E),
+                            x1=f32(Mp * E), qkv=f32(Mp * 3 * E + slack), ctx=f32(Mp * E + slack), a=f32(Mp * Fd + slack), out=f32(Mp * E),
+                            out_pad=f32(M * E),
+                            a3=torch.empty(Mp * 3 * max(C, E, Fd) + 2 * slack, dtype=torch.bfloat16, device=self.dev),
+                            a3b=torch.empty(Mp * 3 * Fd + 2 * slack, dtype=torch.bfloat16, device=self.dev))
             return dict(z=[f32(B * t * C + slack) for t in Ts], y=f32(B * Ts[1] * C), stat=f32(2 * B * Ts[1]), h=f32(M * max(C, E) + slack),
                                    x0=f32(M * E), xpad=torch.zeros(B * (T + K) * E + slack, device=self.dev), xa=f32(M * E), xb=f32(M * E),
                                    x1=f32(M * E), qkv=f32(M * 3 * E + slack), S=f32(bc * H * T * Tp), Pm=torch.zeros(bc * H * T * Tp + 1024, device=self.dev),
@@ -704,34 +732,37 @@ class Encoder:
         # fc1 -> fc2 without an f32 activation: needs the wide-tile kernel for fc1 (it alone writes the triple-plane image), i.e. K, N
         # multiples of 64 / 8 and enough tiles — asked of the library once per shape
         ffn3 = bool(use3 and E % 64 == 0 and Fd % 64 == 0 and
-                    ops.gemm_wide_kind(Op(d["a3"], 3 * E), Op(d["a3"], 3 * E), d["a3b"], M, Fd, 3 * E, ldc=3 * Fd))
+                    ops.gemm_wide_kind(Op(d["a3"], 3 * E), Op(d["a3"], 3 * E), d["a3b"], Mt, Fd, 3 * E, ldc=3 * Fd))
 
         LN3 = 0x100      # scl_layernorm_fwd: write [hi | hi | lo] rows straight into a3 (no f32 copy, no split pass)
 
-        def ln_then_lin(xsrc, lnw, lnb, Kin, wname, N, out, **epi):
-            """LayerNorm(xsrc) -> Linear: the LayerNorm kernel writes the triple-plane operand itself when that path is on."""
+        def ln_then_lin(xsrc, lnw, lnb, Kin, wname, N, out, rows=None, **epi):
+            """LayerNorm(xsrc) -> Linear: the LayerNorm kernel writes the triple-plane operand itself when that path is on.
+            rows: the row count (default: the transformer layers', Mt)."""
+            R_ = Mt if rows is None else rows
             if use3 and Kin % 64 == 0 and N % 8 == 0:
-                ops.layernorm_fwd(xsrc, self.b(lnw), self.b(lnb), d["a3"], None, mean, rstd, M, Kin, act=LN3)
-                ops.gemm(Op(d["a3"], 3 * Kin), Op(self._w3(fw, wname, N, Kin), 3 * Kin), out, M, N, 3 * Kin, **epi)
+                ops.layernorm_fwd(xsrc, self.b(lnw), self.b(lnb), d["a3"], None, mean, rstd, R_, Kin, act=LN3)
+                ops.gemm(Op(d["a3"], 3 * Kin), Op(self._w3(fw, wname, N, Kin), 3 * Kin), out, R_, N, 3 * Kin, **epi)
             else:
-                ops.layernorm_fwd(xsrc, self.b(lnw), self.b(lnb), None, d["h"], mean, rstd, M, Kin)
-                ops.gemm(Op(d["h"], Kin), Wf(wname, Kin), out, M, N, Kin, **epi)
+                ops.layernorm_fwd(xsrc, self.b(lnw), self.b(lnb), None, d["h"], mean, rstd, R_, Kin)
+                ops.gemm(Op(d["h"], Kin), Wf(wname, Kin), out, R_, N, Kin, **epi)
 
         def lin(A, Kin, wname, N, out, **epi):
             if use3 and Kin % 64 == 0 and N % 8 == 0:
-                ops.split3(A, M, Kin, d["a3"], 0)
-                ops.gemm(Op(d["a3"], 3 * Kin), Op(self._w3(fw, wname, N, Kin), 3 * Kin), out, M, N, 3 * Kin, **epi)
+                ops.split3(A, Mt, Kin, d["a3"], 0)
+                ops.gemm(Op(d["a3"], 3 * Kin), Op(self._w3(fw, wname, N, Kin), 3 * Kin), out, Mt, N, 3 * Kin, **epi)
             else:
-                ops.gemm(Op(A, Kin), Wf(wname, Kin), out, M, N, Kin, **epi)
+                ops.gemm(Op(A, Kin), Wf(wname, Kin), out, Mt, N, Kin, **epi)
         fe = "feature_extractor.conv_layers.%d."
-        mean, rstd = d["stat"][: B * Ts[1]], d["stat"][B * Ts[1]:]
+        mean, rstd = d["stat"][:nstat], d["stat"][nstat:]
         ops.conv0_fwd_f32(x, self.b(fe % 0 + "0.weight"), self.b(fe % 0 + "0.bias"), self.b(fe % 0 + "2.1.weight"), self.b(fe % 0 + "2.1.bias"),
                           d["z"][0], B, L, C, cfg.conv_kernels[0], cfg.conv_strides[0])
         for i in range(1, len(Ts)):
             k, s, Tin, Tout = cfg.conv_kernels[i], cfg.conv_strides[i], Ts[i - 1], Ts[i]
             ops.gemm(Op(d["z"][i - 1], s * C, rpb=Tout, rbstride=Tin * C), Op(fw["wk"][i], k * C), d["y"], B * Tout, C, k * C, bias=self.b(fe % i + "0.bias"))
             ops.layernorm_fwd(d["y"], self.b(fe % i + "2.1.weight"), self.b(fe % i + "2.1.bias"), None, d["z"][i], mean, rstd, B * Tout, C, act=1)
-        ln_then_lin(d["z"][-1], "layer_norm.weight", "layer_norm.bias", C, "post_extract_proj.weight", E, d["x0"], bias=self.b("post_extract_proj.bias"))
+        ln_then_lin(d["z"][-1], "layer_norm.weight", "layer_norm.bias", C, "post_extract_proj.weight", E, d["x0"], rows=M,
+                    bias=self.b("post_extract_proj.bias"))
         # positional conv: zero-padded rows (the pad rows of xpad are never written), GELU, residual
         if frames is not None:
             ops.zero_tail_rows(d["x0"], frames, B, T, E)      # fairseq: features[padding_mask] = 0
@@ -739,36 +770,47 @@ class Encoder:
         xin, xout = d["xa"], d["xb"]
         ops.gemm(Op(d["xpad"], E, rpb=T, rbstride=(T + K) * E, cin=Cg, cout=E, bs2=Cg), Op(fw["pos"], K * Cg, bs2=Cg * K * Cg), xin, M, Cg, K * Cg,
                  nb2=G, ldc=E, c_bs2=Cg, bias=self.b("encoder.pos_conv.0.bias"), bias_bs2=Cg, act=ACT_GELU, R=d["x0"], rmode=1)
-        qkv, S, Pm = d["qkv"], d["S"], d["Pm"]
-        # fp32 soft-max, as fairseq: one wave per row with the row in registers up to 512 frames, the looped kernel for longer rows
-        softmax = ops.softmax_fwd_f32_long if long_attn else ops.softmax_fwd_f32
+        if packed is not None:      # valid frames back to back into the other ping-pong buffer, rows [row0[B], Mt) zero
+            ops.pack_rows(xin, xout, row0, B, T, E, Mt)
+            xin, xout = xout, xin
+        qkv = d["qkv"]
+        if packed is None:
+            S, Pm = d["S"], d["Pm"]
+            # fp32 soft-max, as fairseq: one wave per row with the row in registers up to 512 frames, the looped kernel for longer rows
+            softmax = ops.softmax_fwd_f32_long if long_attn else ops.softmax_fwd_f32
         for n in range(cfg.layers):
             pn = "encoder.layers.%d." % n
             ln_then_lin(xin, pn + "self_attn_layer_norm.weight", pn + "self_attn_layer_norm.bias", E, pn + "self_attn.q_proj.weight", 3 * E, qkv,
                         bias=self.b(pn + "self_attn.q_proj.bias"))
-            for c0 in range(0, B, bc):      # scores, soft-max, P V per chunk of utterances (up to 512 frames: one chunk of all B)
-                nb, o3 = min(bc, B - c0), c0 * T * 3 * E
-                ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + E), S, T, T, D, nb1=nb, nb2=H,
-                         alpha=D ** -0.5, ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
-                if frames is not None:      # keys beyond the utterance's frames take no part (any T: one entry point)
-                    ops.softmax_fwd_f32_varlen(S, Pm, frames, nb * H * T, H * T, T, Tp, Tp, klen_offset=c0)
-                else:
-                    softmax(S, Pm, nb * H * T, T, Tp, Tp)
-                ops.gemm(Op(Pm, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + 2 * E), d["ctx"], T, D, T, b_t=True,
-                         nb1=nb, nb2=H, ldc=E, c_bs1=T * E, c_bs2=D, c_offset=c0 * T * E)
+            if packed is not None:      # streaming fp32 attention over the packed rows: one launch, nothing of size T^2
+                ops.attn_fwd_packed_f32(qkv, d["ctx"], row0, B, T, H, D, Mt, D ** -0.5)
+            else:
+                for c0 in range(0, B, bc):      # scores, soft-max, P V per chunk of utterances (up to 512 frames: one chunk of all B)
+                    nb, o3 = min(bc, B - c0), c0 * T * 3 * E
+                    ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + E), S, T, T, D, nb1=nb, nb2=H,
+                             alpha=D ** -0.5, ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
+                    if frames is not None:      # keys beyond the utterance's frames take no part (any T: one entry point)
+                        ops.softmax_fwd_f32_varlen(S, Pm, frames, nb * H * T, H * T, T, Tp, Tp, klen_offset=c0)
+                    else:
+                        softmax(S, Pm, nb * H * T, T, Tp, Tp)
+                    ops.gemm(Op(Pm, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + 2 * E), d["ctx"], T, D, T, b_t=True,
+                             nb1=nb, nb2=H, ldc=E, c_bs1=T * E, c_bs2=D, c_offset=c0 * T * E)
             lin(d["ctx"], E, pn + "self_attn.out_proj.weight", E, d["x1"], bias=self.b(pn + "self_attn.out_proj.bias"), R=xin, rmode=1)
             if use3 and ffn3:
                 # fc1 writes gelu(.) as the triple-plane image itself (SCL_GEMM_C_SPLIT3: no f32 activation, no split pass) and fc2 reads it
                 ln_then_lin(d["x1"], pn + "final_layer_norm.weight", pn + "final_layer_norm.bias", E, pn + "fc1.weight", Fd, d["a3b"],
                             bias=self.b(pn + "fc1.bias"), act=ACT_GELU, ldc=3 * Fd, split3=True)
-                ops.gemm(Op(d["a3b"], 3 * Fd), Op(self._w3(fw, pn + "fc2.weight", E, Fd), 3 * Fd), xout, M, E, 3 * Fd, bias=self.b(pn + "fc2.bias"),
+                ops.gemm(Op(d["a3b"], 3 * Fd), Op(self._w3(fw, pn + "fc2.weight", E, Fd), 3 * Fd), xout, Mt, E, 3 * Fd, bias=self.b(pn + "fc2.bias"),
                          R=d["x1"], rmode=1)
             else:
                 ln_then_lin(d["x1"], pn + "final_layer_norm.weight", pn + "final_layer_norm.bias", E, pn + "fc1.weight", Fd, d["a"],
                             bias=self.b(pn + "fc1.bias"), act=ACT_GELU)
                 lin(d["a"], Fd, pn + "fc2.weight", E, xout, bias=self.b(pn + "fc2.bias"), R=d["x1"], rmode=1)
             xin, xout = xout, xin
-        ops.layernorm_fwd(xin, self.b("encoder.layer_norm.weight"), self.b("encoder.layer_norm.bias"), None, d["out"], mean, rstd, M, E)
+        ops.layernorm_fwd(xin, self.b("encoder.layer_norm.weight"), self.b("encoder.layer_norm.bias"), None, d["out"], mean, rstd, Mt, E)
+        if packed is not None:      # back to the padded [B*T, E] rectangle, zero rows beyond each utterance
+            ops.unpack_rows(d["out"], d["out_pad"], row0, B, T, E, Mt)
+            return d["out_pad"], T
         return d["out"], T
 
     # ---- backward --------------------------------------------------------------------------------

@@ -199,6 +199,8 @@ def _protos():
         "scl_attn_bwd_packed": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _u32, _vp], _i32),
         "scl_pack_rows": ([_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
         "scl_unpack_rows": ([_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
+        # attention_f32.hip
+        "scl_attn_fwd_packed_f32": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp], _i32),
         # conv0.hip
         "scl_conv0_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp], _i32),
         "scl_conv0_fwd_f32": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp], _i32),

@@ -396,12 +396,14 @@ class Model(nn.Module):
             enc_slots = self.encoder.backward(sv["ectx"], hb["denc"])
         return dict(drop_descs=drop_descs, meanpool_entry=mp_entry, meanpool_seed_pos=mp_pos, enc_slots=enc_slots)
 
-    def _score_fp32(self, x, frames=None):
+    def _score_fp32(self, x, frames=None, rows=None):
         """Scoring forward (no grad, eval mode): fp32 activations, fp32 master weights, exact-fp32 GEMMs end to end — the
-        reference's precision (main.py:161-214), for scores / embeddings within 1e-3 of it."""
+        reference's precision (main.py:161-214), for scores / embeddings within 1e-3 of it.
+        rows: (row0, Mq) of _packed_rows — the encoder's transformer layers run on the packed valid frames (encoder.SCORE_PACK); the
+        encoder hands back the padded rectangle, so the head below is the same either way."""
         P, E = self.P, self.cfg.embed
         B = x.shape[0]
-        enc, T = self.encoder.forward_f32(x, frames)
+        enc, T = self.encoder.forward_f32(x, frames, packed=rows)
         M = B * T
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
         Wf = lambda name, ld: Op(P.flat, ld, offset=P.off(name))
@@ -432,13 +434,15 @@ class Model(nn.Module):
                                           "mode on model.train() with autograd on; eval with autograd, or train under no_grad, is neither")
             counts = self._frame_counts(lengths, x.shape[0], x.shape[1])
             frames = self._upload_i32(counts)
-            # the packed layout (encoder.VARLEN_PACK) serves the bf16 encoder path; the fp32 scoring path's attention is strided per utterance
-            if ENC.VARLEN_PACK and (self.training or not SCORE_FP32):
+            # the packed layout: encoder.VARLEN_PACK serves the bf16 encoder path, encoder.SCORE_PACK the fp32 scoring path (whose
+            # materialised-score attention is strided per utterance: packed, it runs the streaming kernel of csrc/attention_f32.hip)
+            score_f32 = not self.training and SCORE_FP32
+            if ENC.SCORE_PACK if score_f32 else ENC.VARLEN_PACK:
                 rows = self._packed_rows(counts, x.shape[1])
         if torch.is_grad_enabled() and any(p.requires_grad for p in (self._anchor,)):
             out, feats, emb = _ModelFn.apply(self, x, self._anchor, frames, rows)
         elif not self.training and SCORE_FP32:
-            out, feats, emb = self._score_fp32(x, frames)
+            out, feats, emb = self._score_fp32(x, frames, rows)
         else:
             out, feats, emb, _ = self._run_forward(x, frames, rows=rows)
             out, feats, emb = out.clone(), feats.clone(), emb.clone()

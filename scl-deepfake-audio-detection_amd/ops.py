@@ -607,6 +607,14 @@ def attn_bwd_packed(qkv, ctx, dctx, lse, row0, dqkv, ws, B, T, H, D, Mq, scale, 
                  float(scale), float(drop_p), int(drop_seed), _stream())
 
 
+def attn_fwd_packed_f32(qkv, ctx, row0, B, T, H, D, Mq, scale):
+    """The fp32 scoring path's attention on packed rows (csrc/attention_f32.hip): qkv f32 [Mq, 3, H, 64] -> ctx f32 [Mq, H * 64], streaming,
+    bf16-pair products (always: F32X3 does not reach it); nothing is stored past an utterance's end, ctx rows [row0[B], Mq) are written as 0."""
+    assert qkv.dtype == torch.float32 and ctx.dtype == torch.float32 and row0.numel() >= B + 1
+    assert qkv.numel() >= Mq * 3 * H * D and ctx.numel() >= Mq * H * D
+    return _call("scl_attn_fwd_packed_f32", _p(qkv), _p(ctx), _p(_klen(row0)), B, T, H, D, int(Mq), float(scale), _stream())
+
+
 def pack_rows(src, dst, row0, B, T, C, Mq):
     """dst[row0[b] + t] = src[b*T + t] for t < frames[b]; dst rows [row0[B], Mq) = 0.  f32 or bf16 rows of C elements (C % 8 == 0)."""
     assert src.dtype == dst.dtype and row0.numel() >= B + 1 and src.numel() >= B * T * C and dst.numel() >= Mq * C
