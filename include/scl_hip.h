@@ -374,7 +374,8 @@ int scl_attn_fwd(const void* qkv, void* ctx, float* lse, int B, int T, int H, in
 int scl_attn_fwd_fp8(const void* qkv, void* ctx, float* lse, int B, int T, int H, int D, float scale, void* stream);
 int scl_attn_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, float* bias_part, int B, int T,
                  int H, int D, float scale, float drop_p, uint32_t drop_seed, void* stream);
-/* Streaming attention for head dim 64 and any T >= 1 (csrc/attention_long.hip): K / V blocks of 64 keys through LDS, online fp32
+/* Streaming attention for head dim 64 and any T >= 1 (csrc/attention_long.hip; kernel bodies in csrc/attn_stream_body.h, shared with the
+ * _varlen and _packed entry points below): K / V blocks of 64 keys through LDS, online fp32
  * soft-max; no T x T buffer.  Same operands, layouts, dropout mask index and outputs as scl_attn_fwd / scl_attn_bwd (row r = (b, h, q) of
  * lse and of the mask).  The encoder's path above 512 frames (and 225-512 with SCL_ATTN_LONG=1).
  * bwd: P recomputed from lse, delta = rowsum(dO o O) into ws (scl_attn_long_ws_bytes(B, T, H) bytes); dK / dV per block of 128 keys,

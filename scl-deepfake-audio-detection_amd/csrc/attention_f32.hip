@@ -2,10 +2,10 @@
 // with packed=(row0, Mq)) without a T x T score buffer and without the padded rows.
 //
 //   scl_attn_fwd_packed_f32   qkv f32 [Mq, 3, H, 64] -> ctx f32 [Mq, H*64]; utterance b owns rows row0[b] .. row0[b + 1] - 1 (row0 int32
-//                             [B + 1] on the device, the layout of attention_packed.hip: Tb and the first row are clamped as UttRows<true>
+//                             [B + 1] on the device, the layout of attention_packed.hip: Tb and the first row are clamped as UttRows<Rows::Packed>
 //                             does, Mv = row0[B] is read on the device).  Forward only: no lse, no dropout.
 //
-// THE TILE SCHEME is attn_fwd_varlen_body's (attn_varlen_body.h): one workgroup per (utterance, head, 64 queries), four waves of 16
+// THE TILE SCHEME is attn_stream_fwd_body's (attn_stream_body.h): one workgroup per (utterance, head, 64 queries), four waves of 16
 // queries; keys stream through LDS in blocks of 64, double-buffered, the next block's global loads in flight under the current block's
 // products; S^T = K Q^T so that a lane holds one query's scores, online soft-max in fp32 with the rescale on every block; every output
 // element is summed by one wave in a fixed order (no atomics: the same bits on every run, and the bits an utterance gets alone).
@@ -21,7 +21,7 @@
 //
 // THE STORES are those of the bf16 packed forward: no row at or beyond an utterance's end is loaded or stored, a query block that starts
 // beyond Tb leaves before its first barrier, rows [Mv, Mq) of ctx are written as zeros by every launch, rows >= Mq are never touched.
-#include "attn_varlen_body.h"
+#include "attn_stream_body.h"
 
 namespace {
 
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_packed_f32_kernel(const float
     const int64_t pitch = 3 * (int64_t)E;
     const int bh = blockIdx.x / nqb, qblk = blockIdx.x % nqb;
     const int b = bh / H, h = bh % H;
-    const UttRows<true> utt(row0, b, T, Mq);
+    const UttRows<Rows::Packed> utt(row0, b, T, Mq);
     const int Tb = utt.Tb;      // one value per workgroup: everything that depends on it is workgroup-uniform
     const float* base = qkv + utt.r0 * pitch + h * LD;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -1,161 +1,27 @@
-// attention_long.hip — streaming ("flash") attention for head dim 64 and any clip length (T >= 1), forward and backward, plus the
-// looped fp32 row soft-max of the fp32 scoring path.  The encoder routes here above the 512 frames the materialised-score path
+// attention_long.hip — the fixed-length layout of the streaming attention (every utterance has T frames, T >= 1): forward, backward, and
+// the looped fp32 row soft-max of the fp32 scoring path.  The encoder routes here above the 512 frames the materialised-score path
 // (attention.hip: a whole score row in registers) accepts; nothing of size T^2 is written to memory.
 //
-// Operands and outputs as scl_attn_fwd / scl_attn_bwd: qkv / dqkv bf16 [B, T, 3, H, 64]; ctx / dctx bf16 [B, T, H*64]; lse f32 [B, H, T]
-// = log sum_k exp(scale * q.k).  Attention dropout draws keep-mask hash(seed, ((b*H + h)*T + q)*T + k), the index of the fused kernels
-// and of scl_dropout_rows.  Every global offset is 64-bit.
-//
-// Forward, one workgroup per (utterance, head, block of 64 queries), 4 waves of 16 queries.  Blocks of 64 keys stream through LDS
-// (double-buffered, the next block's loads are issued before the current block is multiplied and written to LDS after it: one barrier
-// per block).  Per block and wave:
-//   S^T[key][q] = K Q^T       MFMA(A = K rows from LDS, B = the wave's Q rows held in registers)  -> lane owns ONE query (lc) and keys
-//                             16t + 4g + r of each 16-key tile t: the row maximum is an in-lane max plus two cross-lane steps
-//   online soft-max in fp32:  m' = max(m, rowmax), O *= 2^((m - m') scale log2 e), l = l * the same + rowsum(2^((S - m') scale log2 e))
-//   O^T[d][q]  += V^T P^T     the exponentials, packed to bf16, ARE the B operand (the transposed LDS read of V supplies the permuted k)
-// The rescale is applied on every block (no deferred rescale): the probabilities fed to the MFMA are <= 1 as in the fused kernel.
-//
-// Backward (P recomputed from lse, delta = rowsum(dO o O) by a small first kernel into the workspace):
-//   dK / dV: one workgroup per (utterance, head, block of 128 keys); wave w owns keys 32w..32w+31 (their K / V fragments in registers,
-//            dK^T / dV^T in accumulators) while the workgroup sweeps the queries 32 at a time (Q and dO tiles in LDS, row and
-//            transposed images, double-buffered): S = Q K^T, dP = dO V^T, P = exp(scale S - lse), dS = P (dP mask - delta),
-//            dV^T += dO^T (P mask), dK^T += Q^T dS.
-//   dQ:      one workgroup per (utterance, head, block of 64 queries), as the forward: S^T = K Q^T, dP^T = V dO^T, dS^T as above,
-//            dQ^T += K^T dS^T with K's transposed image.
-// Each output element is summed by one wave in a fixed order: no atomics, bitwise reproducible.
-#include "attn_tiles.h"      // lk_off / lt_off tile images, l_frag_* / l_pack8 / l_load_rows operands, kv_fetch / kv_store / qt_fetch / qt_store staging
+// The forward, delta and dQ kernels are the bodies of attn_stream_body.h (the tile scheme, the operand layouts and the dropout mask index are
+// described there) with Rows::Fixed: utterance b at rows b*T, Tb = T, no length array.  attention_varlen.hip and attention_packed.hip hold
+// the same bodies for a zero-padded and a packed variable-length batch.  The dK / dV kernel has a body of its own here.
+#include "attn_stream_body.h"
 
 namespace {
 
-constexpr int LD = 64;        // head dim
-constexpr int LKB = 64;       // keys per streamed block (forward, dQ)
-constexpr int LQB = 64;       // queries per workgroup (forward, dQ)
-constexpr int LKW = 128;      // keys per workgroup (dK / dV)
-
-// =====================================================================================================================================
-// Forward
-// =====================================================================================================================================
 template <bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, float* __restrict__ lse,
                                                             int T, int H, int nqb, float scale, float drop_p, uint32_t drop_seed) {
-    __shared__ __attribute__((aligned(16))) char smem[2][2][LKB * 128];      // [buffer][K rows, V tr][64 keys x 128 B]
-    const int E = H * LD;
-    const int64_t pitch = 3 * (int64_t)E;
-    const int bh = blockIdx.x / nqb, qblk = blockIdx.x % nqb;
-    const int b = bh / H, h = bh % H;
-    const bf16_t* base = qkv + (int64_t)b * T * pitch + h * LD;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lc = lane & 15, g = lane >> 4;
-    const int q = qblk * LQB + 16 * wave + lc;
-    const int nkb = (T + LKB - 1) / LKB;
-    bf16x8 qf[2];
-    l_load_rows(base, pitch, q, T, g, qf);
-    KVRegs r;
-    kv_fetch(r, base, pitch, E, 0, T);
-    kv_store(r, smem[0][0], nullptr, nullptr, smem[0][1]);
-    __syncthreads();
-    const float sl2 = scale * LOG2E;
-    const uint64_t rowbase = (((uint64_t)b * H + h) * T + (uint64_t)(q < T ? q : 0)) * (uint64_t)T;
-    float m = -INFINITY, l = 0.f;      // running max (raw score units) and this lane's share of the running sum
-    f32x4 o[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int kb = 0; kb < nkb; ++kb) {
-        const int p = kb & 1;
-        if (kb + 1 < nkb) kv_fetch(r, base, pitch, E, (kb + 1) * LKB, T);      // in flight under this block's products
-        const char* Kr = smem[p][0];
-        const char* Vt = smem[p][1];
-        const int key0 = kb * LKB;
-        f32x4 s[4];
-        float mb = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l_frag_rows(Kr, t, ks, lane), qf[ks], s[t], 0, 0, 0);
-            if (key0 + LKB > T) {      // the last block only
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr)
-                    if (key0 + 16 * t + 4 * g + rr >= T) s[t][rr] = -INFINITY;
-            }
-            mb = fmaxf(mb, fmaxf(fmaxf(s[t][0], s[t][1]), fmaxf(s[t][2], s[t][3])));
-        }
-        mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
-        mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
-        const float mn = fmaxf(m, mb);      // finite: every block holds at least one key < T
-        const float alpha = __builtin_amdgcn_exp2f((m - mn) * sl2);      // 0 on the first block (m = -inf)
-        m = mn;
-        const float msl = -mn * sl2;
-        float ls = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) { s[t][rr] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t][rr], sl2, msl)); ls += s[t][rr]; }
-        l = l * alpha + ls;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
-        if (DROP) {      // the sum above is of the undropped probabilities; P x mask feeds P V
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) {
-                    const int key = key0 + 16 * t + 4 * g + rr;
-                    s[t][rr] *= dropout_scale(drop_seed, rowbase + (uint64_t)(key < T ? key : 0), drop_p);
-                }
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const bf16x8 pf = l_pack8(s[2 * u], s[2 * u + 1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l_frag_tr(Vt, 32 * u, 32 * u + 16, dt, lane), pf, o[dt], 0, 0, 0);
-        }
-        if (kb + 1 < nkb) kv_store(r, smem[p ^ 1][0], nullptr, nullptr, smem[p ^ 1][1]);      // its last readers finished before the previous barrier
-        __syncthreads();
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / l;
-    if (q < T) {
-        if (g == 0) lse[((int64_t)b * H + h) * T + q] = scale * m + __logf(l);
-        bf16_t* dst = ctx + ((int64_t)b * T + q) * E + h * LD + 4 * g;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-            *reinterpret_cast<uint2*>(dst + 16 * dt) = make_uint2(pack_bf2(o[dt][0] * inv, o[dt][1] * inv), pack_bf2(o[dt][2] * inv, o[dt][3] * inv));
-    }
+    attn_stream_fwd_body<DROP, Rows::Fixed>(qkv, ctx, lse, nullptr, T, H, nqb, 0, 0, scale, drop_p, drop_seed);
 }
 
-// =====================================================================================================================================
-// Backward
-// =====================================================================================================================================
-// delta[(b*H + h)*T + q] = <dO, O> of the row (8 lanes per row, one 16-byte piece each, fixed-order sum)
 __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restrict__ ctx, const bf16_t* __restrict__ dctx, float* __restrict__ delta,
                                                          int64_t rows, int T, int H) {
-    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t row = gid >> 3;      // (b, q, h) in memory order
-    const int c = (int)(gid & 7);
-    float dot = 0.f;
-    if (row < rows) {
-        const uint4 vo = *reinterpret_cast<const uint4*>(dctx + row * LD + 8 * c);
-        const uint4 vc = *reinterpret_cast<const uint4*>(ctx + row * LD + 8 * c);
-        const unsigned ow[4] = {vo.x, vo.y, vo.z, vo.w}, cw[4] = {vc.x, vc.y, vc.z, vc.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            dot += __uint_as_float(ow[k] << 16) * __uint_as_float(cw[k] << 16);
-            dot += __uint_as_float(ow[k] & 0xFFFF0000u) * __uint_as_float(cw[k] & 0xFFFF0000u);
-        }
-    }
-    dot = lanes8_sum(dot);
-    if (row < rows && c == 0) {
-        const int64_t bq = row / H;
-        const int h = (int)(row % H);
-        const int64_t b = bq / T, q = bq % T;
-        delta[(b * H + h) * T + q] = dot;
-    }
+    attn_stream_delta_body<Rows::Fixed>(ctx, dctx, delta, nullptr, rows, T, H, 0);
 }
 
-// ---- dK / dV ------------------------------------------------------------------------------------------------------------------------
-// Query tiles of 32 rows per step: QRegs / qt_fetch / qt_store of attn_tiles.h (Q rows, Q tr, dO rows, dO tr images, lse x log2 e, delta)
+// dK / dV: attn_stream_dkdv_body's scheme with Tb = T and no early exit, written out because the shared body compiles to a slower
+// schedule for this layout (profiles/attn_stream_unify.txt).  A change to the tile scheme has to be made in both.
 template <bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dkdv_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
                                                                  const float* __restrict__ lse, const float* __restrict__ delta,
@@ -266,99 +132,20 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_long_kernel(const bf16_t* _
     }
 }
 
-// ---- dQ -------------------------------------------------------------------------------------------------------------------------------
 template <bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dq_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                bf16_t* __restrict__ dqkv, int T, int H, int nqb, float scale,
                                                                float drop_p, uint32_t drop_seed) {
-    __shared__ __attribute__((aligned(16))) char smem[2][3][LKB * 128];      // [buffer][K rows, K tr, V rows]
-    const int E = H * LD;
-    const int64_t pitch = 3 * (int64_t)E;
-    const int bh = blockIdx.x / nqb, qblk = blockIdx.x % nqb;
-    const int b = bh / H, h = bh % H;
-    const bf16_t* base = qkv + (int64_t)b * T * pitch + h * LD;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lc = lane & 15, g = lane >> 4;
-    const int q0 = qblk * LQB + 16 * wave, q = q0 + lc;
-    const int nkb = (T + LKB - 1) / LKB;
-    bf16x8 qf[2], of[2];
-    l_load_rows(base, pitch, q, T, g, qf);
-    l_load_rows(dctx + (int64_t)b * T * E + h * LD, E, q, T, g, of);
-    const int64_t rbh = ((int64_t)b * H + h) * T;
-    const float lq = q < T ? lse[rbh + q] * LOG2E : 1e30f;
-    const float dl = q < T ? delta[rbh + q] : 0.f;
-    KVRegs r;
-    kv_fetch(r, base, pitch, E, 0, T);
-    kv_store(r, smem[0][0], smem[0][1], smem[0][2], nullptr);
-    __syncthreads();
-    const float sc2 = scale * LOG2E;
-    const uint64_t rowbase = ((uint64_t)rbh + (uint64_t)(q < T ? q : 0)) * (uint64_t)T;
-    f32x4 dq[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int kb = 0; kb < nkb; ++kb) {
-        const int p = kb & 1;
-        if (kb + 1 < nkb) kv_fetch(r, base, pitch, E, (kb + 1) * LKB, T);
-        const char* Kr = smem[p][0];
-        const char* Kt = smem[p][1];
-        const char* Vr = smem[p][2];
-        const int key0 = kb * LKB;
-        f32x4 ds[4];      // dS^T[key = 16t + 4g + r][q = lc]
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f32x4 sv = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                sv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l_frag_rows(Kr, t, ks, lane), qf[ks], sv, 0, 0, 0);
-                dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l_frag_rows(Vr, t, ks, lane), of[ks], dp, 0, 0, 0);
-            }
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int key = key0 + 16 * t + 4 * g + rr;
-                const float pv = key >= T ? 0.f : __builtin_amdgcn_exp2f(__builtin_fmaf(sv[rr], sc2, -lq));
-                const float mk = DROP ? dropout_scale(drop_seed, rowbase + (uint64_t)(key < T ? key : 0), drop_p) : 1.f;
-                ds[t][rr] = pv * (dp[rr] * mk - dl);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const bf16x8 sf = l_pack8(ds[2 * u], ds[2 * u + 1]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-                dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l_frag_tr(Kt, 32 * u, 32 * u + 16, dt, lane), sf, dq[dt], 0, 0, 0);
-        }
-        if (kb + 1 < nkb) kv_store(r, smem[p ^ 1][0], smem[p ^ 1][1], smem[p ^ 1][2], nullptr);
-        __syncthreads();
-    }
-    if (q < T) {
-        bf16_t* dst = dqkv + ((int64_t)b * T + q) * pitch + h * LD + 4 * g;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-            *reinterpret_cast<uint2*>(dst + 16 * dt) = make_uint2(pack_bf2(dq[dt][0] * scale, dq[dt][1] * scale), pack_bf2(dq[dt][2] * scale, dq[dt][3] * scale));
-    }
+    attn_stream_dq_body<DROP, Rows::Fixed>(qkv, dctx, lse, delta, dqkv, nullptr, T, H, nqb, 0, 0, scale, drop_p, drop_seed);
 }
 
-// =====================================================================================================================================
-// fp32 row soft-max of any length: one wave per row, a looped online (max, sum) pass then a write pass
-// =====================================================================================================================================
+// fp32 row soft-max of any length: one wave per row
 __global__ __launch_bounds__(256) void softmax_fwd_f32_long_kernel(const float* __restrict__ S, float* __restrict__ P, int64_t R, int T,
                                                                    int ldS, int Tp) {
-    const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= R) return;
-    const float* s = S + row * ldS;
-    float m = -INFINITY, l = 0.f;
-    for (int c = lane; c < T; c += 64) {
-        const float v = s[c];
-        if (v > m) { l = l * __expf(m - v) + 1.f; m = v; }
-        else if (m != -INFINITY) l += __expf(v - m);      // v = m = -inf adds nothing
-    }
-    const float mx = wave_max(m);
-    const float sum = wave_sum(m == -INFINITY ? 0.f : l * __expf(m - mx));
-    const float inv = 1.0f / sum;
-    float* p = P + row * Tp;
-    for (int c = lane; c < Tp; c += 64) p[c] = c < T ? __expf(s[c] - mx) * inv : 0.f;
+    softmax_f32_looped_row(S + row * ldS, P + row * Tp, T, Tp, threadIdx.x & 63);
 }
 
 }  // namespace

@@ -7,8 +7,8 @@
 //   Mq           the launch's row count (Mv <= Mq): rows [Mv, Mq) belong to no utterance.  Mv is READ FROM row0[B] on the device, so a
 //                recorded launch stays valid when the lengths change within the same Mq.
 //
-//   scl_attn_fwd_packed / _drop   the streaming forward of attention_varlen.hip (the same body, attn_varlen_body.h) with the utterance's
-//                                 rows addressed from row0[b] instead of b*T.  lse and the dropout mask index stay in the padded
+//   scl_attn_fwd_packed / _drop   the streaming forward of attn_stream_body.h with Rows::Packed: the body of attention_varlen.hip with the
+//                                 utterance's rows addressed from row0[b] instead of b*T.  lse and the dropout mask index stay in the padded
 //                                 (b, h, q, T) space: rows row0[b] + t of ctx carry the bits scl_attn_fwd_varlen(_drop) gives at b*T + t.
 //   scl_attn_bwd_packed           the deterministic streaming backward likewise (delta workspace in the padded space).
 //                                 THE STORES: where the padded kernels zero-fill rows >= klen[b], the packed rows behind an utterance
@@ -17,7 +17,7 @@
 //                                 forward, dqkv by the backward): the gradients of rows that belong to nobody are exactly 0.
 //   scl_pack_rows                 dst[row0[b] + t] = src[b*T + t] for t < Tb; dst rows [Mv, Mq) = 0 (padded source rows are not read).
 //   scl_unpack_rows               dst[b*T + t] = t < Tb ? src[row0[b] + t] : 0.  Either way every row of the destination is written.
-#include "attn_varlen_body.h"
+#include "attn_stream_body.h"
 
 namespace {
 
@@ -25,13 +25,13 @@ template <bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_packed_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, float* __restrict__ lse,
                                                               const int* __restrict__ row0, int T, int H, int nqb, int B, int Mq, float scale,
                                                               float drop_p, uint32_t drop_seed) {
-    attn_fwd_varlen_body<DROP, true>(qkv, ctx, lse, row0, T, H, nqb, B, Mq, scale, drop_p, drop_seed);
+    attn_stream_fwd_body<DROP, Rows::Packed>(qkv, ctx, lse, row0, T, H, nqb, B, Mq, scale, drop_p, drop_seed);
 }
 
 __global__ __launch_bounds__(256) void attn_delta_packed_kernel(const bf16_t* __restrict__ ctx, const bf16_t* __restrict__ dctx,
                                                                 float* __restrict__ delta, const int* __restrict__ row0, int64_t rows, int T, int H,
                                                                 int Mq) {
-    attn_delta_varlen_body<true>(ctx, dctx, delta, row0, rows, T, H, Mq);
+    attn_stream_delta_body<Rows::Packed>(ctx, dctx, delta, row0, rows, T, H, Mq);
 }
 
 template <bool DROP>
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_packed_kernel(const bf16_t*
                                                                    const float* __restrict__ lse, const float* __restrict__ delta,
                                                                    bf16_t* __restrict__ dqkv, const int* __restrict__ row0, int T, int H, int nkw,
                                                                    int Mq, float scale, float drop_p, uint32_t drop_seed) {
-    attn_bwd_dkdv_varlen_body<DROP, true>(qkv, dctx, lse, delta, dqkv, row0, T, H, nkw, Mq, scale, drop_p, drop_seed);
+    attn_stream_dkdv_body<DROP, Rows::Packed>(qkv, dctx, lse, delta, dqkv, row0, T, H, nkw, Mq, scale, drop_p, drop_seed);
 }
 
 template <bool DROP>
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_packed_kernel(const bf16_t* _
                                                                  const float* __restrict__ lse, const float* __restrict__ delta,
                                                                  bf16_t* __restrict__ dqkv, const int* __restrict__ row0, int T, int H, int nqb,
                                                                  int B, int Mq, float scale, float drop_p, uint32_t drop_seed) {
-    attn_bwd_dq_varlen_body<DROP, true>(qkv, dctx, lse, delta, dqkv, row0, T, H, nqb, B, Mq, scale, drop_p, drop_seed);
+    attn_stream_dq_body<DROP, Rows::Packed>(qkv, dctx, lse, delta, dqkv, row0, T, H, nqb, B, Mq, scale, drop_p, drop_seed);
 }
 
 // ---- pack / unpack: one thread per 16 bytes, rows of vec_per_row vectors; both walk the PADDED (b, t) space ---------------------------------
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const uint4* __restrict_
         const int b = (int)(i / per_utt);
         const int64_t in_utt = i - (int64_t)b * per_utt;
         const int t = (int)(in_utt / vec_per_row);
-        const UttRows<true> utt(row0, b, T, Mq);
+        const UttRows<Rows::Packed> utt(row0, b, T, Mq);
         if (t < utt.Tb) dst[utt.r0 * vec_per_row + in_utt] = src[i];
     }
     zero_tail_vectors(dst, row0, B, Mq, vec_per_row);
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(const uint4* __restric
         const int b = (int)(i / per_utt);
         const int64_t in_utt = i - (int64_t)b * per_utt;
         const int t = (int)(in_utt / vec_per_row);
-        const UttRows<true> utt(row0, b, T, Mq);
+        const UttRows<Rows::Packed> utt(row0, b, T, Mq);
         dst[i] = t < utt.Tb ? src[utt.r0 * vec_per_row + in_utt] : make_uint4(0u, 0u, 0u, 0u);
     }
 }

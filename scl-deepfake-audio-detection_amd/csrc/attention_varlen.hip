@@ -1,14 +1,14 @@
 // attention_varlen.hip — a zero-padded batch of utterances of different lengths: per-utterance frame counts klen[b] (int32 on the
 // device, 1 <= klen[b] <= T) play the part of fairseq's padding_mask, for scoring and for training.
 //
-//   scl_attn_fwd_varlen          the streaming forward of attention_long.hip with the key loop, the K / V staging and the last block's
+//   scl_attn_fwd_varlen          the streaming forward (attn_stream_body.h) with the key loop, the K / V staging and the last block's
 //                                mask running to klen[b] instead of T: keys >= klen[b] are never loaded, and a block of 64 queries that
 //                                starts at or beyond klen[b] writes zeros and leaves before the first barrier.  klen[b] is one value per
 //                                workgroup, so the trip count and the early exit are workgroup-uniform.  Per query the blocks are visited
 //                                in the order of scl_attn_fwd_long at T = klen[b]: rows < klen[b] carry the same bits.
 //   scl_attn_fwd_varlen_drop     the same with attention dropout: keep-mask hash(seed, ((b*H + h)*T + q)*T + k) with the PADDED T, the
 //                                index of the fixed-length kernels.
-//   scl_attn_bwd_varlen          the deterministic streaming backward of attention_long.hip (delta, dK / dV per 128 keys, dQ per 64
+//   scl_attn_bwd_varlen          the deterministic streaming backward of attn_stream_body.h (delta, dK / dV per 128 keys, dQ per 64
 //                                queries, no atomics) with query tiles and key blocks running to klen[b].  A dK / dV or dQ block that
 //                                starts at or beyond klen[b] writes zeros into its rows of dqkv and leaves before its first barrier;
 //                                rows >= klen[b] of the last partial block are stored as zeros: EVERY row of dqkv is written, rows
@@ -21,23 +21,23 @@
 //   scl_meanpool_bwd_varlen      scl_meanpool_bwd (activation derivative and head-dropout mask fused) scaled by 1 / len[b]; rows
 //                                t >= len[b] are written as 0.
 // The device-side counts are clamped to [1, T] for memory safety; scl_varlen_check_lengths validates the host copy before the upload.
-// The three attention kernels are the bodies of attn_varlen_body.h in the padded layout (PACKED = false); attention_packed.hip holds the
-// same bodies for frames packed back to back.
-#include "attn_varlen_body.h"
+// The attention kernels are the bodies of attn_stream_body.h in the padded layout (Rows::Padded); attention_long.hip holds the same bodies
+// for batches without a length array (Rows::Fixed) and attention_packed.hip for frames packed back to back (Rows::Packed).
+#include "attn_stream_body.h"
 
 namespace {
 
-// the padded layout's kernels: the shared bodies with PACKED = false (utterance b at rows b*T, every row of the outputs written)
+// the padded layout's kernels: the shared bodies with Rows::Padded (utterance b at rows b*T, every row of the outputs written)
 template <bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_varlen_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, float* __restrict__ lse,
                                                               const int* __restrict__ klen, int T, int H, int nqb, float scale,
                                                               float drop_p, uint32_t drop_seed) {
-    attn_fwd_varlen_body<DROP, false>(qkv, ctx, lse, klen, T, H, nqb, 0, 0, scale, drop_p, drop_seed);
+    attn_stream_fwd_body<DROP, Rows::Padded>(qkv, ctx, lse, klen, T, H, nqb, 0, 0, scale, drop_p, drop_seed);
 }
 
 __global__ __launch_bounds__(256) void attn_delta_varlen_kernel(const bf16_t* __restrict__ ctx, const bf16_t* __restrict__ dctx,
                                                                 float* __restrict__ delta, const int* __restrict__ klen, int64_t rows, int T, int H) {
-    attn_delta_varlen_body<false>(ctx, dctx, delta, klen, rows, T, H, 0);
+    attn_stream_delta_body<Rows::Padded>(ctx, dctx, delta, klen, rows, T, H, 0);
 }
 
 template <bool DROP>
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_varlen_kernel(const bf16_t*
                                                                    const float* __restrict__ lse, const float* __restrict__ delta,
                                                                    bf16_t* __restrict__ dqkv, const int* __restrict__ klen, int T, int H, int nkw,
                                                                    float scale, float drop_p, uint32_t drop_seed) {
-    attn_bwd_dkdv_varlen_body<DROP, false>(qkv, dctx, lse, delta, dqkv, klen, T, H, nkw, 0, scale, drop_p, drop_seed);
+    attn_stream_dkdv_body<DROP, Rows::Padded>(qkv, dctx, lse, delta, dqkv, klen, T, H, nkw, 0, scale, drop_p, drop_seed);
 }
 
 template <bool DROP>
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_varlen_kernel(const bf16_t* _
                                                                  const float* __restrict__ lse, const float* __restrict__ delta,
                                                                  bf16_t* __restrict__ dqkv, const int* __restrict__ klen, int T, int H, int nqb,
                                                                  float scale, float drop_p, uint32_t drop_seed) {
-    attn_bwd_dq_varlen_body<DROP, false>(qkv, dctx, lse, delta, dqkv, klen, T, H, nqb, 0, 0, scale, drop_p, drop_seed);
+    attn_stream_dq_body<DROP, Rows::Padded>(qkv, dctx, lse, delta, dqkv, klen, T, H, nqb, 0, 0, scale, drop_p, drop_seed);
 }
 
 // ---- fp32 row soft-max over the first klen columns ----------------------------------------------------------------------------------
@@ -91,17 +91,8 @@ __global__ __launch_bounds__(256) void softmax_fwd_f32_varlen_kernel(const float
             const int c = i * 64 + lane;
             if (c < Tp) p[c] = v[i] * inv;
         }
-    } else {      // attention_long.hip's softmax_fwd_f32_long_kernel: online (max, sum) pass, then the write pass
-        float m = -INFINITY, l = 0.f;
-        for (int c = lane; c < Tv; c += 64) {
-            const float v = s[c];
-            if (v > m) { l = l * __expf(m - v) + 1.f; m = v; }
-            else if (m != -INFINITY) l += __expf(v - m);      // v = m = -inf adds nothing
-        }
-        const float mx = wave_max(m);
-        const float sum = wave_sum(m == -INFINITY ? 0.f : l * __expf(m - mx));
-        const float inv = 1.0f / sum;
-        for (int c = lane; c < Tp; c += 64) p[c] = c < Tv ? __expf(s[c] - mx) * inv : 0.f;
+    } else {      // online (max, sum) pass, then the write pass
+        softmax_f32_looped_row(s, p, Tv, Tp, lane);
     }
 }
 

@@ -1,33 +1,65 @@
-// attn_varlen_body.h — the streaming attention kernels over per-utterance frame counts as device-function bodies, shared by the two
-// row layouts of a variable-length batch (everything is internal to the including file and force-inlined into its kernels):
-//   PACKED = false  attention_varlen.hip: the zero-padded rectangle.  Utterance b owns rows b*T .. b*T + T - 1 of qkv / ctx / dctx / dqkv,
-//                   `lens` is klen[B]; rows >= klen[b] of a partial block are stored as zeros and a block beyond klen[b] writes zeros.
-//   PACKED = true   attention_packed.hip: valid frames back to back.  Utterance b owns rows row0[b] .. row0[b+1] - 1, `lens` is row0[B+1]
-//                   and Mq the launch's row count.  The rows behind an utterance belong to the NEXT one (or to nobody), so nothing is
-//                   stored at or beyond Tb and a block that starts there leaves before its first barrier without a store; the rows
-//                   [row0[B], Mq) that belong to no utterance are written as zeros by every launch (zero_tail_vectors).
-// lse, delta and the attention-dropout mask index live in the padded (b, h, q, T) space in both layouts: the same batch draws the same
-// masks and carries the same bits either way.
+// attn_stream_body.h — streaming ("flash") attention for head dim 64 and any clip length (T >= 1), forward and backward, as device-function
+// bodies shared by the three row layouts of a batch (everything is internal to the including file and force-inlined into its kernels).
+// Nothing of size T^2 is written to memory.
+//
+// Operands and outputs as scl_attn_fwd / scl_attn_bwd: qkv / dqkv bf16 [rows, 3, H, 64]; ctx / dctx bf16 [rows, H*64]; lse f32 [B, H, T]
+// = log sum_k exp(scale * q.k).  Attention dropout draws keep-mask hash(seed, ((b*H + h)*T + q)*T + k), the index of the fused kernels
+// and of scl_dropout_rows.  Every global offset is 64-bit.
+//
+// THE ROW LAYOUTS (template parameter Rows; utterance b owns Tb rows from row r0, see UttRows):
+//   Rows::Fixed    attention_long.hip: every utterance has T frames.  r0 = b*T, Tb = T, `lens` is null and never read.  (Its dK / dV
+//                  kernel is the one body not taken from here: attention_long.hip.)
+//   Rows::Padded   attention_varlen.hip: the zero-padded rectangle.  Utterance b owns rows b*T .. b*T + T - 1 of qkv / ctx / dctx / dqkv,
+//                  `lens` is klen[B]; rows >= klen[b] of a partial block are stored as zeros and a block beyond klen[b] writes zeros.
+//   Rows::Packed   attention_packed.hip: valid frames back to back.  Utterance b owns rows row0[b] .. row0[b+1] - 1, `lens` is row0[B+1]
+//                  and Mq the launch's row count.  The rows behind an utterance belong to the NEXT one (or to nobody), so nothing is
+//                  stored at or beyond Tb and a block that starts there leaves before its first barrier without a store; the rows
+//                  [row0[B], Mq) that belong to no utterance are written as zeros by every launch (zero_tail_vectors).
+// lse, delta and the attention-dropout mask index live in the padded (b, h, q, T) space in every layout: the same batch draws the same
+// masks and carries the same bits in each.  Tb is one value per workgroup, so the trip counts and the early exits are
+// workgroup-uniform; per query the blocks are visited in the order of the fixed layout at T = Tb.
+//
+// THE TILE SCHEME.  Forward, one workgroup per (utterance, head, block of 64 queries), 4 waves of 16 queries.  Blocks of 64 keys stream
+// through LDS (double-buffered, the next block's loads are issued before the current block is multiplied and written to LDS after it: one
+// barrier per block).  Per block and wave:
+//   S^T[key][q] = K Q^T       MFMA(A = K rows from LDS, B = the wave's Q rows held in registers)  -> lane owns ONE query (lc) and keys
+//                             16t + 4g + r of each 16-key tile t: the row maximum is an in-lane max plus two cross-lane steps
+//   online soft-max in fp32:  m' = max(m, rowmax), O *= 2^((m - m') scale log2 e), l = l * the same + rowsum(2^((S - m') scale log2 e))
+//   O^T[d][q]  += V^T P^T     the exponentials, packed to bf16, ARE the B operand (the transposed LDS read of V supplies the permuted k)
+// The rescale is applied on every block (no deferred rescale): the probabilities fed to the MFMA are <= 1 as in the fused kernel.
+//
+// Backward (P recomputed from lse, delta = rowsum(dO o O) by a small first kernel into the workspace):
+//   dK / dV: one workgroup per (utterance, head, block of 128 keys); wave w owns keys 32w..32w+31 (their K / V fragments in registers,
+//            dK^T / dV^T in accumulators) while the workgroup sweeps the queries 32 at a time (Q and dO tiles in LDS, row and
+//            transposed images, double-buffered): S = Q K^T, dP = dO V^T, P = exp(scale S - lse), dS = P (dP mask - delta),
+//            dV^T += dO^T (P mask), dK^T += Q^T dS.
+//   dQ:      one workgroup per (utterance, head, block of 64 queries), as the forward: S^T = K Q^T, dP^T = V dO^T, dS^T as above,
+//            dQ^T += K^T dS^T with K's transposed image.
+// Each output element is summed by one wave in a fixed order: no atomics, bitwise reproducible.
+//
+// Also here: the looped fp32 row soft-max of the fp32 scoring path (softmax_f32_looped_row), one wave per row.
 #pragma once
-#include "attn_tiles.h"
+#include "attn_tiles.h"      // lk_off / lt_off tile images, l_frag_* / l_pack8 / l_load_rows operands, kv_fetch / kv_store / qt_fetch / qt_store staging
 
 namespace {
 
 constexpr int LD = 64;        // head dim
-constexpr int LKB = 64;       // keys per streamed block
-constexpr int LQB = 64;       // queries per workgroup
+constexpr int LKB = 64;       // keys per streamed block (forward, dQ)
+constexpr int LQB = 64;       // queries per workgroup (forward, dQ)
 constexpr int LKW = 128;      // keys per workgroup (dK / dV)
+
+enum class Rows { Fixed, Padded, Packed };
 
 __device__ __forceinline__ int clamp_len(int n, int T) { return n < 1 ? 1 : (n > T ? T : n); }
 
-// first row and frame count of utterance b; both clamped for memory safety (the host copy is validated before the upload):
-// 1 <= Tb <= T, and in the packed layout 0 <= r0 and r0 + Tb <= Mq
-template <bool PACKED>
+// first row and frame count of utterance b.  Fixed: b*T and T, `lens` is not read.  Padded / packed: both clamped for memory safety (the
+// host copy is validated before the upload): 1 <= Tb <= T, and in the packed layout 0 <= r0 and r0 + Tb <= Mq
+template <Rows L>
 struct UttRows {
     int64_t r0;
     int Tb;
     __device__ __forceinline__ UttRows(const int* __restrict__ lens, int b, int T, int Mq) {
-        if constexpr (PACKED) {
+        if constexpr (L == Rows::Packed) {
             const int a = lens[b];
             const int first = a < 0 ? 0 : (a > Mq - 1 ? Mq - 1 : a);
             const int n = clamp_len(lens[b + 1] - a, T);
@@ -35,7 +67,7 @@ struct UttRows {
             Tb = n > Mq - first ? Mq - first : n;
         } else {
             r0 = (int64_t)b * T;
-            Tb = clamp_len(lens[b], T);
+            Tb = L == Rows::Fixed ? T : clamp_len(lens[b], T);
         }
     }
 };
@@ -49,17 +81,20 @@ __device__ __forceinline__ void zero_tail_vectors(uint4* __restrict__ x, const i
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) tail[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-// attn_fwd_long_kernel with Tb keys (see attention_long.hip for the tile scheme)
-template <bool DROP, bool PACKED>
-__device__ __forceinline__ void attn_fwd_varlen_body(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, float* __restrict__ lse,
+// =====================================================================================================================================
+// Forward
+// =====================================================================================================================================
+template <bool DROP, Rows L>
+__device__ __forceinline__ void attn_stream_fwd_body(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, float* __restrict__ lse,
                                                      const int* __restrict__ lens, int T, int H, int nqb, int B, int Mq, float scale,
                                                      float drop_p, uint32_t drop_seed) {
+    constexpr bool PACKED = L == Rows::Packed;
     __shared__ __attribute__((aligned(16))) char smem[2][2][LKB * 128];      // [buffer][K rows, V tr][64 keys x 128 B]
     const int E = H * LD;
     const int64_t pitch = 3 * (int64_t)E;
     const int bh = blockIdx.x / nqb, qblk = blockIdx.x % nqb;
     const int b = bh / H, h = bh % H;
-    const UttRows<PACKED> utt(lens, b, T, Mq);
+    const UttRows<L> utt(lens, b, T, Mq);
     const int Tb = utt.Tb;      // one value per workgroup: everything that depends on it is workgroup-uniform
     const bf16_t* base = qkv + utt.r0 * pitch + h * LD;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -68,15 +103,17 @@ __device__ __forceinline__ void attn_fwd_varlen_body(const bf16_t* __restrict__ 
     bf16_t* dst = ctx + (utt.r0 + q) * E + h * LD + 4 * g;
     float* lse_q = lse + ((int64_t)b * H + h) * T + q;
     if constexpr (PACKED) zero_tail_vectors(reinterpret_cast<uint4*>(ctx), lens, B, Mq, E / 8);
-    if (qblk * LQB >= Tb) {      // the whole query block is padding: zeros, and out before any barrier (uniform: qblk and Tb are)
-        if (q < T) {
-            if (g == 0) *lse_q = 0.f;      // lse is padded in both layouts
-            if constexpr (!PACKED) {       // packed: these rows are another utterance's
+    if constexpr (L != Rows::Fixed) {
+        if (qblk * LQB >= Tb) {      // the whole query block is padding: zeros, and out before any barrier (uniform: qblk and Tb are)
+            if (q < T) {
+                if (g == 0) *lse_q = 0.f;      // lse is padded in every layout
+                if constexpr (!PACKED) {       // packed: these rows are another utterance's
 #pragma unroll
-                for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<uint2*>(dst + 16 * dt) = make_uint2(0u, 0u);
+                    for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<uint2*>(dst + 16 * dt) = make_uint2(0u, 0u);
+                }
             }
+            return;
         }
-        return;
     }
     const int nkb = (Tb + LKB - 1) / LKB;
     bf16x8 qf[2];
@@ -160,12 +197,12 @@ __device__ __forceinline__ void attn_fwd_varlen_body(const bf16_t* __restrict__ 
 }
 
 // =====================================================================================================================================
-// Backward: the three passes of scl_attn_bwd_long with Tb keys and queries (see attention_long.hip for the tile scheme)
+// Backward
 // =====================================================================================================================================
 // delta[(b*H + h)*T + q] = <dO, O> of the row for q < Tb, 0 beyond (those rows of ctx / dctx are not read); one thread group of 8 per
-// (b, q, h) of the PADDED space in both layouts, rows = B * T * H
-template <bool PACKED>
-__device__ __forceinline__ void attn_delta_varlen_body(const bf16_t* __restrict__ ctx, const bf16_t* __restrict__ dctx, float* __restrict__ delta,
+// (b, q, h) of the PADDED space in every layout, rows = B * T * H (8 lanes per row, one 16-byte piece each, fixed-order sum)
+template <Rows L>
+__device__ __forceinline__ void attn_stream_delta_body(const bf16_t* __restrict__ ctx, const bf16_t* __restrict__ dctx, float* __restrict__ delta,
                                                        const int* __restrict__ lens, int64_t rows, int T, int H, int Mq) {
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t row = gid >> 3;      // (b, q, h) in memory order
@@ -175,9 +212,9 @@ __device__ __forceinline__ void attn_delta_varlen_body(const bf16_t* __restrict_
     const int64_t b = bq / T, q = bq % T;
     float dot = 0.f;
     if (row < rows) {
-        const UttRows<PACKED> utt(lens, (int)b, T, Mq);
-        if (q < utt.Tb) {
-            const int64_t src = PACKED ? (utt.r0 + q) * H + h : row;
+        const UttRows<L> utt(lens, (int)b, T, Mq);
+        if (L == Rows::Fixed || q < utt.Tb) {
+            const int64_t src = L == Rows::Packed ? (utt.r0 + q) * H + h : row;
             const uint4 vo = *reinterpret_cast<const uint4*>(dctx + src * LD + 8 * c);
             const uint4 vc = *reinterpret_cast<const uint4*>(ctx + src * LD + 8 * c);
             const unsigned ow[4] = {vo.x, vo.y, vo.z, vo.w}, cw[4] = {vc.x, vc.y, vc.z, vc.w};
@@ -192,18 +229,21 @@ __device__ __forceinline__ void attn_delta_varlen_body(const bf16_t* __restrict_
     if (row < rows && c == 0) delta[(b * H + h) * T + q] = dot;
 }
 
-// ---- dK / dV: attn_bwd_dkdv_long_kernel over the utterance's own queries and keys -----------------------------------------------------------
-template <bool DROP, bool PACKED>
-__device__ __forceinline__ void attn_bwd_dkdv_varlen_body(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
-                                                          const float* __restrict__ lse, const float* __restrict__ delta,
-                                                          bf16_t* __restrict__ dqkv, const int* __restrict__ lens, int T, int H, int nkw, int Mq,
-                                                          float scale, float drop_p, uint32_t drop_seed) {
+// ---- dK / dV ------------------------------------------------------------------------------------------------------------------------
+// Query tiles of 32 rows per step: QRegs / qt_fetch / qt_store of attn_tiles.h (Q rows, Q tr, dO rows, dO tr images, lse x log2 e, delta)
+template <bool DROP, Rows L>
+__device__ __forceinline__ void attn_stream_dkdv_body(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
+                                                      const float* __restrict__ lse, const float* __restrict__ delta,
+                                                      bf16_t* __restrict__ dqkv, const int* __restrict__ lens, int T, int H, int nkw, int Mq,
+                                                      float scale, float drop_p, uint32_t drop_seed) {
+    static_assert(L != Rows::Fixed, "the fixed layout's dK / dV kernel has its own body in attention_long.hip");
+    constexpr bool PACKED = L == Rows::Packed;
     __shared__ __attribute__((aligned(16))) char smem[2][QT_BYTES];
     const int E = H * LD;
     const int64_t pitch = 3 * (int64_t)E;
     const int bh = blockIdx.x / nkw, kblk = blockIdx.x % nkw;
     const int b = bh / H, h = bh % H;
-    const UttRows<PACKED> utt(lens, b, T, Mq);
+    const UttRows<L> utt(lens, b, T, Mq);
     const int Tb = utt.Tb;      // one value per workgroup
     const bf16_t* base = qkv + utt.r0 * pitch + h * LD;
     const bf16_t* dob = dctx + utt.r0 * E + h * LD;
@@ -324,18 +364,19 @@ __device__ __forceinline__ void attn_bwd_dkdv_varlen_body(const bf16_t* __restri
     }
 }
 
-// ---- dQ: attn_bwd_dq_long_kernel over the utterance's own keys ---------------------------------------------------------------------------
-template <bool DROP, bool PACKED>
-__device__ __forceinline__ void attn_bwd_dq_varlen_body(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
-                                                        const float* __restrict__ lse, const float* __restrict__ delta,
-                                                        bf16_t* __restrict__ dqkv, const int* __restrict__ lens, int T, int H, int nqb, int B, int Mq,
-                                                        float scale, float drop_p, uint32_t drop_seed) {
+// ---- dQ -------------------------------------------------------------------------------------------------------------------------------
+template <bool DROP, Rows L>
+__device__ __forceinline__ void attn_stream_dq_body(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dctx,
+                                                    const float* __restrict__ lse, const float* __restrict__ delta,
+                                                    bf16_t* __restrict__ dqkv, const int* __restrict__ lens, int T, int H, int nqb, int B, int Mq,
+                                                    float scale, float drop_p, uint32_t drop_seed) {
+    constexpr bool PACKED = L == Rows::Packed;
     __shared__ __attribute__((aligned(16))) char smem[2][3][LKB * 128];      // [buffer][K rows, K tr, V rows]
     const int E = H * LD;
     const int64_t pitch = 3 * (int64_t)E;
     const int bh = blockIdx.x / nqb, qblk = blockIdx.x % nqb;
     const int b = bh / H, h = bh % H;
-    const UttRows<PACKED> utt(lens, b, T, Mq);
+    const UttRows<L> utt(lens, b, T, Mq);
     const int Tb = utt.Tb;      // one value per workgroup
     const bf16_t* base = qkv + utt.r0 * pitch + h * LD;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -343,13 +384,15 @@ __device__ __forceinline__ void attn_bwd_dq_varlen_body(const bf16_t* __restrict
     const int q0 = qblk * LQB + 16 * wave, q = q0 + lc;
     bf16_t* dst = dqkv + (utt.r0 + q) * pitch + h * LD + 4 * g;
     if constexpr (PACKED) zero_tail_vectors(reinterpret_cast<uint4*>(dqkv), lens, B, Mq, 3 * E / 8);
-    if (qblk * LQB >= Tb) {      // the whole query block is padding: zero dQ rows, and out before any barrier (uniform: qblk and Tb are)
-        if constexpr (PACKED) return;      // packed: these rows are another utterance's
-        if (q < T) {
+    if constexpr (L != Rows::Fixed) {
+        if (qblk * LQB >= Tb) {      // the whole query block is padding: zero dQ rows, and out before any barrier (uniform: qblk and Tb are)
+            if constexpr (PACKED) return;      // packed: these rows are another utterance's
+            if (q < T) {
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<uint2*>(dst + 16 * dt) = make_uint2(0u, 0u);
+                for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<uint2*>(dst + 16 * dt) = make_uint2(0u, 0u);
+            }
+            return;
         }
-        return;
     }
     const int nkb = (Tb + LKB - 1) / LKB;
     bf16x8 qf[2], of[2];
@@ -408,6 +451,23 @@ __device__ __forceinline__ void attn_bwd_dq_varlen_body(const bf16_t* __restrict
             *reinterpret_cast<uint2*>(dst + 16 * dt) = valid ? make_uint2(pack_bf2(dq[dt][0] * scale, dq[dt][1] * scale), pack_bf2(dq[dt][2] * scale, dq[dt][3] * scale))
                                                              : make_uint2(0u, 0u);
     }
+}
+
+// =====================================================================================================================================
+// fp32 row soft-max of any length by one wave: a looped online (max, sum) pass over the first Tv columns of s, then the write pass
+// (p[c] = 0 for Tv <= c < Tp)
+// =====================================================================================================================================
+__device__ __forceinline__ void softmax_f32_looped_row(const float* s, float* p, int Tv, int Tp, int lane) {
+    float m = -INFINITY, l = 0.f;
+    for (int c = lane; c < Tv; c += 64) {
+        const float v = s[c];
+        if (v > m) { l = l * __expf(m - v) + 1.f; m = v; }
+        else if (m != -INFINITY) l += __expf(v - m);      // v = m = -inf adds nothing
+    }
+    const float mx = wave_max(m);
+    const float sum = wave_sum(m == -INFINITY ? 0.f : l * __expf(m - mx));
+    const float inv = 1.0f / sum;
+    for (int c = lane; c < Tp; c += 64) p[c] = c < Tv ? __expf(s[c] - mx) * inv : 0.f;
 }
 
 }  // namespace

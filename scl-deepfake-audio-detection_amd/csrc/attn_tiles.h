@@ -1,6 +1,6 @@
 // attn_tiles.h — LDS tile images, MFMA operand fragments and the K / V block staging shared by the streaming attention kernels
-// (attention_long.hip: fixed-length forward / backward; attn_varlen_body.h: the same with per-utterance key counts, for the padded layout of
-// attention_varlen.hip and the packed one of attention_packed.hip).
+// (attn_stream_body.h: the forward / backward bodies behind the fixed-length kernels of attention_long.hip, the padded layout of
+// attention_varlen.hip and the packed one of attention_packed.hip; attention_f32.hip: the fp32 packed forward).
 // Everything is internal to the including file (anonymous namespace, force-inlined).
 #pragma once
 #include "common.h"
