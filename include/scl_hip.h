@@ -212,7 +212,7 @@ int scl_reduce_slabs_multi(const SclSlabJob* jobs, int njobs, void* stream);
 /* ------------------------------------------------------------------------------------------ */
 /* AASIST / ResNet back-end pieces over channels-last fp32 maps (csrc/nn.hip)                  */
 /* ------------------------------------------------------------------------------------------ */
-/* BatchNorm over the rows of x [N, C] (C a power of two <= 512) fused with an activation (act: 0 none, 1 ReLU, 2 SELU).
+/* BatchNorm over the rows of x [N, C] (C a power of two <= 512; with training == 0 <= 2048, the bottleneck networks' last stage) fused with an activation (act: 0 none, 1 ReLU, 2 SELU).
  * training != 0: batch statistics (part: scratch of scl_bn_nslabs(N) * 2 * C DOUBLES = 16 * nslabs * C bytes, 8-byte aligned), running_mean / running_var / num_batches_tracked
  * updated like torch (momentum, unbiased variance); else the running statistics are used.  Saves mean / rstd [C].  Writes
  * y [N, C] f32 (may be NULL) and / or y2: element (row r = (b,i,j), c) at y2[m_base + b*m_bs + i*m_rs + j*m_cs + c] with
@@ -228,6 +228,12 @@ int scl_bn_fwd(const float* x, int N, int C, const float* gamma, const float* be
  * (autograd's accumulation into an attached .grad buffer, done by the finishing kernel). */
 int scl_bn_bwd(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* gamma, int N, int C,
                int act, int training, float* part, float* sums, float* dgamma, float* dbeta, float* dx, int accumulate, void* stream);
+/* Eval-mode BatchNorm + activation of a zero-padded variable-length batch of maps x [B, H, W, C] (scoring only): utterance b owns the rows
+ * h < valid[b] (int32 [B] on the GPU, 0 <= valid[b] <= H; values outside are clamped).  y[b][h] = act(bn(x[b][h])) with the running statistics for
+ * h < valid[b], the bits scl_bn_fwd (training = 0) gives, and exactly 0.0f for h >= valid[b]: selected, never multiplied, and x is not read
+ * there (it may hold NaN / Inf).  mean / rstd [C]: scratch, written.  One apply launch, no zeroing pass.  C a power of two <= 2048; C % 4 == 0: 16-byte aligned pointers. */
+int scl_bn_eval_masked(const float* x, int B, int H, int W, int C, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, float eps, int act, const int32_t* valid, float* mean, float* rstd, float* y, void* stream);
 /* src [rows, C] contiguous f32 -> mapped (padded / dilated) destination, f32 or bf16 (row mapping as scl_bn_fwd's y2) */
 int scl_pad_nhwc_f32(const float* src, int64_t rows, int C, void* dst, int dst_bf16, int m_W, int m_HW, int64_t m_bs, int64_t m_rs,
                      int64_t m_cs, int64_t m_base, void* stream);
@@ -244,6 +250,9 @@ int scl_maxpool3_bwd(const float* dy, const int* idx, int H, int W, int B, float
 /* y[b][c] = mean_r x[b][r][c] (F.adaptive_avg_pool2d(x, 1) on a channels-last map, model/resnet.py:186) and its backward */
 int scl_avgpool_fwd(const float* x, int B, int R, int C, float* y, void* stream);
 int scl_avgpool_bwd(const float* dy, int B, int R, int C, float* dx, void* stream);
+/* y[b][c] = sum_{h < valid[b], w} x[b][h][w][c] / (valid[b] * W) over x [B, H, W, C], valid as above with valid[b] >= 1 (validate on the host:
+ * scl_varlen_check_lengths; a count of 0 yields 0).  Fixed order, no atomics: the bits of scl_avgpool_fwd on the slice [1, valid[b] * W, C] alone. */
+int scl_avgpool_fwd_masked(const float* x, const int32_t* valid, int B, int H, int W, int C, float* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* LayerNorm (+GELU), column reductions                                                        */

@@ -31,6 +31,7 @@ from model.wav2vec2_btse import wav2vec2_btse
 
 MODEL_REGISTRY = {"wav2vec2_linear_nll": wav2vec2_linear_nll, "wav2vec2_aasist": wav2vec2_aasist, "wav2vec2_resnet_nll": wav2vec2_resnet_nll,
                   "wav2vec2_btse": wav2vec2_btse}
+VARLEN_MODELS = ("wav2vec2_linear_nll", "wav2vec2_resnet_nll")      # --padding_type none: the plugins whose forward takes `lengths`
 
 
 class EarlyStop:
@@ -402,9 +403,9 @@ def main(argv=None):
         sys.exit("main.py: model wav2vec2_btse needs the YAML key model.bio_tokenizer = '<module>:<callable>' (waveforms [bz, L] numpy, "
                  "sample_rate) -> equal-length token rows; the reference's biosegment package does not exist, so %s cannot run as shipped "
                  "(scl_amd/model_btse.py; bench.py --model wav2vec2_btse feeds synthetic tokens)" % args.config)
-    if args.padding_type == "none" and config["model"]["name"] != "wav2vec2_linear_nll":
-        sys.exit("main.py: --padding_type none needs a model that takes per-utterance lengths: wav2vec2_linear_nll only (%s has no padding "
-                 "mask in its back-end); use --padding_type zero or repeat" % config["model"]["name"])
+    if args.padding_type == "none" and config["model"]["name"] not in VARLEN_MODELS:
+        sys.exit("main.py: --padding_type none needs a model that takes per-utterance lengths: wav2vec2_linear_nll only, or the scoring mode "
+                 "of wav2vec2_resnet_nll (%s has no padding mask in its back-end); use --padding_type zero or repeat" % config["model"]["name"])
     model = MODEL_REGISTRY[config["model"]["name"]](config["model"], device, seed=args.seed, rank=rank)
     print("nb_params:", sum(p.numel() for p in model.parameters()))
 
@@ -438,6 +439,8 @@ def main(argv=None):
         _, file_eval = genList(dir_meta=proto, is_train=False, is_eval=True)
         print("no. of eval trials", len(file_eval))
         eval_set = Dataset_for_eval(list_IDs=file_eval, base_dir=os.path.join(args.database_path + "/"), padding_type=args.padding_type)
+        if args.padding_type == "none":      # shorter files are zero-padded to what the model takes (400 samples; 17,680 for the ResNet back-end)
+            eval_set.min_samples = model.min_samples()
         final_output = args.eval_output
         if world > 1:
             eval_set = Subset(eval_set, list(range(rank, len(eval_set), world)))

@@ -159,6 +159,20 @@ __device__ __forceinline__ long long map_row(const RowMap& m, long long r) {
     return m.base + b * m.bs + (long long)i * m.rs + (long long)j * m.cs;
 }
 
+// one element of BatchNorm + activation: the single expression every apply kernel below compiles, so their valid elements agree bit for bit
+__device__ __forceinline__ float bn_elem(int act, float x, float m, float r, float g, float b) { return nn_act(act, (x - m) * r * g + b); }
+__device__ __forceinline__ float4 bn_elem4(int act, const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                           const float* __restrict__ gamma, const float* __restrict__ beta, long long e, int c) {
+    const float4 xv = *reinterpret_cast<const float4*>(x + e), mv = *reinterpret_cast<const float4*>(mean + c), rv = *reinterpret_cast<const float4*>(rstd + c);
+    float4 gv = make_float4(1.f, 1.f, 1.f, 1.f), bv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (gamma) gv = *reinterpret_cast<const float4*>(gamma + c);
+    if (beta) bv = *reinterpret_cast<const float4*>(beta + c);
+    float4 o;
+    o.x = bn_elem(act, xv.x, mv.x, rv.x, gv.x, bv.x); o.y = bn_elem(act, xv.y, mv.y, rv.y, gv.y, bv.y);
+    o.z = bn_elem(act, xv.z, mv.z, rv.z, gv.z, bv.z); o.w = bn_elem(act, xv.w, mv.w, rv.w, gv.w, bv.w);
+    return o;
+}
+
 // y = act((x - mean) * rstd * gamma + beta) -> contiguous f32 (kept for the backward) and / or a mapped (padded) f32 / bf16 map
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta, long long n, int C, int act,
@@ -167,27 +181,52 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     if ((C & 3) == 0 && !y2) {       // 16-byte path (every map but the single-channel input)
         for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < (n >> 2); q += (long long)gridDim.x * 256) {
             const long long e = q << 2;
-            const int c = (int)(e & (C - 1));
-            const float4 xv = *reinterpret_cast<const float4*>(x + e), mv = *reinterpret_cast<const float4*>(mean + c), rv = *reinterpret_cast<const float4*>(rstd + c);
-            float4 gv = make_float4(1.f, 1.f, 1.f, 1.f), bv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gamma) gv = *reinterpret_cast<const float4*>(gamma + c);
-            if (beta) bv = *reinterpret_cast<const float4*>(beta + c);
-            float4 o;
-            o.x = nn_act(act, (xv.x - mv.x) * rv.x * gv.x + bv.x); o.y = nn_act(act, (xv.y - mv.y) * rv.y * gv.y + bv.y);
-            o.z = nn_act(act, (xv.z - mv.z) * rv.z * gv.z + bv.z); o.w = nn_act(act, (xv.w - mv.w) * rv.w * gv.w + bv.w);
-            *reinterpret_cast<float4*>(y + e) = o;
+            *reinterpret_cast<float4*>(y + e) = bn_elem4(act, x, mean, rstd, gamma, beta, e, (int)(e & (C - 1)));
         }
         return;
     }
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
         const int c = (int)(e & (C - 1));
         const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-        const float v = nn_act(act, (x[e] - mean[c]) * rstd[c] * g + b);
+        const float v = bn_elem(act, x[e], mean[c], rstd[c], g, b);
         if (y) y[e] = v;
         if (y2) {
             const long long o = map_row(map, e >> cshift) + c;
             if (y2_bf16) reinterpret_cast<bf16_t*>(y2)[o] = f2bf(v); else reinterpret_cast<float*>(y2)[o] = v;
         }
+    }
+}
+
+// The same on a zero-padded batch of maps [B][H][W][C] whose utterance b owns the rows h < valid[b]: y = act(bn(x)) there and exactly 0
+// beyond, by SELECTION - x is not read at or beyond row valid[b] (it may hold NaN / Inf: the padding of a variable-length batch after a
+// convolution is junk).  blockIdx.y is the utterance, so the row limit is one uniform scalar load per block and an element's place is a
+// compare against `lim`; `per` = H*W*C and `rowc` = W*C are launch constants.  Zeros are written by the launch that writes the rest.
+__global__ __launch_bounds__(256) void bn_apply_masked_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              const int* __restrict__ valid, long long per, int rowc, int H, int C, int act,
+                                                              float* __restrict__ y) {
+    const int b = blockIdx.y;
+    int v = valid[b];
+    v = v < 0 ? 0 : (v > H ? H : v);          // the host validates; a stale count must still stay inside the map
+    const long long lim = (long long)v * rowc;
+    const float* __restrict__ xb = x + (long long)b * per;
+    float* __restrict__ yb = y + (long long)b * per;
+    if ((C & 3) == 0) {       // per, lim and every row start are multiples of 4 elements: a 16-byte vector is valid or padding as a whole
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < (per >> 2); q += (long long)gridDim.x * 256) {
+            const long long e = q << 2;
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e < lim) o = bn_elem4(act, xb, mean, rstd, gamma, beta, e, (int)(e & (C - 1)));
+            *reinterpret_cast<float4*>(yb + e) = o;
+        }
+        return;
+    }
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long long)gridDim.x * 256) {
+        float o = 0.f;
+        if (e < lim) {
+            const int c = (int)(e & (C - 1));
+            o = bn_elem(act, xb[e], mean[c], rstd[c], gamma ? gamma[c] : 1.f, beta ? beta[c] : 0.f);
+        }
+        yb[e] = o;
     }
 }
 
@@ -331,6 +370,21 @@ __global__ __launch_bounds__(256) void avgpool_fwd_kernel(const float* __restric
         y[(long long)b * C + c] = s / (float)R;
     }
 }
+// y[b][c] = mean over the rows r < valid[b] * W of x[b] ([B][H*W][C], utterance b owns its first valid[b] * W rows): avgpool_fwd_kernel's
+// summation order and division for the utterance's slice alone, so the bits are those of that slice pooled on its own.  Rows beyond are not read.
+__global__ __launch_bounds__(256) void avgpool_fwd_masked_kernel(const float* __restrict__ x, const int* __restrict__ valid, int H, int W, int C,
+                                                                 float* __restrict__ y) {
+    const int b = blockIdx.x;
+    int v = valid[b];
+    v = v < 0 ? 0 : (v > H ? H : v);
+    const int R = v * W;
+    const float* __restrict__ xb = x + (long long)b * H * W * C;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float s = 0.f;
+        for (int r = 0; r < R; ++r) s += xb[(long long)r * C + c];
+        y[(long long)b * C + c] = R > 0 ? s / (float)R : 0.f;
+    }
+}
 __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float* __restrict__ dy, int R, int C, long long n, float* __restrict__ dx) {
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
         const long long b = e / ((long long)R * C);
@@ -340,6 +394,9 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float* __restric
 
 int grid_for(long long n) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
 bool bn_channels_ok(int C) { return C >= 1 && (C == 512 || (C <= 256 && 256 % C == 0)); }
+// eval mode launches no statistics kernel (their slab layout is what limits C above): any power of two the apply kernels' `e & (C - 1)`
+// takes, up to the 2048 channels of the bottleneck networks' last stage
+bool bn_eval_channels_ok(int C) { return C >= 1 && C <= 2048 && (C & (C - 1)) == 0; }
 
 }  // namespace
 
@@ -349,7 +406,8 @@ extern "C" int scl_bn_fwd(const float* x, int N, int C, const float* gamma, cons
                           long long* num_batches_tracked, int training, float momentum, float eps, int act, float* part, float* mean,
                           float* rstd, float* y, void* y2, int y2_bf16, int m_W, int m_HW, int64_t m_bs, int64_t m_rs, int64_t m_cs,
                           int64_t m_base, void* stream) {
-    SCL_REQUIRE(x && mean && rstd && (y || y2) && N >= 1 && bn_channels_ok(C), "bn_fwd: bad args (C must divide 256 or be 512)");
+    SCL_REQUIRE(x && mean && rstd && (y || y2) && N >= 1 && (training ? bn_channels_ok(C) : bn_eval_channels_ok(C)),
+                "bn_fwd: bad args (C must divide 256 or be 512; eval mode: a power of two <= 2048)");
     SCL_REQUIRE(training ? part != nullptr : (running_mean && running_var), "bn_fwd: training needs `part`, eval needs running statistics");
     SCL_REQUIRE(act >= 0 && act <= 2, "bn_fwd: act");
     hipStream_t s = (hipStream_t)stream;
@@ -361,6 +419,26 @@ extern "C" int scl_bn_fwd(const float* x, int N, int C, const float* gamma, cons
     hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for((long long)N * C)), dim3(256), 0, s, x, mean, rstd, gamma, beta, (long long)N * C, C, act, y, y2,
                        y2_bf16, map);
     return scl_check_launch("scl_bn_fwd");
+}
+
+extern "C" int scl_bn_eval_masked(const float* x, int B, int H, int W, int C, const float* gamma, const float* beta, const float* running_mean,
+                                  const float* running_var, float eps, int act, const int32_t* valid, float* mean, float* rstd, float* y,
+                                  void* stream) {
+    SCL_REQUIRE(x && running_mean && running_var && valid && mean && rstd && y, "bn_eval_masked: null argument (running statistics: eval mode only)");
+    SCL_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && bn_eval_channels_ok(C), "bn_eval_masked: need 1 <= B <= 65535, H, W >= 1, C a power of two <= 2048");
+    SCL_REQUIRE((long long)H * W * C < (1ll << 31), "bn_eval_masked: H * W * C of one utterance must stay below 2^31");
+    SCL_REQUIRE(act >= 0 && act <= 2, "bn_eval_masked: act");
+    SCL_REQUIRE((C & 3) != 0 || ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0),
+                "bn_eval_masked: C % 4 == 0 takes 16-byte aligned x, y, mean, rstd, gamma, beta");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_finish_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, (const double*)nullptr, 0, 1, C, eps, 0.f, 0, const_cast<float*>(running_mean),
+                       const_cast<float*>(running_var), (long long*)nullptr, mean, rstd);
+    const long long per = (long long)H * W * C;
+    int gx = grid_for(per >> ((C & 3) == 0 ? 2 : 0));
+    const int cap = (8192 + B - 1) / B;          // the unmasked launch's block budget, shared among the utterances
+    if (gx > cap) gx = cap;
+    hipLaunchKernelGGL(bn_apply_masked_kernel, dim3(gx, B), dim3(256), 0, s, x, mean, rstd, gamma, beta, valid, per, W * C, H, C, act, y);
+    return scl_check_launch("scl_bn_eval_masked");
 }
 
 extern "C" int scl_bn_bwd(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* gamma, int N, int C,
@@ -473,6 +551,12 @@ extern "C" int scl_avgpool_fwd(const float* x, int B, int R, int C, float* y, vo
     SCL_REQUIRE(x && y && B >= 1 && R >= 1 && C >= 1, "avgpool_fwd: bad args");
     hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x, R, C, y);
     return scl_check_launch("scl_avgpool_fwd");
+}
+extern "C" int scl_avgpool_fwd_masked(const float* x, const int32_t* valid, int B, int H, int W, int C, float* y, void* stream) {
+    SCL_REQUIRE(x && valid && y && B >= 1 && H >= 1 && W >= 1 && C >= 1, "avgpool_fwd_masked: bad args");
+    SCL_REQUIRE((long long)H * W < (1ll << 31), "avgpool_fwd_masked: H * W must stay below 2^31");
+    hipLaunchKernelGGL(avgpool_fwd_masked_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x, valid, H, W, C, y);
+    return scl_check_launch("scl_avgpool_fwd_masked");
 }
 extern "C" int scl_avgpool_bwd(const float* dy, int B, int R, int C, float* dx, void* stream) {
     SCL_REQUIRE(dy && dx && B >= 1 && R >= 1 && C >= 1, "avgpool_bwd: bad args");

@@ -106,12 +106,16 @@ class W2VConfig:
             out.append(L)
         return out
 
-    def min_samples(self):
-        """The shortest clip that yields one frame (400 samples for the XLS-R stack)."""
-        L = 1
+    def samples_for(self, frames):
+        """The shortest clip that yields `frames` frames (400 + 320 (frames - 1) samples for the XLS-R stack)."""
+        L = int(frames)
         for k, s in zip(reversed(self.conv_kernels), reversed(self.conv_strides)):
             L = (L - 1) * s + k
         return L
+
+    def min_samples(self):
+        """The shortest clip that yields one frame (400 samples for the XLS-R stack)."""
+        return self.samples_for(1)
 
 
 def param_specs(cfg, prefix="ssl_model.model."):

@@ -79,11 +79,14 @@ def _packed_conv(weight, dtype, Co, Ci, kh, kw, Cp, Cop):
 _ZERO_POOL = {}
 
 
-def _zeros_acquire(key, numel, dtype, dev):
+def _zeros_acquire(key, numel, dtype, dev, pooled=True):
     """-> entry [tensor, busy, generation].  The generation is bumped on every hand-out: whoever releases (or reads, in a backward) passes
     the generation it was given, so a stale owner — the finaliser of a graph whose backward already released the entry, after a later
-    forward took it — can neither free nor silently read a buffer that now belongs to someone else (round-5 advisory)."""
-    if torch.cuda.is_current_stream_capturing():
+    forward took it — can neither free nor silently read a buffer that now belongs to someone else (round-5 advisory).
+    pooled=False: a buffer of the caller's own, zero-filled now and back with the allocator when the caller lets go of it — the
+    variable-length scoring batches (conv2d pooled=False), whose every padded length is a geometry of its own: pooled, each length met
+    would pin a set of staging maps for the life of the process."""
+    if not pooled or torch.cuda.is_current_stream_capturing():
         return [torch.zeros(numel, dtype=dtype, device=dev), True, 1]
     lst = _ZERO_POOL.setdefault((key, numel, dtype, dev.index, torch.cuda.current_stream(dev).cuda_stream), [])
     for ent in lst:
@@ -119,7 +122,7 @@ def _colsum(x2d, M, N):
 # ---- convolution ---------------------------------------------------------------------------------------------------------------------
 class _Conv2dFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, padding, dtype, x3_bwd=False, grad_in_place=False, residual=None):
+    def forward(ctx, x, weight, bias, stride, padding, dtype, x3_bwd=False, grad_in_place=False, residual=None, pooled=True):
         """x [B, H, W, Ci] f32; weight [Co, Ci, kh, kw] (torch layout); bias [Co] or None -> y [B, OH, OW, Co] f32 (+ residual, same shape)."""
         B, H, W, Ci = x.shape
         Co, _, kh, kw = weight.shape
@@ -131,7 +134,7 @@ class _Conv2dFn(torch.autograd.Function):
         OH, OW = (Hp - kh) // sh + 1, (Wp - kw) // sw + 1
         dev = x.device
         rowmap = (W, H * W, Hp * Wp * Cp, Wp * Cp, Cp, (ph * Wp + pw) * Cp)
-        ent = _zeros_acquire(("xp", id(weight), Ci) + rowmap, B * Hp * Wp * Cp + 4096, dtype, dev)        # tail slack: tile rows past the map are masked, not skipped
+        ent = _zeros_acquire(("xp", id(weight), Ci) + rowmap, B * Hp * Wp * Cp + 4096, dtype, dev, pooled)        # tail slack: tile rows past the map are masked, not skipped
         xp = ent[0]
         xc = x.contiguous()
         ops.pad_nhwc(xc, B * H * W, Ci, xp, rowmap)
@@ -230,16 +233,19 @@ class _Conv2dFn(torch.autograd.Function):
         if ent_p is not None:
             _zeros_release(ent_p)
         _zeros_release(ctx.xp_ent, ctx.xp_gen)
-        return dx, dw, db, None, None, None, None, None, (dy if ctx.needs_input_grad[8] else None)
+        return dx, dw, db, None, None, None, None, None, (dy if ctx.needs_input_grad[8] else None), None
 
 
-def conv2d(x, weight, bias=None, stride=(1, 1), padding=(0, 0), dtype=torch.float32, x3_bwd=False, grad_in_place=False, residual=None):
+def conv2d(x, weight, bias=None, stride=(1, 1), padding=(0, 0), dtype=torch.float32, x3_bwd=False, grad_in_place=False, residual=None,
+           pooled=True):
     """Channels-last 2-D convolution (cross-correlation, as nn.Conv2d): x [B, H, W, Ci] -> [B, OH, OW, Co] (+ residual [B, OH, OW, Co], added in
     the GEMM epilogue; its gradient is the output gradient).  grad_in_place: the weight
     gradient is ADDED into `weight.grad` by the finishing kernel (when that tensor exists) instead of being returned to autograd — for
     `.backward()` callers whose parameters carry attached .grad views (the plugins' flat gradient buffer); torch.autograd.grad callers
-    leave it off."""
-    return _Conv2dFn.apply(x, weight, bias, tuple(stride), tuple(padding), dtype, x3_bwd, grad_in_place, residual)
+    leave it off.  pooled=False (no-grad callers only): the zero-bordered staging map is not kept in the per-geometry pool (_zeros_acquire)."""
+    if not pooled and torch.is_grad_enabled():
+        raise ValueError("hipnn.conv2d: pooled=False is for forward-only callers (torch.no_grad())")
+    return _Conv2dFn.apply(x, weight, bias, tuple(stride), tuple(padding), dtype, x3_bwd, grad_in_place, residual, pooled)
 
 
 # ---- BatchNorm (+ activation) --------------------------------------------------------------------------------------------------------
@@ -281,10 +287,25 @@ class _BatchNormFn(torch.autograd.Function):
         return dx, dg, db, None, None, None, None, None, None, None, None
 
 
-def batch_norm(x, bn, act=ACT_NONE, grad_in_place=False):
+def batch_norm(x, bn, act=ACT_NONE, grad_in_place=False, valid=None):
     """nn.BatchNorm1d / 2d semantics over the LAST dimension of x (channels-last), fused with `act`; `bn` supplies weight, bias, the
-    running statistics and the training flag (its forward is never called).  grad_in_place: as conv2d's."""
+    running statistics and the training flag (its forward is never called).  grad_in_place: as conv2d's.
+    valid: int32 [B] on the GPU with x [B, H, W, C], the rows h < valid[b] that utterance b of a zero-padded variable-length batch owns
+    (0 <= valid[b] <= H, validated by the caller on the host).  Eval mode under torch.no_grad() only: in eval mode a BatchNorm is a
+    per-element map, so the valid rows get the bits they get without `valid`, and the rest is exactly 0 whatever x holds there."""
     training = bn.training or bn.running_mean is None
+    if valid is not None:
+        if training or torch.is_grad_enabled():
+            raise NotImplementedError("hipnn.batch_norm: `valid` is a scoring mode (a BatchNorm in eval mode under torch.no_grad()); "
+                                      "batch statistics over the valid positions and a backward are not implemented")
+        if x.dim() != 4:
+            raise ValueError("hipnn.batch_norm: `valid` needs a [B, H, W, C] map, got %r" % (tuple(x.shape),))
+        B, H, W, C = x.shape
+        xc = x.contiguous().float()
+        mean, rstd = torch.empty(C, device=x.device), torch.empty(C, device=x.device)
+        y = torch.empty_like(xc)
+        ops.bn_eval_masked(xc, B, H, W, C, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, act, valid, mean, rstd, y)
+        return y
     momentum = 0.1 if bn.momentum is None else bn.momentum
     return _BatchNormFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked if training else None, training,
                               momentum, bn.eps, act, grad_in_place)
@@ -439,3 +460,17 @@ class _AvgPoolFn(torch.autograd.Function):
 
 def avg_pool_rows(x):
     return _AvgPoolFn.apply(x)
+
+
+def avg_pool_rows_masked(x, valid, counts=None):
+    """x [B, H, W, C] of a zero-padded variable-length batch -> [B, C]: the mean over the rows h < valid[b] (int32 [B] on the GPU) and all of
+    W, the bits avg_pool_rows gives for the utterance's [1, valid[b] * W, C] slice alone.  counts: the same counts on the host, checked to be
+    in 1..H before anything is launched (a caller that validated them already leaves it out).  Forward only."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise NotImplementedError("hipnn.avg_pool_rows_masked: forward only (scoring mode)")
+    B, H, W, C = x.shape
+    if counts is not None:
+        ops.check_lengths(counts, H)
+    y = torch.empty(B, C, device=x.device)
+    ops.avgpool_fwd_masked(x.contiguous().float(), valid, B, H, W, C, y)
+    return y

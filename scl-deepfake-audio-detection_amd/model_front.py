@@ -7,6 +7,9 @@ features is an nn.Module (a parameter container whose forward is hand-written HI
 graph.py, resnet_head.py, btse_head.py) whose parameters are views into the same flat fp32 buffer, so the fused AdamW kernel and the
 data-parallel gradient buckets cover them too.  SCL_HEAD_GRAPH=1 replays a back-end as two captured hipGraphs per feature shape (off by
 default: the HIP back-ends are a few dozen launches).
+Variable-length scoring batches (forward(x, lengths), eval mode under torch.no_grad()) for a back-end that declares `head_takes_frames`
+and whose `_head_forward(mod, feats, frames)` masks the padding itself (resnet_head.py): the encoder runs with its padding mask on either
+scoring precision and either row layout, feats rows beyond an utterance's frames are zeroed, and the back-end gets the host-side frame counts.
 Sub-classes supply `_build_head(args)` (an nn.Module whose children / parameters are grafted at the root under the
 reference's state-dict names) and `_head_forward(mod, feats) -> (output, emb)`.
 """
@@ -15,8 +18,9 @@ import os
 import torch
 from torch import nn
 
+from . import encoder as ENC
 from . import ops
-from .encoder import Encoder, W2VConfig, param_specs
+from .encoder import Encoder, VarlenSets, W2VConfig, param_specs
 from .model_linear import SCORE_FP32, dropout_stream_seed, init_parameters_, loss_custom, maybe_load_pretrained
 from .ops import Op
 from .params import FlatParams, register_by_name
@@ -57,6 +61,7 @@ class _HeadRunner(nn.Module):
 
 class FrontHeadModel(nn.Module):
     flag_fix_ssl = False
+    head_takes_frames = False      # the back-end masks the padding of a variable-length batch: _head_forward(mod, feats, frames)
     front_prefix = ""        # module path of `ssl_model` / `LL` in the state dict ("backend." for wav2vec2_btse, backend.py:31-33)
 
     def _build_head(self, args):
@@ -68,6 +73,14 @@ class FrontHeadModel(nn.Module):
 
     def _ssl_train(self):
         return bool(self.training)
+
+    def head_min_frames(self):
+        """The fewest frames per utterance the back-end takes (a head_takes_frames plugin overrides it)."""
+        return 1
+
+    def min_samples(self):
+        """The shortest row forward(x, lengths) takes: main.py --padding_type none zero-pads shorter files to it."""
+        return self.cfg.samples_for(self.head_min_frames())
 
     def __init__(self, args, device, is_train=True, w2v_cfg=None, seed=0, rank=0):
         super().__init__()
@@ -113,6 +126,10 @@ class FrontHeadModel(nn.Module):
         self.ssl = Encoder(self.cfg, self.P)
         self._anchor = torch.zeros((), device=self.device, requires_grad=True)
         self._states = {}
+        # variable-length scoring batches on the bf16 path: boundary buffers, frame counts and launch plans per padded shape, least
+        # recently used of at most encoder.VARLEN_SETS (every padded length of a --padding_type none run is a shape of its own); an
+        # evicted shape takes its encoder buffer set with it.  The fp32 scoring path keeps no state here (Encoder.forward_f32's own LRU).
+        self._vstates = VarlenSets(on_evict=lambda key: self.ssl._vbufs.pop(key, None))
         self.out_dim = self.cfg.embed
         self.grad_sync = None
         self._drop_step = dropout_stream_seed(seed, rank)      # encoder element-dropout masks differ per --seed and per data-parallel rank
@@ -226,15 +243,92 @@ class FrontHeadModel(nn.Module):
 
     # forward / loss --------------------------------------------------------------------------------
     VARLEN_REFUSAL = ("variable-length batches (forward(x, lengths), main.py --padding_type none) are implemented for the "
-                      "wav2vec2_linear_nll plugin only: this back-end has no padding mask; score fixed-length clips (--padding_type "
-                      "zero / repeat) or one utterance per call")
+                      "wav2vec2_linear_nll plugin and, for scoring, wav2vec2_resnet_nll: this back-end has no padding mask; score "
+                      "fixed-length clips (--padding_type zero / repeat) or one utterance per call")
+
+    def _frame_counts(self, lengths, B, L):
+        """Sample counts of a zero-padded batch -> frame counts, a list of ints validated on the host (model_linear._frame_counts, but a
+        row below the back-end's minimum is an error: its zero padding would have to count as signal through the whole back-end)."""
+        lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lengths) != B or any(n < 1 or n > L for n in lengths):
+            raise ValueError("lengths: need one sample count in 1..%d per row of the [%d, %d] batch, got %r" % (L, B, L, lengths))
+        lo = self.min_samples()
+        if any(n < lo for n in lengths):
+            raise ValueError("lengths: this back-end needs at least %d samples (%d frames) per row, got %r; zero-pad shorter utterances "
+                             "to %d samples" % (lo, self.head_min_frames(), lengths, lo))
+        return ops.check_lengths([self.cfg.conv_lens(n)[-1] for n in lengths], self.cfg.conv_lens(L)[-1])
+
+    def _upload_i32(self, values):
+        return torch.tensor(values, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+
+    def _varlen_state(self, B, L, packed):
+        def make():
+            T = self.cfg.conv_lens(L)[-1]
+            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
+            return dict(T=T, x=f32(B, L), feats=f32(B, T, FEAT_DIM), scratch=torch.empty(B * T * FEAT_DIM + 1024, dtype=torch.bfloat16, device=self.device),
+                        frames=torch.ones(B, dtype=torch.int32, device=self.device),
+                        row0=torch.arange(B + 1, dtype=torch.int32, device=self.device) if packed else None, plans={})
+        return self._vstates.get_or_make((B, L, "packed") if packed else (B, L), make)
+
+    def _front_forward_varlen(self, x, frames, rows):
+        """Encoder (bf16 kernels, padding mask; rows = (row0, Mq): packed layout) + LL + zero_tail_rows on a variable-length scoring batch:
+        the shape's state with fixed addresses, one launch plan per shape (and packed row count), counts overwritten before a replay."""
+        B, L = x.shape
+        st = self._varlen_state(B, L, rows is not None)
+        st["x"].copy_(x)
+        st["frames"].copy_(frames)
+        Mq = None
+        if rows is not None:
+            st["row0"].copy_(rows[0])
+            Mq = int(rows[1])
+        self.ssl.refresh_weights()
+        plan = st["plans"].get(Mq)
+        if plan is not None:
+            ops.replay(plan)
+            return st["feats"]
+        ops.start_recording()
+        P, E = self.P, self.cfg.embed
+        enc_out, _ = self.ssl.forward(st["x"], training=False, refresh=False, frames=st["frames"], grad=False,
+                                      packed=None if Mq is None else (st["row0"], Mq))
+        M = B * st["T"]
+        ops.gemm(Op(enc_out, E), Op(P.bf16, E, offset=P.off("LL.weight")), st["scratch"], M, FEAT_DIM, E, bias=P.f32("LL.bias"), c2=st["feats"])
+        ops.zero_tail_rows(st["feats"], st["frames"], B, st["T"], FEAT_DIM)
+        st["plans"][Mq] = ops.stop_recording()
+        return st["feats"]
+
+    def _forward_varlen(self, x, lengths):
+        if self.training or torch.is_grad_enabled():
+            raise NotImplementedError("%s: forward(x, lengths) is a scoring mode on model.eval() under torch.no_grad(); training on "
+                                      "zero-padded batches is implemented for the wav2vec2_linear_nll plugin only"
+                                      % type(self).__module__.split(".")[-1])
+        B, L = x.shape
+        counts = self._frame_counts(lengths, B, L)
+        frames = self._upload_i32(counts)
+        rows = None
+        if ENC.SCORE_PACK if SCORE_FP32 else ENC.VARLEN_PACK:      # as model_linear._forward: one switch per scoring precision
+            row0, Mq = ops.packed_rows(counts, self.cfg.conv_lens(L)[-1], ENC.PACK_ROWS)
+            rows = (self._upload_i32(row0), Mq)
+        if SCORE_FP32:
+            E = self.cfg.embed
+            enc, T = self.ssl.forward_f32(x, frames, packed=rows)
+            feats = torch.empty(B, T, FEAT_DIM, device=self.device)
+            ops.gemm(Op(enc, E), Op(self.P.flat, E, offset=self.P.off("LL.weight")), feats, B * T, FEAT_DIM, E, bias=self.P.f32("LL.bias"))
+            ops.zero_tail_rows(feats, frames, B, T, FEAT_DIM)
+        else:
+            feats = self._front_forward_varlen(x, frames, rows).clone()
+        output, last_hidden = self._head_forward(self, feats, counts)
+        if self.is_train:
+            return output, feats, last_hidden
+        return output
 
     def forward(self, x, lengths=None):
-        if lengths is not None:
+        if lengths is not None and not self.head_takes_frames:
             raise NotImplementedError("%s: %s" % (type(self).__module__.split(".")[-1], self.VARLEN_REFUSAL))
         if x.dim() == 3:
             x = x[:, :, 0]
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        if lengths is not None:
+            return self._forward_varlen(x, lengths)
         if torch.is_grad_enabled():
             feats = _FrontFn.apply(self, x, self._anchor)
         elif not self.training and SCORE_FP32:

@@ -249,6 +249,10 @@ class Model(nn.Module):
                              % (L, B, L, lo, lengths))
         return ops.check_lengths([self.cfg.conv_lens(max(n, lo))[-1] for n in lengths], self.cfg.conv_lens(L)[-1])
 
+    def min_samples(self):
+        """The shortest row forward(x, lengths) takes (main.py --padding_type none pads shorter files to it): one frame."""
+        return self.cfg.min_samples()
+
     def _upload_i32(self, values):
         host = torch.tensor(values, dtype=torch.int32)
         return (host.pin_memory() if self.device.type == "cuda" else host).to(self.device, non_blocking=True)

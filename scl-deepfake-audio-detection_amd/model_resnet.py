@@ -2,6 +2,8 @@
 
     Model(args: dict with `flag_fix_ssl`, `contra_mode`, `loss_type` and a `resnet` section, device, is_train=True)
     forward(x [bz, L]) -> (logits [bz, 2], feats [bz, T, 128], emb [bz, 256])   (logits only when not is_train)
+    forward(x, lengths=[n_0, ...])   scoring mode (eval, no grad): row b holds n_b >= min_samples() samples followed by padding and gets the
+                                     result it gets alone at its own length; feats rows beyond an utterance's frames are 0
     loss(output, feats, emb, labels, config, info=None) -> dict of 0-d tensors
 
 Encoder + LL + losses: HIP kernels; back-end: `resnet_head.ResNetHead` on flat-buffer parameter views, replayed as hipGraphs in
@@ -11,10 +13,12 @@ training (scl_amd/model_front.py).  Differences from the linear plugin that the 
 """
 from .model_front import FrontHeadModel
 from .model_linear import loss_custom
-from .resnet_head import DEFAULT_RESNET, ResNetHead
+from .resnet_head import DEFAULT_RESNET, ResNetHead, min_frames
 
 
 class Model(FrontHeadModel):
+    head_takes_frames = True      # forward(x, lengths) in scoring mode: the back-end masks the padding (resnet_head.py)
+
     def __init__(self, args, device, is_train=True, w2v_cfg=None, seed=0, rank=0):
         super().__init__(args, device, is_train=is_train, w2v_cfg=w2v_cfg, seed=seed, rank=rank)
         self.flag_fix_ssl = bool(args.get("flag_fix_ssl", False))
@@ -26,6 +30,9 @@ class Model(FrontHeadModel):
         return ResNetHead(args.get("resnet") or DEFAULT_RESNET)
 
     _head_forward = staticmethod(ResNetHead.forward)
+
+    def head_min_frames(self):
+        return min_frames(self.resnet.resnet_type, self.resnet.num_nodes)
 
     def _ssl_train(self):
         # wav2vec2_resnet_nll.py:54-58 -> xlsr.py:23-42: eval mode when frozen, else train/eval follows `is_train`

@@ -799,6 +799,14 @@ def bn_fwd(x, N, C, gamma, beta, running_mean, running_var, nbt, training, momen
           _p(part), _p(mean), _p(rstd), _p(y), _p(y2), 1 if (y2 is not None and y2.dtype == torch.bfloat16) else 0, W_, HW, bs, rs, cs, base, _stream())
 
 
+def bn_eval_masked(x, B, H, W, C, gamma, beta, running_mean, running_var, eps, act, valid, mean, rstd, y):
+    """Eval-mode BatchNorm + activation of x [B, H, W, C] for the rows h < valid[b] (int32 [B] on the GPU), exactly 0 beyond (selected: x is
+    not read there)."""
+    assert valid.numel() >= B
+    _call("scl_bn_eval_masked", _p(x), B, H, W, C, _p(gamma), _p(beta), _p(running_mean), _p(running_var), eps, act, _p(_klen(valid)), _p(mean),
+          _p(rstd), _p(y), _stream())
+
+
 def bn_bwd(dy, y, x, mean, rstd, gamma, N, C, act, training, part, sums, dgamma, dbeta, dx, accumulate=False):
     _call("scl_bn_bwd", _p(dy), _p(y), _p(x), _p(mean), _p(rstd), _p(gamma), N, C, act, 1 if training else 0, _p(part), _p(sums), _p(dgamma),
           _p(dbeta), _p(dx), 1 if accumulate else 0, _stream())
@@ -827,6 +835,12 @@ def maxpool3_bwd(dy, idx, H, W_, B, dx, xs_h, xs_w, xs_b):
 
 def avgpool_fwd(x, B, R, C, y):
     _call("scl_avgpool_fwd", _p(x), B, R, C, _p(y), _stream())
+
+
+def avgpool_fwd_masked(x, valid, B, H, W, C, y):
+    """y[b] = mean of x[b] over the rows h < valid[b] (and all of W): avgpool_fwd's bits for that slice alone."""
+    assert valid.numel() >= B
+    _call("scl_avgpool_fwd_masked", _p(x), _p(_klen(valid)), B, H, W, C, _p(y), _stream())
 
 
 def avgpool_bwd(dy, B, R, C, dx):

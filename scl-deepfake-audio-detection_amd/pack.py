@@ -346,7 +346,8 @@ def pad_eval(x, padding_type, max_len=64600):
 
 
 # Variable-length scoring (main.py --eval --padding_type none): whole utterances, batched by length.
-VARLEN_MIN_SAMPLES = 400          # the shortest clip the XLS-R conv stack turns into a frame; shorter files are zero-padded to it
+VARLEN_MIN_SAMPLES = 400          # the shortest clip the XLS-R conv stack turns into a frame; shorter files are zero-padded to it (EvalDataset.min_samples:
+                                  # a model whose back-end needs more says so, 17,680 samples = 55 frames for the ResNet plugin)
 VARLEN_MAX_SAMPLES = 960000       # 60 s at 16 kHz; longer files are cut
 VARLEN_QUANTUM = 16000            # padded batch lengths are multiples of this: few distinct shapes, at most 1 s of padding on the longest row
 VARLEN_WINDOW = 16                # utterances are sorted by length inside windows of VARLEN_WINDOW * batch_size consecutive ones
@@ -507,6 +508,7 @@ class EvalDataset(Dataset):
         self.cut = 64600
         self.padding_type = padding_type      # "zero" / "repeat": cut or pad to self.cut; "none": the waveform at its own length
         self.n_cut = 0                        # "none": files longer than VARLEN_MAX_SAMPLES that were cut
+        self.min_samples = VARLEN_MIN_SAMPLES     # "none": shorter files are zero-padded to it (main.py sets the model's own minimum)
         self._cut_lock = threading.Lock()
 
     def __len__(self):
@@ -521,8 +523,8 @@ class EvalDataset(Dataset):
                 x = x[:VARLEN_MAX_SAMPLES]
                 with self._cut_lock:
                     self.n_cut += 1
-            elif x.shape[0] < VARLEN_MIN_SAMPLES:
-                x = np.concatenate([x, np.zeros(VARLEN_MIN_SAMPLES - x.shape[0], dtype=np.float32)])
+            elif x.shape[0] < self.min_samples:
+                x = np.concatenate([x, np.zeros(self.min_samples - x.shape[0], dtype=np.float32)])
             return torch.from_numpy(np.ascontiguousarray(x)), utt_id
         return torch.from_numpy(np.ascontiguousarray(pad_eval(x, self.padding_type, self.cut), dtype=np.float32)), utt_id
 

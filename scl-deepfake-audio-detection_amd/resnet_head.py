@@ -10,6 +10,12 @@ early layers come out 10-28 % off there, so it stays opt-in), every BatchNorm + 
 parameter and buffer CONTAINERS named like the reference's state dict (resnet.layer2.0.shortcut.0.weight, ...), so its checkpoints
 load; none of their torch forwards is ever called.
 
+Variable-length scoring batches (ResNetHead.forward(feats, frames), eval mode under torch.no_grad()): only the time axis H shrinks through the
+network, so an utterance of T frames owns the first layer_rows(T) rows of every map.  In eval mode a BatchNorm is a per-element map and every
+convolution but conv5 reads BatchNorm outputs only: each BatchNorm + activation that feeds a convolution writes exact zeros (selected, not
+multiplied) at and beyond the utterance's own row count — what the convolution's zero border holds for the utterance alone — and the
+average runs over the utterance's own conv5 rows.
+
 Reference details kept: a block's shortcut convolution reads the block's BN+ReLU output (resnet.py:64-66); `_make_layer` builds a
 `downsample` module that is swallowed by *args and never registered (resnet.py:150-157) — no such keys here either; first_bn1 is
 defined and unused (wav2vec2_resnet_nll.py:38).
@@ -53,9 +59,11 @@ class ConvWeight(nn.Module):
         else:
             self.bias = None
 
-    def conv(self, x, dtype, residual=None):
-        """x [B, H, W, Ci] channels-last -> [B, OH, OW, Co] (+ residual, the block's skip connection, in the GEMM epilogue)."""
-        return hipnn.conv2d(x, self.weight, self.bias, self.stride, self.padding, dtype, x3_bwd=X3_BWD, grad_in_place=True, residual=residual)
+    def conv(self, x, dtype, residual=None, pooled=True):
+        """x [B, H, W, Ci] channels-last -> [B, OH, OW, Co] (+ residual, the block's skip connection, in the GEMM epilogue).
+        pooled=False: a variable-length scoring batch, whose staging map is not kept per geometry (hipnn.conv2d)."""
+        return hipnn.conv2d(x, self.weight, self.bias, self.stride, self.padding, dtype, x3_bwd=X3_BWD, grad_in_place=True, residual=residual,
+                            pooled=pooled)
 
 
 class _Shortcut(nn.Module):
@@ -79,11 +87,13 @@ class PreActBlock(nn.Module):
         if stride != 1 or cin != planes:
             self.shortcut = _Shortcut(cin, planes, stride)
 
-    def run(self, x, dt):
-        a = hipnn.batch_norm(x, self.bn1, hipnn.ACT_RELU, grad_in_place=True)
-        skip = getattr(self.shortcut, "0").conv(a, dt) if hasattr(self, "shortcut") else x
-        h = hipnn.batch_norm(self.conv1.conv(a, dt), self.bn2, hipnn.ACT_RELU, grad_in_place=True)
-        return self.conv2.conv(h, dt, residual=skip)
+    def run(self, x, dt, vin=None, vout=None):
+        """vin / vout: valid rows per utterance (int32 [B] on the GPU) of the block's input / output map, or None for a fixed-length batch."""
+        pooled = vin is None
+        a = hipnn.batch_norm(x, self.bn1, hipnn.ACT_RELU, grad_in_place=True, valid=vin)
+        skip = getattr(self.shortcut, "0").conv(a, dt, pooled=pooled) if hasattr(self, "shortcut") else x
+        h = hipnn.batch_norm(self.conv1.conv(a, dt, pooled=pooled), self.bn2, hipnn.ACT_RELU, grad_in_place=True, valid=vout)
+        return self.conv2.conv(h, dt, residual=skip, pooled=pooled)
 
 
 class PreActBottleneck(nn.Module):
@@ -101,12 +111,14 @@ class PreActBottleneck(nn.Module):
         if stride != 1 or cin != 4 * planes:
             self.shortcut = _Shortcut(cin, 4 * planes, stride)
 
-    def run(self, x, dt):
-        a = hipnn.batch_norm(x, self.bn1, hipnn.ACT_RELU, grad_in_place=True)
-        skip = getattr(self.shortcut, "0").conv(a, dt) if hasattr(self, "shortcut") else x
-        h = hipnn.batch_norm(self.conv1.conv(a, dt), self.bn2, hipnn.ACT_RELU, grad_in_place=True)
-        h = hipnn.batch_norm(self.conv2.conv(h, dt), self.bn3, hipnn.ACT_RELU, grad_in_place=True)
-        return self.conv3.conv(h, dt, residual=skip)
+    def run(self, x, dt, vin=None, vout=None):
+        """vin / vout as PreActBlock.run's: bn2 sits behind the 1x1 conv1 (input rows), bn3 behind the strided conv2 (output rows)."""
+        pooled = vin is None
+        a = hipnn.batch_norm(x, self.bn1, hipnn.ACT_RELU, grad_in_place=True, valid=vin)
+        skip = getattr(self.shortcut, "0").conv(a, dt, pooled=pooled) if hasattr(self, "shortcut") else x
+        h = hipnn.batch_norm(self.conv1.conv(a, dt, pooled=pooled), self.bn2, hipnn.ACT_RELU, grad_in_place=True, valid=vin)
+        h = hipnn.batch_norm(self.conv2.conv(h, dt, pooled=pooled), self.bn3, hipnn.ACT_RELU, grad_in_place=True, valid=vout)
+        return self.conv3.conv(h, dt, residual=skip, pooled=pooled)
 
 
 class _Stage(nn.Module):
@@ -130,19 +142,67 @@ class ResNet(nn.Module):
                 blocks.append(block(cin, planes, stride if j == 0 else 1))
                 cin = planes * block.expansion
             self.add_module("layer%d" % s, _Stage(blocks))
+        self.num_nodes, self.resnet_type = int(num_nodes), str(resnet_type)
         self.conv5 = ConvWeight(cin, 256, (num_nodes, 3), (1, 1), (0, 1))
         self.bn5 = nn.BatchNorm2d(256)
         self.fc = nn.Linear(256, nclasses)          # container for fc.weight / fc.bias
 
-    def run(self, x, dt):
-        """x [bz, T, 128, 1] -> (logits [bz, nclasses], emb [bz, 256])."""
-        x = hipnn.batch_norm(self.conv1.conv(x, dt), self.bn1, hipnn.ACT_RELU, grad_in_place=True)
+    def run(self, x, dt, rows=None):
+        """x [bz, T, 128, 1] -> (logits [bz, nclasses], emb [bz, 256]).
+        rows: int32 [N_LEVELS, bz] on the GPU, layer_rows() of every utterance of a zero-padded variable-length batch (level 0, the frames, is
+        the caller's: x is masked already); None for a fixed-length batch."""
+        lv = (lambda i: None) if rows is None else (lambda i: rows[i])
+        pooled = rows is None
+        x = hipnn.batch_norm(self.conv1.conv(x, dt, pooled=pooled), self.bn1, hipnn.ACT_RELU, grad_in_place=True, valid=lv(1))
         for s in (1, 2, 3, 4):
-            for blk in getattr(self, "layer%d" % s).children():
-                x = blk.run(x, dt)
-        x = hipnn.batch_norm(self.conv5.conv(x, dt), self.bn5, hipnn.ACT_RELU, grad_in_place=True)          # [bz, H', W', 256]
-        emb = hipnn.avg_pool_rows(x.reshape(x.shape[0], -1, x.shape[-1]))
+            for j, blk in enumerate(getattr(self, "layer%d" % s).children()):
+                x = blk.run(x, dt, lv(s if j == 0 else s + 1), lv(s + 1))      # a stage's first block takes the map of the stage before
+        x = hipnn.batch_norm(self.conv5.conv(x, dt, pooled=pooled), self.bn5, hipnn.ACT_RELU, grad_in_place=True, valid=lv(6))          # [bz, H', W', 256]
+        if rows is None:
+            emb = hipnn.avg_pool_rows(x.reshape(x.shape[0], -1, x.shape[-1]))
+        else:
+            emb = hipnn.avg_pool_rows_masked(x, rows[6])
         return hipnn.linear(emb, self.fc.weight, self.fc.bias), emb
+
+
+N_LEVELS = 7      # frames, conv1, layer1 .. layer4, conv5
+_STAGE_STRIDES = (1, 2, 2, 2)
+
+
+def layer_rows(frames, resnet_type="18", num_nodes=3):
+    """Rows (the time axis) of every map of the network for an utterance of `frames` LL frames: [frames, conv1, layer1, layer2, layer3, layer4,
+    conv5].  conv1 is 9 tall with stride 3 and padding 1; a stage's first block is 3 tall with its stage's stride and padding 1 (the 1x1
+    strided shortcut gives the same count), every other convolution of a stage keeps the rows — whatever the block kind and the block
+    counts, so `resnet_type` only has to name a network; conv5 is num_nodes tall without padding.  The last count is < 1 for an utterance
+    the network cannot take."""
+    if str(resnet_type) not in STAGES:
+        raise ValueError("resnet_type %r: one of %s" % (resnet_type, sorted(STAGES)))
+    t = int(frames)
+    h = (t + 2 - 9) // 3 + 1 if t >= 7 else 0
+    out = [t, h]
+    for stride in _STAGE_STRIDES:
+        h = (h - 1) // stride + 1 if h >= 1 else 0
+        out.append(h)
+    out.append(h - int(num_nodes) + 1)
+    return out
+
+
+def min_frames(resnet_type="18", num_nodes=3):
+    """The fewest LL frames that leave conv5 an output row (55 for num_nodes 3): the row counts never decrease with the frames."""
+    t = 7
+    while layer_rows(t, resnet_type, num_nodes)[-1] < 1:
+        t += 1
+    return t
+
+
+def batch_rows(frames, resnet_type="18", num_nodes=3):
+    """Host-side frame counts of a batch -> [N_LEVELS][B] row counts (one small int32 upload holds them all).  ValueError below min_frames."""
+    lo = min_frames(resnet_type, num_nodes)
+    frames = [int(t) for t in frames]
+    if not frames or min(frames) < lo:
+        raise ValueError("ResNet back-end: every utterance needs at least %d frames (conv5 has no output row below), got %r" % (lo, frames))
+    per = [layer_rows(t, resnet_type, num_nodes) for t in frames]
+    return [[p[i] for p in per] for i in range(N_LEVELS)]
 
 
 class ResNetHead(nn.Module):
@@ -154,6 +214,19 @@ class ResNetHead(nn.Module):
         self.first_bn1 = nn.BatchNorm2d(64)      # defined, never used (wav2vec2_resnet_nll.py:38): state-dict compatibility
         self.resnet = ResNet(**(cfg or DEFAULT_RESNET))
 
-    def forward(self, feats):
-        x = hipnn.batch_norm(feats.unsqueeze(-1), self.first_bn, hipnn.ACT_SELU, grad_in_place=True)       # the [bz, 1, T, 128] map, channels last
-        return self.resnet.run(x, _conv_dtype())
+    def forward(self, feats, frames=None):
+        """frames: host-side frame counts (a list of ints, one per row of a zero-padded batch, each in min_frames()..T) — a scoring mode:
+        eval under torch.no_grad().  feats rows at or beyond an utterance's frames are not interpreted.  None: a fixed-length batch."""
+        rows = None
+        if frames is not None:
+            if self.training or torch.is_grad_enabled():
+                raise NotImplementedError("ResNetHead.forward(feats, frames) is a scoring mode: model.eval() under torch.no_grad()")
+            frames = [int(t) for t in frames]
+            if len(frames) != feats.shape[0] or max(frames) > feats.shape[1]:
+                raise ValueError("frames: need one count in %d..%d per row of the %r batch, got %r"
+                                 % (min_frames(self.resnet.resnet_type, self.resnet.num_nodes), feats.shape[1], tuple(feats.shape), frames))
+            host = torch.tensor(batch_rows(frames, self.resnet.resnet_type, self.resnet.num_nodes), dtype=torch.int32)
+            rows = host.pin_memory().to(feats.device, non_blocking=True)
+        x = hipnn.batch_norm(feats.unsqueeze(-1), self.first_bn, hipnn.ACT_SELU, grad_in_place=True,       # the [bz, 1, T, 128] map, channels last
+                             valid=None if rows is None else rows[0])
+        return self.resnet.run(x, _conv_dtype(), rows)
