@@ -77,6 +77,86 @@ class VarlenSets(collections.OrderedDict):
         return self[key]
 
 
+class RowLayout(collections.namedtuple("RowLayout", "frames row0 Mq", defaults=(None, None, None))):
+    """How the rows of a [B, T] batch are laid out, the host-side twin of `enum class Rows` (csrc/attn_stream_body.h): fixed (every frame of
+    every utterance counts), padded (frames: int32 [B] on the device, the valid frames of each zero-padded utterance) or packed (row0 besides:
+    int32 [B + 1] on the device, the row offsets of the valid frames back to back; Mq rows per launch, a multiple of 64, ops.packed_rows)."""
+    __slots__ = ()
+    BAD_MQ = "encoder: packed row count %d: need a multiple of 64"
+
+    def __new__(cls, frames=None, row0=None, Mq=None):
+        if (row0 is not None or Mq is not None) and frames is None:
+            raise ValueError("encoder: packed=(row0, Mq) needs the frame counts of the batch (frames)")
+        if Mq is not None and int(Mq) % 64:
+            raise ValueError(cls.BAD_MQ % Mq)
+        return super().__new__(cls, frames, row0, None if Mq is None else int(Mq))
+
+    @classmethod
+    def of(cls, frames, packed):
+        """From the arguments of Encoder.forward / forward_f32: frames, packed=(row0, Mq)."""
+        return cls(frames, *(packed if packed is not None else ()))
+
+    fixed = property(lambda self: self.frames is None)
+    padded = property(lambda self: self.frames is not None and self.Mq is None)
+    packed = property(lambda self: self.Mq is not None)
+
+    @property
+    def args(self):
+        """The layout as Encoder.forward / forward_f32 take it."""
+        return dict(frames=self.frames, packed=(self.row0, self.Mq) if self.packed else None)
+
+    def check(self, B, T):
+        """The packed row count against the shape of the batch: B <= Mq <= roundup(B * T, 64)."""
+        cap = (B * T + 63) // 64 * 64
+        if self.packed and not B <= self.Mq <= cap:
+            raise ValueError((self.BAD_MQ + " in %d..%d") % (self.Mq, B, cap))
+
+    def rows(self, M):
+        """The rows the transformer layers run over, of the M = B * T of the padded rectangle."""
+        return self.Mq if self.packed else M
+
+    def key(self, B, L):
+        """Of the buffer set / state of a [B, L] batch: the packed layout has a set of its own."""
+        return (B, L, "packed") if self.packed else (B, L)
+
+    def plan_key(self, *base):
+        """Of a recorded launch plan: one plan per packed row count."""
+        return base + (self.Mq,) if self.packed else base
+
+
+FIXED = RowLayout()
+
+
+def row_layout(cfg, lengths, B, L, *, min_samples, refuse_short, score_f32, device):
+    """Sample counts of a zero-padded [B, L] batch -> (frame counts, a list of ints validated on the host; the RowLayout with the counts
+    uploaded to `device`).  A row below min_samples: counted as min_samples (refuse_short=False: its zero padding is part of the signal, as
+    for a file padded on disk) or an error (refuse_short=True: a back-end that would have to take the padding as signal throughout).
+    Packed when the switch of the precision is on, read at call time: SCORE_PACK for fp32 scoring (score_f32), else VARLEN_PACK."""
+    lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+    need = "lengths: need one sample count in 1..%d per row of the [%d, %d] batch" % (L, B, L)
+    bad = len(lengths) != B or any(n < 1 or n > L for n in lengths)
+    if refuse_short:
+        if bad:
+            raise ValueError("%s, got %r" % (need, lengths))
+        if any(n < min_samples for n in lengths):
+            raise ValueError("lengths: this back-end needs at least %d samples (%d frames) per row, got %r; zero-pad shorter utterances "
+                             "to %d samples" % (min_samples, cfg.conv_lens(min_samples)[-1], lengths, min_samples))
+    elif bad or L < min_samples:
+        raise ValueError("%s (at least %d samples per row), got %r" % (need, min_samples, lengths))
+    T = cfg.conv_lens(L)[-1]
+    counts = ops.check_lengths([cfg.conv_lens(max(n, min_samples))[-1] for n in lengths], T)
+    device = torch.device(device)
+
+    def upload(values):
+        host = torch.tensor(values, dtype=torch.int32)
+        return (host.pin_memory() if device.type == "cuda" else host).to(device, non_blocking=True)
+    frames, row0, Mq = upload(counts), None, None
+    if SCORE_PACK if score_f32 else VARLEN_PACK:
+        row0, Mq = ops.packed_rows(counts, T, PACK_ROWS)
+        row0 = upload(row0)
+    return counts, RowLayout(frames, row0, Mq)
+
+
 class W2VConfig:
     def __init__(self, conv_dim=512, conv_kernels=(10, 3, 3, 3, 3, 2, 2), conv_strides=(5, 2, 2, 2, 2, 2, 2), embed=1024,
                  layers=24, heads=16, ffn=4096, pos_k=128, pos_groups=16, final_dim=768, latent_vars=320, latent_groups=2,
@@ -247,24 +327,25 @@ class Encoder:
         return self.P.f32(self.n(name))
 
     # ---- buffers ---------------------------------------------------------------------------------
-    def bufs(self, B, L, varlen=False, train=False, packed=False):
-        """The buffer set of a [B, L] batch.  varlen: the set of a variable-length batch — streaming attention whatever T is (lse,
-        attn_ws, no T x T buffers); a scoring batch's lives in the LRU, a training batch's (train: its saved activations wait for the
-        backward) is kept.  packed: the set of the packed layout, a set of its own under the key (B, L, "packed") — one per padded shape,
-        sized for roundup(B * T, 64) rows whatever the step's lengths are."""
-        key = (B, L, "packed") if packed else (B, L)
-        if varlen and train:
-            if key not in self._vbufs_train:
-                self._vbufs_train[key] = self._make_bufs(B, L, True, packed)
-            return self._vbufs_train[key]
-        if varlen:
-            return self._vbufs.get_or_make(key, lambda: self._make_bufs(B, L, True, packed))
-        key = (B, L)
-        if key not in self._bufs:
-            self._bufs[key] = self._make_bufs(B, L, False)
-        return self._bufs[key]
+    def _set(self, key, make, layout, train=False, f32=False):
+        """The buffer set under `key`, made on first use, in the store of its kind: a fixed shape's is kept for ever (_bufs); a variable-length
+        scoring batch's lives in the LRU of its precision (_vbufs, _vbufs_f32); a variable-length training batch's (train: its saved activations
+        wait for the backward) is kept (_vbufs_train)."""
+        if not layout.fixed and not train:
+            return (self._vbufs_f32 if f32 else self._vbufs).get_or_make(key, make)
+        store = self._bufs if layout.fixed else self._vbufs_train
+        if key not in store:
+            store[key] = make()
+        return store[key]
 
-    def _make_bufs(self, B, L, varlen, packed=False):
+    def bufs(self, B, L, layout=FIXED, train=False):
+        """The buffer set of a [B, L] batch on the bf16 path.  A variable-length batch's runs the streaming attention whatever T is (lse,
+        attn_ws, no T x T buffers); the packed layout's is a set of its own (layout.key) — one per padded shape, sized for roundup(B * T, 64)
+        rows whatever the step's lengths are."""
+        return self._set(layout.key(B, L), lambda: self._make_bufs(B, L, layout), layout, train)
+
+    def _make_bufs(self, B, L, layout):
+        varlen, packed = not layout.fixed, layout.packed
         cfg, dev = self.cfg, self.dev
         C, E, H, Fd, K = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k
         Ts = cfg.conv_lens(L)
@@ -502,6 +583,86 @@ class Encoder:
         part, out, nparts, width, out2, split = (self._ln_job(d["ln_part"], nparts, C, wname, bname, resid_bias) + (None, 0))[:6]
         ops.colreduce_seg(part, out, nparts, width, out2=out2, split=split)
 
+    # ---- attention: the path of a layer, by row layout and buffer set ---------------------------------
+    def _attn_fwd(self, d, n, layout, B, training, p_attn, seed, slots):
+        """qkv[n] -> ctx[n] (and lse[n], or P[n]).  With attention dropout the launch that carries `seed` leaves its slot in `slots`."""
+        E, H = self.cfg.embed, self.cfg.heads
+        D, T, Tp = E // H, d["T"], d["Tp"]
+        qkv, ctx, sc = d["qkv"][n], d["ctx"][n], (E // H) ** -0.5
+        e = pos = None
+        if layout.packed and p_attn > 0:
+            e = ops.attn_fwd_packed_drop(qkv, ctx, d["lse"][n], layout.row0, B, T, H, D, layout.Mq, sc, drop_p=p_attn, drop_seed=seed)
+            pos = ops.ATTN_FWD_PACKED_SEED
+        elif layout.packed:
+            ops.attn_fwd_packed(qkv, ctx, d["lse"][n], layout.row0, B, T, H, D, layout.Mq, sc)
+        elif layout.padded and p_attn > 0:
+            e = ops.attn_fwd_varlen_drop(qkv, ctx, d["lse"][n], layout.frames, B, T, H, D, sc, drop_p=p_attn, drop_seed=seed)
+            pos = ops.ATTN_FWD_VARLEN_SEED
+        elif layout.padded:
+            ops.attn_fwd_varlen(qkv, ctx, d["lse"][n], layout.frames, B, T, H, D, sc)
+        elif d["fused_attn"] and ATTN_FP8 and not training and T <= 256:
+            ops.attn_fwd_fp8(qkv, ctx, d["lse"][n], B, T, H, D, sc)      # configs[4]'s fp8 attention (opt-in, no-grad forward)
+        elif d["fused_attn"]:
+            e, pos = ops.attn_fwd(qkv, ctx, d["lse"][n], B, T, H, D, sc, drop_p=p_attn, drop_seed=seed), ops.ATTN_FWD_SEED
+        elif d["long_attn"]:
+            e, pos = ops.attn_fwd_long(qkv, ctx, d["lse"][n], B, T, H, D, sc, drop_p=p_attn, drop_seed=seed), ops.ATTN_FWD_LONG_SEED
+        else:
+            ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=E), d["S"], T, T, D,
+                     nb1=B, nb2=H, alpha=sc, ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
+            ops.softmax_fwd(d["S"], d["P"][n], B * H * T, T, Tp, Tp)
+            Pv = d["P"][n]
+            if p_attn > 0:      # attention dropout: the dropped copy feeds P V (the backward rebuilds it from P and the seed)
+                Pv = d["dS"]
+                e, pos = ops.dropout_rows(d["P"][n], Pv, B * H * T, T, Tp, seed, p_attn), ops.DROPOUT_ROWS_SEED
+            ops.gemm(Op(Pv, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=2 * E),
+                     ctx, T, D, T, b_t=True, nb1=B, nb2=H, ldc=E, c_bs1=T * E, c_bs2=D)
+        if p_attn > 0:
+            self._slot(slots, e, pos, n, self.SITE_ATTN)
+
+    def _attn_bwd(self, d, n, layout, B, dqkv, p_attn, seed, slots, jobs):
+        """d_ctx -> dqkv, every row of it written (beyond an utterance's frames, and in the packed tail [row0[B], Mq), as 0).  Seed slots as in
+        _attn_fwd.  The fused kernel leaves per-utterance column sums for the q/k/v bias gradients: their reduction joins `jobs`; on the other
+        paths the caller's colsum_reduce over dqkv gives them."""
+        E, H = self.cfg.embed, self.cfg.heads
+        D, T, Tp = E // H, d["T"], d["Tp"]
+        qkv, sc = d["qkv"][n], (E // H) ** -0.5
+        drop = dict(drop_p=p_attn, drop_seed=seed)
+        if layout.packed:
+            e = ops.attn_bwd_packed(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], layout.row0, dqkv, d["attn_ws"], B, T, H, D, layout.Mq, sc, **drop)
+            pos = ops.ATTN_BWD_PACKED_SEED
+        elif layout.padded:
+            e = ops.attn_bwd_varlen(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], layout.frames, dqkv, d["attn_ws"], B, T, H, D, sc, **drop)
+            pos = ops.ATTN_BWD_VARLEN_SEED
+        elif d["fused_attn"]:
+            e = ops.attn_bwd(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], dqkv, B, T, H, D, sc, bias_part=d["qkv_bias_part"], **drop)
+            pos = ops.ATTN_BWD_SEED
+            jobs.append((d["qkv_bias_part"], self._qkv_view("encoder.layers.%d." % n, "bias"), B, 3 * E))
+        elif d["long_attn"]:
+            e, pos = ops.attn_bwd_long(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], dqkv, d["attn_ws"], B, T, H, D, sc, **drop), ops.ATTN_BWD_LONG_SEED
+        else:
+            Pn = Pv = d["P"][n]
+            bq = dict(nb1=B, nb2=H)
+            if p_attn > 0:      # the dropped probabilities, rebuilt from P with the forward's seed
+                Pv = d["dS"]
+                self._slot(slots, ops.dropout_rows(Pn, Pv, B * H * T, T, Tp, seed, p_attn), ops.DROPOUT_ROWS_SEED, n, self.SITE_ATTN)
+            # dV[j] = sum_i (P o mask)[i][j] dctx[i]
+            ops.gemm(Op(Pv, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(d["d_ctx"], E, bs1=T * E, bs2=D), dqkv, T, D, T, a_t=True, b_t=True,
+                     ldc=3 * E, c_bs1=T * 3 * E, c_bs2=D, c_offset=2 * E, **bq)
+            # dP = (dctx V^T) o mask
+            ops.gemm(Op(d["d_ctx"], E, bs1=T * E, bs2=D), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=2 * E), d["S"], T, T, D,
+                     ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp, **bq)
+            e, pos = None, ops.DROPOUT_ROWS_SEED
+            if p_attn > 0:
+                e = ops.dropout_rows(d["S"], d["S"], B * H * T, T, Tp, seed, p_attn)
+            ops.softmax_bwd(Pn, d["S"], d["dS"], B * H * T, T, Tp, Tp)
+            dS = Op(d["dS"], Tp, bs1=H * T * Tp, bs2=T * Tp)
+            ops.gemm(dS, Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=E), dqkv, T, D, T, b_t=True, alpha=sc, ldc=3 * E,
+                     c_bs1=T * 3 * E, c_bs2=D, c_offset=0, **bq)                                   # dQ = s dS K
+            ops.gemm(dS, Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=0), dqkv, T, D, T, a_t=True, b_t=True, alpha=sc, ldc=3 * E,
+                     c_bs1=T * 3 * E, c_bs2=D, c_offset=E, **bq)                                   # dK = s dS^T Q
+        if p_attn > 0:
+            self._slot(slots, e, pos, n, self.SITE_ATTN)
+
     # ---- forward ---------------------------------------------------------------------------------
     def forward(self, x, training=True, refresh=True, step_seed=0, frames=None, grad=None, packed=None):
         """x [B, L] fp32 contiguous on the GPU -> (enc_out bf16 [B*T, E], ctx).  step_seed: seed of this step's element-dropout masks.
@@ -519,8 +680,9 @@ class Encoder:
         pack writes them), every kernel but the attention works row by row and keeps them finite, and the attention writes zeros there."""
         cfg, P = self.cfg, self.P
         B, L = x.shape
+        layout = RowLayout.of(frames, packed)
         grad = torch.is_grad_enabled() if grad is None else bool(grad)
-        if frames is not None and training and not grad:
+        if not layout.fixed and training and not grad:
             raise NotImplementedError("encoder: per-utterance frame counts without a backward are a scoring mode (training=False, "
                                       "torch.no_grad()); with training=True they need autograd on")
         p_res, p_attn, p_act, p_in = self.drop_probs(training)
@@ -529,18 +691,13 @@ class Encoder:
         recording = ops._rec() is not None
         if refresh:
             self.refresh_weights()
-        if packed is not None and frames is None:
-            raise ValueError("encoder: packed=(row0, Mq) needs the frame counts of the batch (frames)")
-        d = self.bufs(B, L, varlen=frames is not None, train=grad, packed=packed is not None)
+        d = self.bufs(B, L, layout, train=grad)
         C, E, H, Fd, K, G = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k, cfg.pos_groups
         D, Cg = E // H, E // G
         Ts, T, M, Tp = d["Ts"], d["T"], d["M"], d["Tp"]
-        Mt, xin0 = M, d["xin"][0]      # rows of the transformer layers; the positional convolution's (padded) output
-        if packed is not None:
-            row0, Mt = packed
-            if Mt % 64 or not B <= Mt <= d["Mp"]:
-                raise ValueError("encoder: packed row count %d: need a multiple of 64 in %d..%d" % (Mt, B, d["Mp"]))
-            xin0 = d["xin_pad"]
+        layout.check(B, T)
+        Mt = layout.rows(M)      # rows of the transformer layers
+        xin0 = d["xin_pad"] if layout.packed else d["xin"][0]      # the positional convolution's (padded) output
         fe = "feature_extractor.conv_layers.%d."
         # -- conv stack (M1)
         ops.conv0_fwd(x, self.b(fe % 0 + "0.weight"), self.b(fe % 0 + "0.bias"), self.b(fe % 0 + "2.1.weight"),
@@ -558,8 +715,8 @@ class Encoder:
         if p_in > 0 and recording:
             self._slot(slots, dsc, None, -1, self.SITE_IN)
         # -- positional conv (grouped, weight-normed), GELU, residual (M2 head)
-        if frames is not None:
-            ops.zero_tail_rows(d["x0"], frames, B, T, E)      # fairseq: features[padding_mask] = 0
+        if not layout.fixed:
+            ops.zero_tail_rows(d["x0"], layout.frames, B, T, E)      # fairseq: features[padding_mask] = 0
         ops.pad_rows(d["x0"], d["xpad"], B, T, E, T + K, K // 2)
         if ops.posconv_supported(T, K, G, Cg):      # utterance slab resident in LDS, weights streamed (csrc/posconv.hip); else the grouped GEMM
             ops.posconv_mfma(d["xpad"], self.pos_wf, xin0, d["x0"], B, T, K, G, Cg, bias=self.b("encoder.pos_conv.0.bias"), c2=d["pc_pre"])
@@ -569,8 +726,8 @@ class Encoder:
                      act=ACT_GELU, c2=d["pc_pre"], R=d["x0"], rmode=1)
         if p_res > 0:      # F.dropout(x + pos_conv(x), p = cfg.dropout): after the residual add, so not a GEMM epilogue
             self._slot(slots, ops.dropout(xin0, xin0, None, M * E, sseed(-1, self.SITE_ENC), p_res), ops.DROPOUT_SEED, -1, self.SITE_ENC)
-        if packed is not None:      # valid frames back to back, rows [row0[B], Mt) zero
-            ops.pack_rows(xin0, d["xin"][0], row0, B, T, E, Mt)
+        if layout.packed:      # valid frames back to back, rows [row0[B], Mt) zero
+            ops.pack_rows(xin0, d["xin"][0], layout.row0, B, T, E, Mt)
         # -- transformer layers
         skipped = []
         for n in range(cfg.layers):
@@ -584,39 +741,7 @@ class Encoder:
                               d["h1"][n], None, d["m1"][n], d["r1"][n], Mt, E)
             ops.gemm(Op(d["h1"][n], E), self.W(pn + "self_attn.q_proj.weight", E), d["qkv"][n], Mt, 3 * E, E,
                      bias=self.b(pn + "self_attn.q_proj.bias"))  # q,k,v biases are adjacent in the flat buffer
-            qkv = d["qkv"][n]
-            if packed is not None and p_attn > 0:
-                e = ops.attn_fwd_packed_drop(qkv, d["ctx"][n], d["lse"][n], row0, B, T, H, D, Mt, D ** -0.5, drop_p=p_attn,
-                                             drop_seed=sseed(n, self.SITE_ATTN))
-                self._slot(slots, e, ops.ATTN_FWD_PACKED_SEED, n, self.SITE_ATTN)
-            elif packed is not None:
-                ops.attn_fwd_packed(qkv, d["ctx"][n], d["lse"][n], row0, B, T, H, D, Mt, D ** -0.5)
-            elif frames is not None and p_attn > 0:
-                e = ops.attn_fwd_varlen_drop(qkv, d["ctx"][n], d["lse"][n], frames, B, T, H, D, D ** -0.5, drop_p=p_attn,
-                                             drop_seed=sseed(n, self.SITE_ATTN))
-                self._slot(slots, e, ops.ATTN_FWD_VARLEN_SEED, n, self.SITE_ATTN)
-            elif frames is not None:
-                ops.attn_fwd_varlen(qkv, d["ctx"][n], d["lse"][n], frames, B, T, H, D, D ** -0.5)
-            elif d["fused_attn"] and ATTN_FP8 and not training and T <= 256:
-                ops.attn_fwd_fp8(qkv, d["ctx"][n], d["lse"][n], B, T, H, D, D ** -0.5)      # configs[4]'s fp8 attention (opt-in, no-grad forward)
-            elif d["fused_attn"]:
-                e = ops.attn_fwd(qkv, d["ctx"][n], d["lse"][n], B, T, H, D, D ** -0.5, drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
-                if p_attn > 0:
-                    self._slot(slots, e, ops.ATTN_FWD_SEED, n, self.SITE_ATTN)
-            elif d["long_attn"]:
-                e = ops.attn_fwd_long(qkv, d["ctx"][n], d["lse"][n], B, T, H, D, D ** -0.5, drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
-                if p_attn > 0:
-                    self._slot(slots, e, ops.ATTN_FWD_LONG_SEED, n, self.SITE_ATTN)
-            else:
-                ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=E), d["S"], T, T, D,
-                         nb1=B, nb2=H, alpha=D ** -0.5, ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
-                ops.softmax_fwd(d["S"], d["P"][n], B * H * T, T, Tp, Tp)
-                Pv = d["P"][n]
-                if p_attn > 0:      # attention dropout: the dropped copy feeds P V (the backward rebuilds it from P and the seed)
-                    Pv = d["dS"]
-                    self._slot(slots, ops.dropout_rows(d["P"][n], Pv, B * H * T, T, Tp, sseed(n, self.SITE_ATTN), p_attn), ops.DROPOUT_ROWS_SEED, n, self.SITE_ATTN)
-                ops.gemm(Op(Pv, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=2 * E),
-                         d["ctx"][n], T, D, T, b_t=True, nb1=B, nb2=H, ldc=E, c_bs1=T * E, c_bs2=D)
+            self._attn_fwd(d, n, layout, B, training, p_attn, sseed(n, self.SITE_ATTN), slots)
             dsc = ops.gemm(Op(d["ctx"][n], E), self.W(pn + "self_attn.out_proj.weight", E), d["x1"][n], Mt, E, E,
                            bias=self.b(pn + "self_attn.out_proj.bias"), R=xin, rmode=1, drop_p=p_res, drop_seed=sseed(n, self.SITE_1))    # dropout1
             if p_res > 0 and recording:
@@ -636,11 +761,11 @@ class Encoder:
         ops.layernorm_fwd(d["xin"][cfg.layers], self.b("encoder.layer_norm.weight"), self.b("encoder.layer_norm.bias"),
                           d["out"], None, d["omean"], d["orstd"], Mt, E)
         out = d["out"]
-        if packed is not None:      # back to the padded [B*T, E] rectangle, zero rows beyond each utterance
+        if layout.packed:      # back to the padded [B*T, E] rectangle, zero rows beyond each utterance
             out = d["out_pad"]
-            ops.unpack_rows(d["out"], out, row0, B, T, E, Mt)
+            ops.unpack_rows(d["out"], out, layout.row0, B, T, E, Mt)
         return out, {"d": d, "x": x, "B": B, "L": L, "skipped": skipped, "drop": (p_res, p_attn, p_act, p_in), "step_seed": step_seed,
-                     "drop_slots": slots, "frames": frames, "packed": packed}
+                     "drop_slots": slots, "layout": layout}
 
     # ---- fp32 scoring forward ----------------------------------------------------------------------
     def _f32_weights(self):
@@ -686,46 +811,33 @@ class Encoder:
         Ts = cfg.conv_lens(L)
         T = Ts[-1]
         M, Tp = B * T, (T + 7) // 8 * 8
-        Mt, Mp = M, (M + 63) // 64 * 64      # rows of the transformer layers; the packed set's capacity
-        if packed is None:
-            # above 512 frames the attention runs in chunks of `bc` utterances (S / Pm sized per chunk, <= F32_ATTN_CHUNK_BYTES)
-            long_attn = T > MAT_ATTN_MAX_T
-            bc = max(1, min(B, F32_ATTN_CHUNK_BYTES // (4 * H * T * Tp))) if long_attn else B
-            key = ("f32", B, L) if not long_attn else ("f32", B, L, bc)
-        else:
-            if frames is None:
-                raise ValueError("encoder: packed=(row0, Mq) needs the frame counts of the batch (frames)")
-            if D != 64:
-                raise NotImplementedError("encoder: SCL_SCORE_PACK=1 needs 64-wide attention heads (this encoder's are %d wide): the "
-                                          "packed fp32 attention kernel takes head dim 64 only" % D)
-            row0, Mt = packed
-            if Mt % 64 or not B <= Mt <= Mp:
-                raise ValueError("encoder: packed row count %d: need a multiple of 64 in %d..%d" % (Mt, B, Mp))
-            key = ("f32", B, L, "packed")
-        nstat = max(B * Ts[1], Mp if packed is not None else 0)      # LayerNorm statistics: the widest row count of the path
+        layout = RowLayout.of(frames, packed)
+        layout.check(B, T)
+        Mt, Mp = layout.rows(M), (M + 63) // 64 * 64      # rows of the transformer layers; the packed set's capacity
+        # above 512 frames the materialised attention runs in chunks of `bc` utterances (S / Pm sized per chunk, <= F32_ATTN_CHUNK_BYTES)
+        long_attn = T > MAT_ATTN_MAX_T and not layout.packed
+        bc = max(1, min(B, F32_ATTN_CHUNK_BYTES // (4 * H * T * Tp))) if long_attn else B
+        if layout.packed and D != 64:
+            raise NotImplementedError("encoder: SCL_SCORE_PACK=1 needs 64-wide attention heads (this encoder's are %d wide): the "
+                                      "packed fp32 attention kernel takes head dim 64 only" % D)
+        R = Mp if layout.packed else M      # row capacity of the layer buffers: every packed row count of the shape
+        nstat = max(B * Ts[1], R)      # LayerNorm statistics: the widest row count of the path
 
         def make():
             f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.dev)
             slack = 128 * max(C, E)
-            if packed is not None:      # layer buffers of Mp rows (every packed row count of the shape), no score buffers
-                return dict(z=[f32(B * t * C + slack) for t in Ts], y=f32(B * Ts[1] * C), stat=f32(2 * nstat), h=f32(Mp * max(C, E) + slack),
-                            x0=f32(M * E), xpad=torch.zeros(B * (T + K) * E + slack, device=self.dev), xa=f32(Mp * E), xb=f32(Mp * E),
-                            x1=f32(Mp * E), qkv=f32(Mp * 3 * E + slack), ctx=f32(Mp * E + slack), a=f32(Mp * Fd + slack), out=f32(Mp * E),
-                            out_pad=f32(M * E),
-                            a3=torch.empty(Mp * 3 * max(C, E, Fd) + 2 * slack, dtype=torch.bfloat16, device=self.dev),
-                            a3b=torch.empty(Mp * 3 * Fd + 2 * slack, dtype=torch.bfloat16, device=self.dev))
-            return dict(z=[f32(B * t * C + slack) for t in Ts], y=f32(B * Ts[1] * C), stat=f32(2 * B * Ts[1]), h=f32(M * max(C, E) + slack),
-                                   x0=f32(M * E), xpad=torch.zeros(B * (T + K) * E + slack, device=self.dev), xa=f32(M * E), xb=f32(M * E),
-                                   x1=f32(M * E), qkv=f32(M * 3 * E + slack), S=f32(bc * H * T * Tp), Pm=torch.zeros(bc * H * T * Tp + 1024, device=self.dev),
-                                   ctx=f32(M * E + slack), a=f32(M * Fd + slack), out=f32(M * E),
-                                   a3=torch.empty(M * 3 * max(C, E, Fd) + 2 * slack, dtype=torch.bfloat16, device=self.dev),
-                                   a3b=torch.empty(M * 3 * Fd + 2 * slack, dtype=torch.bfloat16, device=self.dev))
-        if frames is not None:
-            d = self._vbufs_f32.get_or_make(key, make)
-        else:
-            if key not in self._bufs:
-                self._bufs[key] = make()
-            d = self._bufs[key]
+            d = dict(z=[f32(B * t * C + slack) for t in Ts], y=f32(B * Ts[1] * C), stat=f32(2 * nstat), h=f32(R * max(C, E) + slack),
+                     x0=f32(M * E), xpad=torch.zeros(B * (T + K) * E + slack, device=self.dev), xa=f32(R * E), xb=f32(R * E),
+                     x1=f32(R * E), qkv=f32(R * 3 * E + slack))
+            if not layout.packed:      # the score buffers of the materialised attention
+                d.update(S=f32(bc * H * T * Tp), Pm=torch.zeros(bc * H * T * Tp + 1024, device=self.dev))
+            d.update(ctx=f32(R * E + slack), a=f32(R * Fd + slack), out=f32(R * E),
+                     a3=torch.empty(R * 3 * max(C, E, Fd) + 2 * slack, dtype=torch.bfloat16, device=self.dev),
+                     a3b=torch.empty(R * 3 * Fd + 2 * slack, dtype=torch.bfloat16, device=self.dev))
+            if layout.packed:      # the padded rectangle behind the unpack
+                d["out_pad"] = f32(M * E)
+            return d
+        d = self._set(("f32",) + layout.key(B, L) + ((bc,) if long_attn else ()), make, layout, f32=True)
         fw = self._f32_weights()
         Wf = lambda name, ld: Op(P.flat, ld, offset=P.off(self.n(name)))
         # Round 6: the plain linears (flat K) as ONE bf16 GEMM over 3 K on the wide-tile kernel — left operand [hi | hi | lo] written by a
@@ -768,17 +880,17 @@ class Encoder:
         ln_then_lin(d["z"][-1], "layer_norm.weight", "layer_norm.bias", C, "post_extract_proj.weight", E, d["x0"], rows=M,
                     bias=self.b("post_extract_proj.bias"))
         # positional conv: zero-padded rows (the pad rows of xpad are never written), GELU, residual
-        if frames is not None:
-            ops.zero_tail_rows(d["x0"], frames, B, T, E)      # fairseq: features[padding_mask] = 0
+        if not layout.fixed:
+            ops.zero_tail_rows(d["x0"], layout.frames, B, T, E)      # fairseq: features[padding_mask] = 0
         d["xpad"][: B * (T + K) * E].view(B, T + K, E)[:, K // 2: K // 2 + T].copy_(d["x0"].view(B, T, E))
         xin, xout = d["xa"], d["xb"]
         ops.gemm(Op(d["xpad"], E, rpb=T, rbstride=(T + K) * E, cin=Cg, cout=E, bs2=Cg), Op(fw["pos"], K * Cg, bs2=Cg * K * Cg), xin, M, Cg, K * Cg,
                  nb2=G, ldc=E, c_bs2=Cg, bias=self.b("encoder.pos_conv.0.bias"), bias_bs2=Cg, act=ACT_GELU, R=d["x0"], rmode=1)
-        if packed is not None:      # valid frames back to back into the other ping-pong buffer, rows [row0[B], Mt) zero
-            ops.pack_rows(xin, xout, row0, B, T, E, Mt)
+        if layout.packed:      # valid frames back to back into the other ping-pong buffer, rows [row0[B], Mt) zero
+            ops.pack_rows(xin, xout, layout.row0, B, T, E, Mt)
             xin, xout = xout, xin
         qkv = d["qkv"]
-        if packed is None:
+        if not layout.packed:
             S, Pm = d["S"], d["Pm"]
             # fp32 soft-max, as fairseq: one wave per row with the row in registers up to 512 frames, the looped kernel for longer rows
             softmax = ops.softmax_fwd_f32_long if long_attn else ops.softmax_fwd_f32
@@ -786,15 +898,15 @@ class Encoder:
             pn = "encoder.layers.%d." % n
             ln_then_lin(xin, pn + "self_attn_layer_norm.weight", pn + "self_attn_layer_norm.bias", E, pn + "self_attn.q_proj.weight", 3 * E, qkv,
                         bias=self.b(pn + "self_attn.q_proj.bias"))
-            if packed is not None:      # streaming fp32 attention over the packed rows: one launch, nothing of size T^2
-                ops.attn_fwd_packed_f32(qkv, d["ctx"], row0, B, T, H, D, Mt, D ** -0.5)
+            if layout.packed:      # streaming fp32 attention over the packed rows: one launch, nothing of size T^2
+                ops.attn_fwd_packed_f32(qkv, d["ctx"], layout.row0, B, T, H, D, Mt, D ** -0.5)
             else:
                 for c0 in range(0, B, bc):      # scores, soft-max, P V per chunk of utterances (up to 512 frames: one chunk of all B)
                     nb, o3 = min(bc, B - c0), c0 * T * 3 * E
                     ops.gemm(Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + E), S, T, T, D, nb1=nb, nb2=H,
                              alpha=D ** -0.5, ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp)
-                    if frames is not None:      # keys beyond the utterance's frames take no part (any T: one entry point)
-                        ops.softmax_fwd_f32_varlen(S, Pm, frames, nb * H * T, H * T, T, Tp, Tp, klen_offset=c0)
+                    if layout.padded:      # keys beyond the utterance's frames take no part (any T: one entry point)
+                        ops.softmax_fwd_f32_varlen(S, Pm, layout.frames, nb * H * T, H * T, T, Tp, Tp, klen_offset=c0)
                     else:
                         softmax(S, Pm, nb * H * T, T, Tp, Tp)
                     ops.gemm(Op(Pm, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=o3 + 2 * E), d["ctx"], T, D, T, b_t=True,
@@ -812,8 +924,8 @@ class Encoder:
                 lin(d["a"], Fd, pn + "fc2.weight", E, xout, bias=self.b(pn + "fc2.bias"), R=d["x1"], rmode=1)
             xin, xout = xout, xin
         ops.layernorm_fwd(xin, self.b("encoder.layer_norm.weight"), self.b("encoder.layer_norm.bias"), None, d["out"], mean, rstd, Mt, E)
-        if packed is not None:      # back to the padded [B*T, E] rectangle, zero rows beyond each utterance
-            ops.unpack_rows(d["out"], d["out_pad"], row0, B, T, E, Mt)
+        if layout.packed:      # back to the padded [B*T, E] rectangle, zero rows beyond each utterance
+            ops.unpack_rows(d["out"], d["out_pad"], layout.row0, B, T, E, Mt)
             return d["out_pad"], T
         return d["out"], T
 
@@ -821,12 +933,12 @@ class Encoder:
     def backward(self, ctx, d_out):
         """d_out: bf16 or f32 [M, E] gradient w.r.t. forward()'s output.  Writes every parameter
         gradient of the encoder into the flat gradient buffer (overwrite semantics).
-        A forward with `frames` (ctx["frames"]): d_out's rows beyond an utterance's frames must be 0 (the head's masked mean pool and feats
+        A forward with `frames` (ctx["layout"] padded or packed): d_out's rows beyond an utterance's frames must be 0 (the head's masked mean pool and feats
         give that).  Two kernels then carry the mask: scl_attn_bwd_varlen writes zero dqkv rows there, and the rows of d(x0) are zeroed
         behind the positional convolution's data gradient (the backward of the forward's zero_tail_rows(x0)).  Every other kernel of the
         chain works row by row, so the gradient of a padded row is exactly 0 from the head down to the conv stack, and padded rows add
         nothing to any weight, bias or LayerNorm gradient.
-        A packed forward (ctx["packed"] = (row0, Mq)): d_out is packed, the layers run over M = Mp = Mq rows with scl_attn_bwd_packed,
+        A packed forward (row0, Mq): d_out is packed, the layers run over M = Mp = Mq rows with scl_attn_bwd_packed,
         and d(xin[0]) is unpacked into the padded buffer; everything behind it runs as above.  Inside the packed stretch there are no padded
         rows, only the tail [row0[B], Mq) that belongs to no utterance.  Going forward those rows start as zeros and stay finite through the
         row-wise kernels.  Going backward they start as exact zeros — the pack of d_out writes zeros there, scl_attn_bwd_packed writes zero
@@ -835,18 +947,17 @@ class Encoder:
         of 64: no K step reaches a stale row), and a zero gradient row times a finite activation row adds nothing to them."""
         cfg, P = self.cfg, self.P
         d, x, B, L = ctx["d"], ctx["x"], ctx["B"], ctx["L"]
-        frames, packed = ctx.get("frames"), ctx.get("packed")
+        layout = ctx["layout"]
         C, E, H, Fd, K, G = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k, cfg.pos_groups
         D, Cg = E // H, E // G
         Ts, T, M, Tp, Mp = d["Ts"], d["T"], d["M"], d["Tp"], d["Mp"]
-        Mt = M      # rows of the transformer layers
-        if packed is not None:
-            row0, Mt = packed
+        Mt = layout.rows(M)      # rows of the transformer layers
+        if layout.packed:
             Mp = Mt      # a multiple of 64
             key = "d_out_pk_f32" if d_out.dtype == torch.float32 else "d_out_pk"
             if key not in d:
                 d[key] = torch.empty(d["Mp"] * E, dtype=d_out.dtype, device=self.dev)
-            ops.pack_rows(d_out, d[key], row0, B, T, E, Mt)      # rows [row0[B], Mt): zeros
+            ops.pack_rows(d_out, d[key], layout.row0, B, T, E, Mt)      # rows [row0[B], Mt): zeros
             d_out = d[key]
         elif not (WGRAD_GROUP and Mp // 64 >= WGRAD_GROUP_MIN_KSTEPS):
             Mp = M      # short reductions stay on the split-K path, which is faster on the exact row count (pack of 11: 16.2 vs 17.6 ms per step)
@@ -920,51 +1031,8 @@ class Encoder:
             with self._side():
                 self._wgrad(d, Op(dxb, E), Op(d["ctx"][n], E), P.g(self.n(pn + "self_attn.out_proj.weight")), E, E, Mp, slot=2)
             ops.gemm(Op(dxb, E), self.W(pn + "self_attn.out_proj.weight", E), d["d_ctx"], Mt, E, E, b_t=True)
-            qkv, dqkv = d["qkv"][n], d["dqkv"][li & 1]
-            if packed is not None:      # rows of an utterance and the zero tail [row0[B], Mt) written; q/k/v bias gradients: colsum_reduce below
-                e = ops.attn_bwd_packed(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], row0, dqkv, d["attn_ws"], B, T, H, D, Mt, D ** -0.5,
-                                        drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
-                if p_attn > 0:
-                    self._slot(slots, e, ops.ATTN_BWD_PACKED_SEED, n, self.SITE_ATTN)
-            elif frames is not None:      # every row of dqkv written, rows beyond the utterance's frames as 0; q/k/v bias gradients: colsum_reduce below
-                e = ops.attn_bwd_varlen(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], frames, dqkv, d["attn_ws"], B, T, H, D, D ** -0.5,
-                                        drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
-                if p_attn > 0:
-                    self._slot(slots, e, ops.ATTN_BWD_VARLEN_SEED, n, self.SITE_ATTN)
-            elif d["fused_attn"]:
-                e = ops.attn_bwd(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], dqkv, B, T, H, D, D ** -0.5,
-                                 bias_part=d["qkv_bias_part"], drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
-                if p_attn > 0:
-                    self._slot(slots, e, ops.ATTN_BWD_SEED, n, self.SITE_ATTN)
-                # q/k/v bias gradients: per-utterance column sums out of attn_bwd's accumulators, summed over B
-                jobs.append((d["qkv_bias_part"], self._qkv_view(pn, "bias"), B, 3 * E))
-            elif d["long_attn"]:      # q/k/v bias gradients: colsum_reduce below
-                e = ops.attn_bwd_long(qkv, d["ctx"][n], d["d_ctx"], d["lse"][n], dqkv, d["attn_ws"], B, T, H, D, D ** -0.5,
-                                      drop_p=p_attn, drop_seed=sseed(n, self.SITE_ATTN))
-                if p_attn > 0:
-                    self._slot(slots, e, ops.ATTN_BWD_LONG_SEED, n, self.SITE_ATTN)
-            else:
-                Pn = d["P"][n]
-                bq = dict(nb1=B, nb2=H)
-                Pv = Pn
-                if p_attn > 0:      # the dropped probabilities, rebuilt from P with the forward's seed
-                    Pv = d["dS"]
-                    self._slot(slots, ops.dropout_rows(Pn, Pv, B * H * T, T, Tp, sseed(n, self.SITE_ATTN), p_attn), ops.DROPOUT_ROWS_SEED, n, self.SITE_ATTN)
-                # dV[j] = sum_i (P o mask)[i][j] dctx[i]
-                ops.gemm(Op(Pv, Tp, bs1=H * T * Tp, bs2=T * Tp), Op(d["d_ctx"], E, bs1=T * E, bs2=D), dqkv, T, D, T, a_t=True, b_t=True,
-                         ldc=3 * E, c_bs1=T * 3 * E, c_bs2=D, c_offset=2 * E, **bq)
-                # dP = (dctx V^T) o mask
-                ops.gemm(Op(d["d_ctx"], E, bs1=T * E, bs2=D), Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=2 * E), d["S"], T, T, D,
-                         ldc=Tp, c_bs1=H * T * Tp, c_bs2=T * Tp, **bq)
-                if p_attn > 0:
-                    self._slot(slots, ops.dropout_rows(d["S"], d["S"], B * H * T, T, Tp, sseed(n, self.SITE_ATTN), p_attn), ops.DROPOUT_ROWS_SEED, n, self.SITE_ATTN)
-                ops.softmax_bwd(Pn, d["S"], d["dS"], B * H * T, T, Tp, Tp)
-                sc = D ** -0.5
-                dS = Op(d["dS"], Tp, bs1=H * T * Tp, bs2=T * Tp)
-                ops.gemm(dS, Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=E), dqkv, T, D, T, b_t=True, alpha=sc, ldc=3 * E,
-                         c_bs1=T * 3 * E, c_bs2=D, c_offset=0, **bq)                                   # dQ = s dS K
-                ops.gemm(dS, Op(qkv, 3 * E, bs1=T * 3 * E, bs2=D, offset=0), dqkv, T, D, T, a_t=True, b_t=True, alpha=sc, ldc=3 * E,
-                         c_bs1=T * 3 * E, c_bs2=D, c_offset=E, **bq)                                   # dK = s dS^T Q
+            dqkv = d["dqkv"][li & 1]
+            self._attn_bwd(d, n, layout, B, dqkv, p_attn, sseed(n, self.SITE_ATTN), slots, jobs)
             with self._side():
                 if not d["fused_attn"]:
                     ops.colsum_reduce(dqkv, d["cs_part"], self._qkv_view(pn, "bias"), Mt, 3 * E)
@@ -995,8 +1063,8 @@ class Encoder:
             prev_off = this_off
             if self.on_grads_ready is not None and ready_off is not None:
                 ops.host_callback(self.on_grads_ready, ready_off)
-        if packed is not None:      # d(xin[0]) back to the padded rectangle (zero rows beyond each utterance): the convolution needs the slab
-            ops.unpack_rows(dx, d["dxin_pad"], row0, B, T, E, Mt)
+        if layout.packed:      # d(xin[0]) back to the padded rectangle (zero rows beyond each utterance): the convolution needs the slab
+            ops.unpack_rows(dx, d["dxin_pad"], layout.row0, B, T, E, Mt)
             dx, (other, otherb) = d["dxin_pad"], d["dx0_pad"]
         # ---- positional conv:  xin0 = x0 + gelu(conv(x0) + b)
         pb = K // 2 - 1
@@ -1020,8 +1088,8 @@ class Encoder:
             ops.gemm(Op(d["dcpad"], E, rpb=T, rbstride=(T + K) * E, cin=Cg, cout=E, bs2=Cg), Op(self.pos_wd, K * Cg, bs2=Cg * K * Cg),
                      other, M, Cg, K * Cg, nb2=G, ldc=E, c_bs2=Cg, R=dx, rmode=1)
         dx0 = other
-        if frames is not None:      # the forward zeroed x0's padded rows: no gradient flows into them (the convolution's reaches them)
-            ops.zero_tail_rows(dx0, frames, B, T, E)
+        if not layout.fixed:      # the forward zeroed x0's padded rows: no gradient flows into them (the convolution's reaches them)
+            ops.zero_tail_rows(dx0, layout.frames, B, T, E)
         if p_in > 0:       # backward of dropout_input: d(post_extract_proj output) = dx0 x mask (f32 for the bias sum, bf16 for the GEMMs)
             self._slot(slots, ops.dropout(dx0, dx0, otherb, M * E, sseed(-1, self.SITE_IN), p_in), ops.DROPOUT_SEED, -1, self.SITE_IN)
         else:

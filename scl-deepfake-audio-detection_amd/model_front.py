@@ -20,7 +20,7 @@ from torch import nn
 
 from . import encoder as ENC
 from . import ops
-from .encoder import Encoder, VarlenSets, W2VConfig, param_specs
+from .encoder import FIXED, Encoder, RowLayout, VarlenSets, W2VConfig, param_specs
 from .model_linear import SCORE_FP32, dropout_stream_seed, init_parameters_, loss_custom, maybe_load_pretrained
 from .ops import Op
 from .params import FlatParams, register_by_name
@@ -173,44 +173,77 @@ class FrontHeadModel(nn.Module):
         self.P.grad[self._head_lo:].zero_()
 
     # encoder + LL ----------------------------------------------------------------------------------
-    def _state(self, B, L):
-        key = (B, L)
-        if key not in self._states:
+    def _state(self, B, L, layout=FIXED):
+        """Boundary buffers and launch plans of a [B, L] batch.  A variable-length (scoring) batch: forward-only, with the frame counts and,
+        packed, the row offsets besides — device buffers of fixed address, overwritten before every replay; a state of its own per layout."""
+        def make():
             T = self.cfg.conv_lens(L)[-1]
             M, E, dev = B * T, self.cfg.embed, self.device
             f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
             bf = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
-            self._states[key] = dict(T=T, x=f32(B, L), feats=f32(B, T, FEAT_DIM), d_feats=f32(B, T, FEAT_DIM),
-                                     dfe_bf=bf(M * FEAT_DIM + 1024), denc=bf(M * E), cs=f32(ops.colsum_reduce_nparts(M, 8) * FEAT_DIM), plans={})
+            i32 = dict(dtype=torch.int32, device=dev)
+            st = dict(T=T, x=f32(B, L), feats=f32(B, T, FEAT_DIM), dfe_bf=bf(M * FEAT_DIM + 1024), plans={})
+            if layout.fixed:
+                st.update(d_feats=f32(B, T, FEAT_DIM), denc=bf(M * E), cs=f32(ops.colsum_reduce_nparts(M, 8) * FEAT_DIM))
+            else:
+                st.update(frames=torch.ones(B, **i32), row0=torch.arange(B + 1, **i32) if layout.packed else None)
+            return st
+        key = layout.key(B, L)
+        if not layout.fixed:
+            return self._vstates.get_or_make(key, make)
+        if key not in self._states:
+            self._states[key] = make()
         return self._states[key]
 
-    def _front_forward(self, x):
+    def _front_forward(self, x, layout=FIXED):
+        """Encoder (bf16 kernels) + LL on the shape's state, recorded once per plan key and replayed.  A variable-length batch is scored,
+        never trained on: padding mask (or packed rows) in the encoder, feats rows beyond an utterance's frames zeroed, no dropout mask drawn."""
         B, L = x.shape
-        ssl_train = self._ssl_train()
-        st = self._state(B, L)
+        ssl_train = layout.fixed and self._ssl_train()
+        st = self._state(B, L, layout)
         st["x"].copy_(x)
+        seed = 0
+        if layout.fixed:
+            self._drop_step = seed = (self._drop_step * 1664525 + 1013904223) & 0x7FFFFFFF
+        else:      # into the state's buffers, which the recorded plans read
+            st["frames"].copy_(layout.frames)
+            if layout.packed:
+                st["row0"].copy_(layout.row0)
+            layout = RowLayout(st["frames"], st["row0"], layout.Mq)
         self.ssl.refresh_weights()
         use_plan = self.cfg.encoder_layerdrop == 0 or not ssl_train
-        pk = ("fwd", ssl_train)
+        pk = layout.plan_key("fwd", ssl_train)
         plan = st["plans"].get(pk) if use_plan else None
-        self._drop_step = (self._drop_step * 1664525 + 1013904223) & 0x7FFFFFFF
         if plan is not None:
             ectx = plan["saved"]["ectx"]
-            self.ssl.apply_seeds(ectx["drop_slots"], self._drop_step)      # the encoder's element-dropout sites (none at p = 0)
+            self.ssl.apply_seeds(ectx["drop_slots"], seed)      # the encoder's element-dropout sites (none at p = 0)
             ops.replay(plan["calls"])
-            return st["feats"], dict(plan["saved"], ectx=dict(ectx, step_seed=self._drop_step))
+            return st["feats"], dict(plan["saved"], ectx=dict(ectx, step_seed=seed))
         if use_plan:
             ops.start_recording()
         P, E = self.P, self.cfg.embed
-        enc_out, ectx = self.ssl.forward(st["x"], training=ssl_train, refresh=False, step_seed=self._drop_step)
+        enc_out, ectx = self.ssl.forward(st["x"], training=ssl_train, refresh=False, step_seed=seed,
+                                         grad=None if layout.fixed else False, **layout.args)
         M = B * st["T"]
         # the bf16 primary output of the GEMM is not needed here: it lands in dfe_bf, which the backward overwrites
         ops.gemm(Op(enc_out, E), Op(P.bf16, E, offset=P.off("LL.weight")), st["dfe_bf"], M, FEAT_DIM, E, bias=P.f32("LL.bias"),
                  c2=st["feats"])
+        if not layout.fixed:
+            ops.zero_tail_rows(st["feats"], layout.frames, B, st["T"], FEAT_DIM)
         saved = dict(ectx=ectx, st=st, enc_out=enc_out, B=B)
         if use_plan:
             st["plans"][pk] = dict(calls=ops.stop_recording(), saved=saved)
         return st["feats"], saved
+
+    def _front_f32(self, x, layout=FIXED):
+        """Scoring: fp32 activations / master weights / exact-fp32 GEMMs through the encoder and LL (the back-end is fp32 anyway)."""
+        B, E = x.shape[0], self.cfg.embed
+        enc, T = self.ssl.forward_f32(x, **layout.args)
+        feats = torch.empty(B, T, FEAT_DIM, device=self.device)
+        ops.gemm(Op(enc, E), Op(self.P.flat, E, offset=self.P.off("LL.weight")), feats, B * T, FEAT_DIM, E, bias=self.P.f32("LL.bias"))
+        if not layout.fixed:
+            ops.zero_tail_rows(feats, layout.frames, B, T, FEAT_DIM)
+        return feats
 
     def _front_backward(self, sv, d_feats):
         P, E = self.P, self.cfg.embed
@@ -246,100 +279,28 @@ class FrontHeadModel(nn.Module):
                       "wav2vec2_linear_nll plugin and, for scoring, wav2vec2_resnet_nll: this back-end has no padding mask; score "
                       "fixed-length clips (--padding_type zero / repeat) or one utterance per call")
 
-    def _frame_counts(self, lengths, B, L):
-        """Sample counts of a zero-padded batch -> frame counts, a list of ints validated on the host (model_linear._frame_counts, but a
-        row below the back-end's minimum is an error: its zero padding would have to count as signal through the whole back-end)."""
-        lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        if len(lengths) != B or any(n < 1 or n > L for n in lengths):
-            raise ValueError("lengths: need one sample count in 1..%d per row of the [%d, %d] batch, got %r" % (L, B, L, lengths))
-        lo = self.min_samples()
-        if any(n < lo for n in lengths):
-            raise ValueError("lengths: this back-end needs at least %d samples (%d frames) per row, got %r; zero-pad shorter utterances "
-                             "to %d samples" % (lo, self.head_min_frames(), lengths, lo))
-        return ops.check_lengths([self.cfg.conv_lens(n)[-1] for n in lengths], self.cfg.conv_lens(L)[-1])
-
-    def _upload_i32(self, values):
-        return torch.tensor(values, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
-
-    def _varlen_state(self, B, L, packed):
-        def make():
-            T = self.cfg.conv_lens(L)[-1]
-            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
-            return dict(T=T, x=f32(B, L), feats=f32(B, T, FEAT_DIM), scratch=torch.empty(B * T * FEAT_DIM + 1024, dtype=torch.bfloat16, device=self.device),
-                        frames=torch.ones(B, dtype=torch.int32, device=self.device),
-                        row0=torch.arange(B + 1, dtype=torch.int32, device=self.device) if packed else None, plans={})
-        return self._vstates.get_or_make((B, L, "packed") if packed else (B, L), make)
-
-    def _front_forward_varlen(self, x, frames, rows):
-        """Encoder (bf16 kernels, padding mask; rows = (row0, Mq): packed layout) + LL + zero_tail_rows on a variable-length scoring batch:
-        the shape's state with fixed addresses, one launch plan per shape (and packed row count), counts overwritten before a replay."""
-        B, L = x.shape
-        st = self._varlen_state(B, L, rows is not None)
-        st["x"].copy_(x)
-        st["frames"].copy_(frames)
-        Mq = None
-        if rows is not None:
-            st["row0"].copy_(rows[0])
-            Mq = int(rows[1])
-        self.ssl.refresh_weights()
-        plan = st["plans"].get(Mq)
-        if plan is not None:
-            ops.replay(plan)
-            return st["feats"]
-        ops.start_recording()
-        P, E = self.P, self.cfg.embed
-        enc_out, _ = self.ssl.forward(st["x"], training=False, refresh=False, frames=st["frames"], grad=False,
-                                      packed=None if Mq is None else (st["row0"], Mq))
-        M = B * st["T"]
-        ops.gemm(Op(enc_out, E), Op(P.bf16, E, offset=P.off("LL.weight")), st["scratch"], M, FEAT_DIM, E, bias=P.f32("LL.bias"), c2=st["feats"])
-        ops.zero_tail_rows(st["feats"], st["frames"], B, st["T"], FEAT_DIM)
-        st["plans"][Mq] = ops.stop_recording()
-        return st["feats"]
-
-    def _forward_varlen(self, x, lengths):
-        if self.training or torch.is_grad_enabled():
-            raise NotImplementedError("%s: forward(x, lengths) is a scoring mode on model.eval() under torch.no_grad(); training on "
-                                      "zero-padded batches is implemented for the wav2vec2_linear_nll plugin only"
-                                      % type(self).__module__.split(".")[-1])
-        B, L = x.shape
-        counts = self._frame_counts(lengths, B, L)
-        frames = self._upload_i32(counts)
-        rows = None
-        if ENC.SCORE_PACK if SCORE_FP32 else ENC.VARLEN_PACK:      # as model_linear._forward: one switch per scoring precision
-            row0, Mq = ops.packed_rows(counts, self.cfg.conv_lens(L)[-1], ENC.PACK_ROWS)
-            rows = (self._upload_i32(row0), Mq)
-        if SCORE_FP32:
-            E = self.cfg.embed
-            enc, T = self.ssl.forward_f32(x, frames, packed=rows)
-            feats = torch.empty(B, T, FEAT_DIM, device=self.device)
-            ops.gemm(Op(enc, E), Op(self.P.flat, E, offset=self.P.off("LL.weight")), feats, B * T, FEAT_DIM, E, bias=self.P.f32("LL.bias"))
-            ops.zero_tail_rows(feats, frames, B, T, FEAT_DIM)
-        else:
-            feats = self._front_forward_varlen(x, frames, rows).clone()
-        output, last_hidden = self._head_forward(self, feats, counts)
-        if self.is_train:
-            return output, feats, last_hidden
-        return output
-
     def forward(self, x, lengths=None):
         if lengths is not None and not self.head_takes_frames:
             raise NotImplementedError("%s: %s" % (type(self).__module__.split(".")[-1], self.VARLEN_REFUSAL))
         if x.dim() == 3:
             x = x[:, :, 0]
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        counts, layout = None, FIXED
         if lengths is not None:
-            return self._forward_varlen(x, lengths)
+            if self.training or torch.is_grad_enabled():
+                raise NotImplementedError("%s: forward(x, lengths) is a scoring mode on model.eval() under torch.no_grad(); training on "
+                                          "zero-padded batches is implemented for the wav2vec2_linear_nll plugin only"
+                                          % type(self).__module__.split(".")[-1])
+            counts, layout = ENC.row_layout(self.cfg, lengths, *x.shape, min_samples=self.min_samples(), refuse_short=True,
+                                            score_f32=SCORE_FP32, device=self.device)
         if torch.is_grad_enabled():
             feats = _FrontFn.apply(self, x, self._anchor)
         elif not self.training and SCORE_FP32:
-            # scoring: fp32 activations / master weights / exact-fp32 GEMMs through the encoder and LL (the back-end is fp32 anyway)
-            enc, T = self.ssl.forward_f32(x)
-            feats = torch.empty(x.shape[0], T, FEAT_DIM, device=self.device)
-            ops.gemm(Op(enc, self.cfg.embed), Op(self.P.flat, self.cfg.embed, offset=self.P.off("LL.weight")), feats, x.shape[0] * T, FEAT_DIM,
-                     self.cfg.embed, bias=self.P.f32("LL.bias"))
+            feats = self._front_f32(x, layout)
         else:
-            feats = self._front_forward(x)[0].clone()
-        output, last_hidden = self._head(feats)
+            feats = self._front_forward(x, layout)[0].clone()
+        # a variable-length batch: the back-end masks the padding itself, from the host-side frame counts
+        output, last_hidden = self._head(feats) if counts is None else self._head_forward(self, feats, counts)
         if self.is_train:
             return output, feats, last_hidden
         return output

@@ -15,18 +15,17 @@ backend.m_frame_level.{0,3,6}.*, backend.m_utt_level.*), so its checkpoints load
 boundaries (model, loss); parameter gradients are written straight into the flat gradient buffer.
 """
 import math
+import os
 
 import torch
 from torch import nn
 
 from . import encoder as ENC
 from . import ops
-from .encoder import Encoder, VarlenSets, W2VConfig, param_specs
+from .encoder import FIXED, Encoder, RowLayout, VarlenSets, W2VConfig, param_specs
 from .lib import ACT_LEAKY, ACT_RELU
 from .ops import Op
 from .params import FlatParams, register_by_name
-
-import os
 
 HEAD_DIM = 128
 N_CLASS = 2
@@ -83,7 +82,6 @@ def dropout_stream_seed(seed, rank):
 def maybe_load_pretrained(model, args):
     """The reference's SSLModel loads pretrained/xlsr2_300m.pt at construction (model/xlsr.py:14-16).  Do the same when the file
     (or the YAML's optional `pretrained:` path) exists; take encoder_layerdrop from its cfg unless the YAML overrides it."""
-    import os
     from . import checkpoint
     explicit = hasattr(args, "get") and args.get("pretrained")
     path = explicit or checkpoint.DEFAULT_PRETRAINED
@@ -101,8 +99,8 @@ class _ModelFn(torch.autograd.Function):
     buffers; backward consumes (d_logp, d_feats, d_emb) and fills the flat gradient buffer."""
 
     @staticmethod
-    def forward(ctx, model, x, anchor, frames=None, rows=None):
-        out, feats, emb, saved = model._run_forward(x, frames, train=frames is not None, rows=rows)
+    def forward(ctx, model, x, anchor, layout=FIXED):
+        out, feats, emb, saved = model._run_forward(x, layout, train=not layout.fixed)
         ctx.model, ctx.saved = model, saved
         # the outputs live in static per-(B, L) buffers (launch plans point at them): hand out copies, so results
         # of successive forward calls do not alias (3 small device copies)
@@ -111,7 +109,7 @@ class _ModelFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_out, d_feats, d_emb):
         ctx.model._run_backward(ctx.saved, d_out, d_feats, d_emb)
-        return None, None, None, None, None
+        return None, None, None, None
 
 
 class Model(nn.Module):
@@ -199,91 +197,52 @@ class Model(nn.Module):
                     demb=f32(B * HEAD_DIM), ws=f32(B * N_CLASS + 16),
                     cs=f32(ops.colsum_reduce_nparts(M, 8) * max(HEAD_DIM, 8)), dW=f32(HEAD_DIM * max(HEAD_DIM, self.cfg.embed)))
 
-    def _state(self, B, L):
-        """Static per-(B, L) buffers at the autograd boundary, so recorded launch plans stay valid."""
-        key = (B, L)
-        if key not in self._states:
-            T = self.cfg.conv_lens(L)[-1]
-            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
-            self._states[key] = dict(T=T, x=f32(B, L), feats=f32(B, T, HEAD_DIM), emb=f32(B, HEAD_DIM), logp=f32(B, N_CLASS),
-                                     d_logp=f32(B, N_CLASS), d_feats=f32(B, T, HEAD_DIM), d_emb=f32(B, HEAD_DIM), plans={})
-        return self._states[key]
-
-    def _row0_buf(self, B, packed):
-        """The packed layout's row offsets [B + 1] of a variable-length state: a device buffer of fixed address like the frame counts,
-        overwritten before every replay (None for the padded layout)."""
-        return torch.arange(B + 1, dtype=torch.int32, device=self.device) if packed else None
-
-    def _varlen_state(self, B, L, packed=False):
-        """_state for a variable-length scoring batch: forward-only buffers, the frame counts (a device buffer of fixed address, overwritten
-        before every replay of the shape's plan) and the shape's own head buffers.  packed: the state of the packed layout (a state of its
-        own, keyed like the encoder's buffer set), with the row offsets besides; its plans are kept per packed row count."""
+    def _state(self, B, L, layout=FIXED, train=False):
+        """Static buffers of a [B, L] batch at the autograd boundary, so recorded launch plans stay valid.  A variable-length batch (a state
+        of its own per row layout, keyed like the encoder's buffer set): the frame counts and, packed, the row offsets besides — device
+        buffers of fixed address, overwritten before every replay of the shape's plans, which are kept per packed row count — and the shape's
+        own head buffers; forward-only for a scoring batch (least recently used of a few), both directions for a training one (kept)."""
         def make():
             T = self.cfg.conv_lens(L)[-1]
             f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
-            return dict(T=T, x=f32(B, L), feats=f32(B, T, HEAD_DIM), emb=f32(B, HEAD_DIM), logp=f32(B, N_CLASS),
-                        frames=torch.ones(B, dtype=torch.int32, device=self.device), row0=self._row0_buf(B, packed),
-                        hb=self._head_bufs(B, T, keep=False), plans={})
-        return self._vstates.get_or_make((B, L, "packed") if packed else (B, L), make)
-
-    def _varlen_train_state(self, B, L, packed=False):
-        """_state for a variable-length training batch: the boundary buffers of both directions, the frame counts (fixed address, read by
-        the forward's and the backward's plans) and the shape's own head buffers.  packed: as in _varlen_state."""
-        key = (B, L, "packed") if packed else (B, L)
-        if key not in self._vstates_train:
-            T = self.cfg.conv_lens(L)[-1]
-            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
-            self._vstates_train[key] = dict(T=T, x=f32(B, L), feats=f32(B, T, HEAD_DIM), emb=f32(B, HEAD_DIM), logp=f32(B, N_CLASS),
-                                            d_logp=f32(B, N_CLASS), d_feats=f32(B, T, HEAD_DIM), d_emb=f32(B, HEAD_DIM), train=True,
-                                            frames=torch.ones(B, dtype=torch.int32, device=self.device), row0=self._row0_buf(B, packed),
-                                            hb=self._head_bufs(B, T, keep=False), plans={})
-        return self._vstates_train[key]
-
-    def _frame_counts(self, lengths, B, L):
-        """Sample counts of a zero-padded batch -> frame counts, a list of ints validated on the host.  Counts below the shortest clip that
-        yields a frame count as that clip: its zero padding is part of the signal, as for a file padded on disk."""
-        lengths = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        lo = self.cfg.min_samples()
-        if len(lengths) != B or L < lo or any(n < 1 or n > L for n in lengths):
-            raise ValueError("lengths: need one sample count in 1..%d per row of the [%d, %d] batch (at least %d samples per row), got %r"
-                             % (L, B, L, lo, lengths))
-        return ops.check_lengths([self.cfg.conv_lens(max(n, lo))[-1] for n in lengths], self.cfg.conv_lens(L)[-1])
+            i32 = dict(dtype=torch.int32, device=self.device)
+            st = dict(T=T, x=f32(B, L), feats=f32(B, T, HEAD_DIM), emb=f32(B, HEAD_DIM), logp=f32(B, N_CLASS), train=train, plans={})
+            if layout.fixed or train:
+                st.update(d_logp=f32(B, N_CLASS), d_feats=f32(B, T, HEAD_DIM), d_emb=f32(B, HEAD_DIM))
+            if not layout.fixed:
+                st.update(frames=torch.ones(B, **i32), row0=torch.arange(B + 1, **i32) if layout.packed else None,
+                          hb=self._head_bufs(B, T, keep=False))
+            return st
+        key = layout.key(B, L)
+        if not layout.fixed and not train:
+            return self._vstates.get_or_make(key, make)
+        store = self._states if layout.fixed else self._vstates_train
+        if key not in store:
+            store[key] = make()
+        return store[key]
 
     def min_samples(self):
         """The shortest row forward(x, lengths) takes (main.py --padding_type none pads shorter files to it): one frame."""
         return self.cfg.min_samples()
 
-    def _upload_i32(self, values):
-        host = torch.tensor(values, dtype=torch.int32)
-        return (host.pin_memory() if self.device.type == "cuda" else host).to(self.device, non_blocking=True)
-
-    def _packed_rows(self, counts, L):
-        """The packed layout of a batch with these frame counts: (row offsets [B + 1] as an int32 device tensor, Mq rows per launch), both
-        from the host-side counts (ops.packed_rows with the encoder's PACK_ROWS)."""
-        row0, Mq = ops.packed_rows(counts, self.cfg.conv_lens(L)[-1], ENC.PACK_ROWS)
-        return self._upload_i32(row0), Mq
-
-    def _run_forward(self, x, frames=None, train=False, rows=None):
-        """rows: (row0, Mq) of _packed_rows — the encoder's transformer layers run on the packed valid frames (with frames only)."""
+    def _run_forward(self, x, layout=FIXED, train=False):
+        """layout: the rows of the batch (encoder.row_layout); train: a backward follows a variable-length batch."""
         B, L = x.shape
         training = bool(self.training)
         ssl_train = False if self.flag_fix_ssl else bool(self.is_train and training)   # SURVEY.md §3.2 quirk
-        Mq = None
-        if frames is not None:
-            st = self._varlen_train_state(B, L, rows is not None) if train else self._varlen_state(B, L, rows is not None)
-            st["frames"].copy_(frames)
-            if rows is not None:
-                st["row0"].copy_(rows[0])
-                Mq = int(rows[1])
-        else:
-            st = self._state(B, L)
+        st = self._state(B, L, layout, train)
+        if not layout.fixed:      # into the state's buffers, which the recorded plans read
+            st["frames"].copy_(layout.frames)
+            if layout.packed:
+                st["row0"].copy_(layout.row0)
+            layout = RowLayout(st["frames"], st["row0"], layout.Mq)
         st["x"].copy_(x)
         drop = DROP_P if training else 0.0
         self._step_seed = (self._step_seed * 1664525 + 1013904223) & 0x7FFFFFFF
         seeds = [(self._step_seed + 7919 * j) & 0x7FFFFFFF for j in range(3)]
         self.encoder.refresh_weights()
         use_plan = self.cfg.encoder_layerdrop == 0 or not ssl_train
-        pk = ("fwd", training, ssl_train) if Mq is None else ("fwd", training, ssl_train, Mq)      # packed: a plan per row count
+        pk = layout.plan_key("fwd", training, ssl_train)
         plan = st["plans"].get(pk) if use_plan else None
         if plan is not None:
             for dsc, sd in zip(plan["drop_descs"], seeds):
@@ -295,20 +254,18 @@ class Model(nn.Module):
             return st["logp"], st["feats"], st["emb"], saved
         if use_plan:
             ops.start_recording()
-        saved, drop_descs = self._forward_kernels(st, B, L, ssl_train, drop, seeds, Mq)
+        saved, drop_descs = self._forward_kernels(st, B, L, ssl_train, drop, seeds, layout)
         if use_plan:
             st["plans"][pk] = dict(calls=ops.stop_recording(), drop_descs=drop_descs, saved=saved)
         return st["logp"], st["feats"], st["emb"], dict(saved, seeds=seeds)
 
-    def _forward_kernels(self, st, B, L, ssl_train, drop, seeds, Mq=None):
+    def _forward_kernels(self, st, B, L, ssl_train, drop, seeds, layout):
         P, E = self.P, self.cfg.embed
-        frames = st.get("frames")      # a variable-length state (scoring, or training: st["train"])
-        enc_out, ectx = self.encoder.forward(st["x"], training=ssl_train, refresh=False, step_seed=self._step_seed, frames=frames,
-                                             grad=bool(st.get("train")) if frames is not None else None,
-                                             packed=None if Mq is None else (st["row0"], Mq))
+        enc_out, ectx = self.encoder.forward(st["x"], training=ssl_train, refresh=False, step_seed=self._step_seed,
+                                             grad=None if layout.fixed else st["train"], **layout.args)
         T = ectx["d"]["T"]
         M = B * T
-        hb = st["hb"] if frames is not None else self._head_bufs(B, T)
+        hb = self._head_bufs(B, T) if layout.fixed else st["hb"]
         feats, emb, logp = st["feats"], st["emb"], st["logp"]
         W = lambda name, ld: Op(P.bf16, ld, offset=P.off(name))
         # feats = LL(x) (pre-ReLU tensor is what SupCon sees, linear_nll:127-129), r0 = relu(feats)
@@ -321,9 +278,9 @@ class Model(nn.Module):
                            drop_seed=seeds[j], x3=False)
             drop_descs.append(dsc)
             prev = hb["h"][j]
-        if frames is not None:
-            ops.zero_tail_rows(feats, frames, B, T, HEAD_DIM)
-            ops.meanpool_fwd_varlen(prev, emb, frames, B, T, HEAD_DIM)
+        if not layout.fixed:
+            ops.zero_tail_rows(feats, layout.frames, B, T, HEAD_DIM)
+            ops.meanpool_fwd_varlen(prev, emb, layout.frames, B, T, HEAD_DIM)
         else:
             ops.meanpool_fwd(prev, emb, B, T, HEAD_DIM)
         ops.utt_head_fwd(emb, P.f32("backend.m_utt_level.weight"), P.f32("backend.m_utt_level.bias"), logp, B, HEAD_DIM, N_CLASS)
@@ -342,9 +299,7 @@ class Model(nn.Module):
         if self.grad_sync is not None:
             self.encoder.on_grads_ready = self.grad_sync.ready_above
         use_plan = not sv["ectx"]["skipped"] and self.cfg.encoder_layerdrop == 0
-        pk = ("bwd", sv["drop"] > 0, self.grad_sync is not None)
-        if sv["ectx"].get("packed") is not None:      # packed: a plan per row count (the row offsets are the state's, already in place)
-            pk += (sv["ectx"]["packed"][1],)
+        pk = sv["ectx"]["layout"].plan_key("bwd", sv["drop"] > 0, self.grad_sync is not None)      # the row offsets are the state's, already in place
         plan = st["plans"].get(pk) if use_plan else None
         if plan is not None:
             plan["drop_descs"][0].drop_seed = seeds[1]
@@ -366,7 +321,7 @@ class Model(nn.Module):
         W = lambda name, ld: Op(P.bf16, ld, offset=P.off(name))
         ops.utt_head_bwd(st["d_logp"], sv["logp"], sv["emb"], P.f32("backend.m_utt_level.weight"), st["d_emb"], hb["demb"],
                          P.g("backend.m_utt_level.weight"), P.g("backend.m_utt_level.bias"), hb["ws"], B, HEAD_DIM, N_CLASS)
-        frames = st.get("frames")      # a variable-length training batch: the mean ran over each utterance's own frames
+        frames = sv["ectx"]["layout"].frames      # a variable-length training batch: the mean ran over each utterance's own frames
         if frames is not None:
             # the forward zeroed feats beyond them, so whatever the loss hands back there (SupCon's gradient is not 0) stops here
             ops.zero_tail_rows(st["d_feats"], frames, B, T, HEAD_DIM)
@@ -400,14 +355,15 @@ class Model(nn.Module):
             enc_slots = self.encoder.backward(sv["ectx"], hb["denc"])
         return dict(drop_descs=drop_descs, meanpool_entry=mp_entry, meanpool_seed_pos=mp_pos, enc_slots=enc_slots)
 
-    def _score_fp32(self, x, frames=None, rows=None):
+    def _score_fp32(self, x, layout=FIXED):
         """Scoring forward (no grad, eval mode): fp32 activations, fp32 master weights, exact-fp32 GEMMs end to end — the
         reference's precision (main.py:161-214), for scores / embeddings within 1e-3 of it.
-        rows: (row0, Mq) of _packed_rows — the encoder's transformer layers run on the packed valid frames (encoder.SCORE_PACK); the
-        encoder hands back the padded rectangle, so the head below is the same either way."""
+        A packed layout (encoder.SCORE_PACK): the encoder's transformer layers run on the packed valid frames and it hands back the padded
+        rectangle, so the head below is the same either way."""
         P, E = self.P, self.cfg.embed
         B = x.shape[0]
-        enc, T = self.encoder.forward_f32(x, frames, packed=rows)
+        enc, T = self.encoder.forward_f32(x, **layout.args)
+        frames = layout.frames
         M = B * T
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
         Wf = lambda name, ld: Op(P.flat, ld, offset=P.off(name))
@@ -431,24 +387,21 @@ class Model(nn.Module):
         if x.dim() == 3:
             x = x[:, :, 0]
         x = x.to(device=self.device, dtype=torch.float32).contiguous()   # main.py:60 hands over a transposed view
-        frames = rows = None
+        layout = FIXED
         if lengths is not None:
             if torch.is_grad_enabled() != bool(self.training):
                 raise NotImplementedError("forward(x, lengths) is a scoring mode on model.eval() under torch.no_grad() and a training "
                                           "mode on model.train() with autograd on; eval with autograd, or train under no_grad, is neither")
-            counts = self._frame_counts(lengths, x.shape[0], x.shape[1])
-            frames = self._upload_i32(counts)
             # the packed layout: encoder.VARLEN_PACK serves the bf16 encoder path, encoder.SCORE_PACK the fp32 scoring path (whose
             # materialised-score attention is strided per utterance: packed, it runs the streaming kernel of csrc/attention_f32.hip)
-            score_f32 = not self.training and SCORE_FP32
-            if ENC.SCORE_PACK if score_f32 else ENC.VARLEN_PACK:
-                rows = self._packed_rows(counts, x.shape[1])
+            _, layout = ENC.row_layout(self.cfg, lengths, *x.shape, min_samples=self.min_samples(), refuse_short=False,
+                                       score_f32=not self.training and SCORE_FP32, device=self.device)
         if torch.is_grad_enabled() and any(p.requires_grad for p in (self._anchor,)):
-            out, feats, emb = _ModelFn.apply(self, x, self._anchor, frames, rows)
+            out, feats, emb = _ModelFn.apply(self, x, self._anchor, layout)
         elif not self.training and SCORE_FP32:
-            out, feats, emb = self._score_fp32(x, frames, rows)
+            out, feats, emb = self._score_fp32(x, layout)
         else:
-            out, feats, emb, _ = self._run_forward(x, frames, rows=rows)
+            out, feats, emb, _ = self._run_forward(x, layout)
             out, feats, emb = out.clone(), feats.clone(), emb.clone()
         if self.is_train:
             return out, feats, emb

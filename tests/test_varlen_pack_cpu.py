@@ -4,6 +4,7 @@ error code and a message before anything is launched.  The header / ctypes agree
 import ctypes
 
 import pytest
+import torch
 
 from scl_amd import encoder, lib, ops
 from scl_amd.lib import SclError
@@ -74,3 +75,46 @@ def test_entry_points_refuse_null_and_bad_arguments_without_touching_the_gpu():
         assert fn(p, p, 1, None, 2, 8, 128, 64, None) == -1
         assert fn(p, p, 0, p, 2, 8, 12, 64, None) == -1 and b"C % 8" in L.scl_last_error()
         assert fn(p, p, 0, p, 2, 8, 128, 128, None) == -1 and b"Mq" in L.scl_last_error()
+
+
+def test_sample_counts_to_a_row_layout(monkeypatch):
+    """encoder.row_layout on the host (device="cpu"): frame counts from the conv stack's own arithmetic, the two rules for a row below the
+    minimum clip, the pack switch of each precision read at call time, and the refusals of RowLayout itself."""
+    cfg = encoder.W2VConfig.tiny()
+    B, L, lengths, lo = 4, 4000, [4000, 1000, 399, 1], cfg.min_samples()
+    assert cfg.conv_lens(L)[-1] == 12 and cfg.conv_lens(lo)[-1] == 1 and lo > 399
+    want = [cfg.conv_lens(max(n, lo))[-1] for n in lengths]
+    assert want[2:] == [1, 1]      # the last two rows count as the minimum clip: one frame
+    monkeypatch.setattr(encoder, "PACK_ROWS", 64)
+    for score_f32, switch, other in ((True, "SCORE_PACK", "VARLEN_PACK"), (False, "VARLEN_PACK", "SCORE_PACK")):
+        kw = dict(min_samples=lo, refuse_short=False, score_f32=score_f32, device="cpu")
+        monkeypatch.setattr(encoder, switch, True)
+        monkeypatch.setattr(encoder, other, False)
+        counts, lay = encoder.row_layout(cfg, lengths, B, L, **kw)
+        assert counts == want and lay.frames.tolist() == want and lay.frames.dtype == torch.int32
+        assert lay.packed and not lay.padded and not lay.fixed and lay.Mq == 64
+        assert lay.row0.tolist() == [sum(want[:b]) for b in range(B + 1)] and lay.row0.dtype == torch.int32
+        assert lay.rows(B * 12) == 64 and lay.key(B, L) == (B, L, "packed") and lay.plan_key("fwd", True) == ("fwd", True, 64)
+        lay.check(B, 12)
+        monkeypatch.setattr(encoder, switch, False)
+        monkeypatch.setattr(encoder, other, True)      # the other precision's switch has no effect
+        counts, lay = encoder.row_layout(cfg, torch.tensor(lengths), B, L, **kw)
+        assert counts == want and lay.frames.tolist() == want and lay.row0 is None and lay.Mq is None
+        assert lay.padded and not lay.packed and not lay.fixed
+        assert lay.rows(B * 12) == B * 12 and lay.key(B, L) == (B, L) and lay.plan_key("fwd", True) == ("fwd", True)
+        with pytest.raises(ValueError, match="at least"):
+            encoder.row_layout(cfg, lengths, B, L, **dict(kw, refuse_short=True))
+        for refuse in (False, True):
+            with pytest.raises(ValueError, match="lengths"):
+                encoder.row_layout(cfg, [4000, 4001], 2, L, **dict(kw, refuse_short=refuse))
+    fixed = encoder.RowLayout()
+    assert fixed.fixed and not fixed.padded and not fixed.packed and fixed.rows(48) == 48 and fixed.key(B, L) == (B, L)
+    frames = torch.tensor(want, dtype=torch.int32)
+    with pytest.raises(ValueError, match=r"packed=\(row0, Mq\) needs the frame counts of the batch"):
+        encoder.RowLayout(None, torch.tensor([0, 12, 14, 15, 16], dtype=torch.int32), 64)
+    with pytest.raises(ValueError, match="packed row count 100: need a multiple of 64"):
+        encoder.RowLayout(frames, torch.tensor([0, 12, 14, 15, 16], dtype=torch.int32), 100)
+    with pytest.raises(ValueError, match=r"packed row count 128: need a multiple of 64 in 4\.\.64"):      # above roundup(B * T, 64)
+        encoder.RowLayout(frames, torch.tensor([0, 12, 14, 15, 16], dtype=torch.int32), 128).check(B, 12)
+    with pytest.raises(AttributeError):      # immutable
+        fixed.Mq = 64

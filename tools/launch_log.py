@@ -1,0 +1,199 @@
+"""Every C-ABI launch of a step in a canonical form, to compare two versions of the host code launch by launch (needs the MI355X; the
+method of profiles/encoder_switch_removal.txt).  Per case a fresh model; ops._call is wrapped and every call of the FIRST step is printed
+in issue order; after a SECOND step every recorded plan held in the model's states is printed, in the order they were recorded.  A call
+prints as the entry-point name, every integer and float argument — each field of the descriptor and job structs passed by reference
+included — and every address as the index of its first appearance in the section.  Two versions issue the same launches when their
+outputs are equal (both on the same libscl_hip.so, SCL_LIB_PATH); the "# counts" lines give calls / scalar / address arguments.
+
+    python tools/launch_log.py [--cases small,other,resnet,aasist,xlsr] > launches.txt
+"""
+import argparse
+import ctypes
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from scl_amd import encoder as ENC  # noqa: E402
+from scl_amd import model_front as MF  # noqa: E402
+from scl_amd import model_linear as ML  # noqa: E402
+from scl_amd import ops  # noqa: E402
+from scl_amd.encoder import W2VConfig  # noqa: E402
+
+LINEAR = {"flag_fix_ssl": False, "contra_mode": "all", "loss_type": 1}
+SMALL = dict(conv_dim=32, embed=128, layers=2, heads=2, ffn=256, pos_k=16, pos_groups=4, final_dim=16, latent_vars=8, latent_groups=2)
+LENGTHS = [20880, 400, 20560, 7777, 12000, 4000]      # tests/test_varlen_pack_gpu.py: 65, 1, 64, 24, 37 and 12 frames
+RESNET_COUNTS = [17680, 18000, 25500, 33040, 41680]   # tests/test_resnet_varlen_gpu.py, in a [5, 48000] batch
+
+
+class Canon:
+    """Arguments -> tokens; an address is the index of its first appearance."""
+
+    def __init__(self):
+        self.addr, self.calls, self.scalars, self.addrs = {}, 0, 0, 0
+
+    def a(self, v):
+        v = v.value if isinstance(v, ctypes.c_void_p) else v
+        self.addrs += 1
+        return "@nil" if not v else "@%d" % self.addr.setdefault(int(v), len(self.addr))
+
+    def n(self, v):
+        self.scalars += 1
+        return repr(v.value if hasattr(v, "value") else v)
+
+    def tok(self, v, ctype=None):
+        v = getattr(v, "_obj", v)      # ctypes.byref(x)
+        if isinstance(v, ctypes.Structure):
+            return "{%s}" % " ".join("%s=%s" % (f[0], self.tok(getattr(v, f[0]), f[1])) for f in v._fields_ if f[0] != "_pad")
+        if isinstance(v, ctypes.Array):
+            return "[%s]" % " ".join(self.tok(e, v._type_) for e in v)
+        if ctype is ctypes.c_void_p or isinstance(v, ctypes.c_void_p) or (v is None and ctype is not None):
+            return self.a(v)
+        return self.n(v)
+
+    def call(self, name, fn, args):
+        types = getattr(fn, "argtypes", None) or [None] * len(args)
+        self.calls += 1
+        return "%s %s" % (name, " ".join(self.tok(v, t) for v, t in zip(args, types)))
+
+    def counts(self):
+        return "# counts: %d calls, %d scalar arguments, %d address arguments" % (self.calls, self.scalars, self.addrs)
+
+
+def run(title, model, step):
+    """First step under the wrapped ops._call, second step, then the plans of every state of the model."""
+    print("== %s: first step" % title)
+    torch.manual_seed(0)
+    first, real = Canon(), ops._call
+
+    def logged(name, *args, keep=None):
+        e = real(name, *args, keep=keep)
+        fn = getattr(ops.L.load(), name)
+        print(first.call(name, fn, args))
+        return e
+    ops._call = logged
+    try:
+        step()
+    finally:
+        ops._call = real
+    print(first.counts())
+    step()
+    torch.cuda.synchronize()
+    k = 0
+    for store in ("_states", "_vstates_train", "_vstates"):
+        for st in getattr(model, store, {}).values():
+            for plan in st["plans"].values():
+                c = Canon()
+                print("== %s: plan %d after the second step" % (title, k))
+                for fn, args, name, _ in (plan["calls"] if isinstance(plan, dict) else plan):
+                    print(c.call(name, fn, args))
+                print(c.counts())
+                k += 1
+
+
+def batch(B, L, lengths=None, seed=0):
+    x = 0.1 * torch.randn(B, L, generator=torch.Generator().manual_seed(seed))
+    for b, n in enumerate(lengths or ()):
+        x[b, n:] = 0
+    return x.cuda()
+
+
+def train(m, x, lengths=None):
+    def step():
+        out = m(x, lengths=lengths) if lengths is not None else m(x)
+        torch.autograd.backward(list(out), [torch.ones_like(o) for o in out])
+    m.train()
+    return step
+
+
+def score(m, x, lengths=None):
+    def step():
+        with torch.no_grad():
+            m(x, lengths=lengths) if lengths is not None else m(x)
+    m.eval()
+    return step
+
+
+def layouts(fixed=True):
+    """(name, lengths or None, pack switches on) of the three row layouts, PACK_ROWS = 64."""
+    return ([("fixed", None, False)] if fixed else []) + [("padded", True, False), ("packed", True, True)]
+
+
+def switches(pack, fp32):
+    ENC.PACK_ROWS = 64
+    ENC.VARLEN_PACK = ENC.SCORE_PACK = pack
+    ML.SCORE_FP32 = MF.SCORE_FP32 = fp32
+
+
+def case_small(dev):
+    x = batch(len(LENGTHS), max(LENGTHS), LENGTHS)
+    for p in (0.0, 0.1):
+        for name, var, pack in layouts():
+            switches(pack, True)
+            m = ML.Model(LINEAR, dev, w2v_cfg=W2VConfig(**SMALL, dropout=p, attention_dropout=p, activation_dropout=p, dropout_input=p))
+            run("linear small train %s dropout %g" % (name, p), m, train(m, x, LENGTHS if var else None))
+    for fp32 in (True, False):
+        for name, var, pack in layouts(fixed=fp32):
+            switches(pack, fp32)
+            m = ML.Model(LINEAR, dev, w2v_cfg=W2VConfig(**SMALL))
+            run("linear small score %s %s" % ("fp32" if fp32 else "bf16", name), m, score(m, x, LENGTHS if var else None))
+
+
+def case_other(dev):
+    switches(False, True)
+    m = ML.Model(LINEAR, dev, w2v_cfg=W2VConfig.tiny())
+    run("linear tiny 5x9000 train (materialised scores)", m, train(m, batch(5, 9000)))
+    m = ML.Model(LINEAR, dev, w2v_cfg=W2VConfig(**SMALL))
+    run("linear small 4x200000 train (streaming)", m, train(m, batch(4, 200000)))
+    cfg = W2VConfig(**SMALL)
+    T = cfg.conv_lens(200000)[-1]
+    ENC.F32_ATTN_CHUNK_BYTES, keep = 4 * cfg.heads * T * ((T + 7) // 8 * 8), ENC.F32_ATTN_CHUNK_BYTES      # one utterance per chunk
+    m = ML.Model(LINEAR, dev, w2v_cfg=cfg)
+    run("linear small 2x200000 score fp32 (chunked)", m, score(m, batch(2, 200000)))
+    ENC.F32_ATTN_CHUNK_BYTES = keep
+
+
+def case_resnet(dev):
+    from scl_amd.model_resnet import Model
+    from scl_amd.resnet_head import DEFAULT_RESNET
+    args = dict(LINEAR, resnet=DEFAULT_RESNET)
+    switches(False, True)
+    m = Model(args, dev, w2v_cfg=W2VConfig.tiny())
+    run("resnet tiny 4x24000 train", m, train(m, batch(4, 24000)))
+    x = batch(5, 48000, RESNET_COUNTS)
+    for fp32 in (True, False):
+        for name, _, pack in layouts(fixed=False):
+            switches(pack, fp32)
+            m = Model(args, dev, w2v_cfg=W2VConfig(**SMALL))
+            run("resnet small score %s %s" % ("fp32" if fp32 else "bf16", name), m, score(m, x, RESNET_COUNTS))
+
+
+def case_aasist(dev):
+    from scl_amd.aasist_head import UPSTREAM_AASIST
+    from scl_amd.model_aasist import Model
+    switches(False, True)
+    m = Model({"contra_mode": "all", "loss_type": 1, "aasist": UPSTREAM_AASIST}, dev, w2v_cfg=W2VConfig.tiny())
+    run("aasist tiny 4x20000 train", m, train(m, batch(4, 20000)))
+
+
+def case_xlsr(dev):
+    switches(False, True)
+    m = ML.Model(LINEAR, dev, w2v_cfg=W2VConfig())
+    run("linear xlsr 64x64000 train", m, train(m, batch(64, 64000)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default="small,other,resnet,aasist,xlsr")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the MI355X"
+    for name in args.cases.split(","):
+        globals()["case_" + name](torch.device("cuda:0"))
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
