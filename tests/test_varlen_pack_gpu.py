@@ -2,7 +2,8 @@
 only, packed back to back.  The small encoder and the oracle set-up of tests/test_varlen_train_gpu.py; PACK_ROWS is set to 64 so that
 bucket edges are reachable at this size.  Outputs and every parameter gradient against the CPU oracle's autograd on each utterance ALONE
 with the padded path's bars; exact zeros wherever no frame is valid; padding content; launch plans per (direction, row count); dropout;
-every frame valid; bf16 scoring; main.py --padding_type zero --batch_size 2 with the switch on."""
+a replayed step against a fresh recording at its seed, bit for bit, on every row layout; every frame valid; bf16 scoring;
+main.py --padding_type zero --batch_size 2 with the switch on."""
 import os
 
 import numpy as np
@@ -251,6 +252,49 @@ def test_packed_training_step_with_every_dropout_on(dev, monkeypatch):
     d = _packed_set(m)
     for dq in d["dqkv"]:
         assert (dq[203 * 3 * cfg.embed:256 * 3 * cfg.embed] == 0).all()
+
+
+@pytest.mark.parametrize("case", ["fixed", "padded", "packed", "tiny"])
+def test_a_replayed_step_is_bit_for_bit_the_recorded_step_of_its_seed(dev, monkeypatch, case):
+    """The per-step values of a launch plan (the encoder's site seeds, the head's three seeds) are patched into every recorded call that
+    carries one: model A records a train step at one step seed and replays it at another; model B, same weights and fresh states, records
+    its first step at that other seed.  A's second step and B's first issue the same launches with the same seeds, so the outputs and the
+    whole flat gradient buffer are equal bit for bit.  Every dropout on (the encoder's four at 0.1, the head's at its 0.5).  The six
+    utterances as a fixed batch (65 frames: the fused attention kernel), padded and packed (the streaming kernels); `tiny`: the 5 x 9000
+    fixed batch of tools/launch_log.py, 16-wide heads, so the materialised scores and scl_dropout_rows."""
+    monkeypatch.setattr(ENC, "VARLEN_PACK", case == "packed")
+    monkeypatch.setattr(ENC, "PACK_ROWS", 64)
+    drops = dict(dropout=0.1, attention_dropout=0.1, activation_dropout=0.1, dropout_input=0.1)
+    if case == "tiny":
+        cfg, lengths = W2VConfig.tiny(), None
+        vars(cfg).update(drops)
+        gen = torch.Generator().manual_seed(5)
+        B, T = 5, cfg.conv_lens(9000)[-1]
+        x = 0.1 * torch.randn(B, 9000, generator=gen)
+        ups = (0.3 * torch.randn(B, 2, generator=gen), 0.01 * torch.randn(B, T, 128, generator=gen), 0.05 * torch.randn(B, 128, generator=gen))
+    else:
+        cfg, lengths = W2VConfig(**SMALL, **drops), (None if case == "fixed" else LENGTHS)
+        x, ups, T = _inputs(LENGTHS)
+
+    def step(m, seed):
+        m._step_seed = seed
+        return VT._step(m, x, lengths, ups, dev)
+
+    def plans(m):
+        st, = (m._states if lengths is None else m._vstates_train).values()
+        return st["plans"]
+    a, b = (ML.Model(VT.ARGS, dev, w2v_cfg=cfg).train() for _ in range(2))
+    assert torch.equal(a.P.flat, b.P.flat)
+    first = step(a, 1234)
+    recorded = {k: len(v["calls"]) for k, v in plans(a).items()}
+    second = step(a, 99)
+    fresh = step(b, 99)
+    assert len(recorded) == 2 and {k: len(v["calls"]) for k, v in plans(a).items()} == recorded      # A's second step was a replay
+    d, = (a.encoder._bufs if lengths is None else a.encoder._vbufs_train).values()
+    assert (d["fused_attn"], d["long_attn"]) == {"fixed": (True, False), "tiny": (False, False)}.get(case, (False, True))
+    for name, got, want in zip(("logp", "feats", "emb", "flat gradient"), second, fresh):
+        assert torch.isfinite(got).all() and torch.equal(got, want), (case, name, (got != want).sum().item())
+    assert second[3].abs().max() > 0 and not torch.equal(first[3], second[3]) and not torch.equal(first[0], second[0])      # masks are drawn anew
 
 
 # ---- 6. bf16 scoring -------------------------------------------------------------------------------------------------------------------------

@@ -1,14 +1,18 @@
 """Every C-ABI launch of a step in a canonical form, to compare two versions of the host code launch by launch (needs the MI355X; the
 method of profiles/encoder_switch_removal.txt).  Per case a fresh model; ops._call is wrapped and every call of the FIRST step is printed
-in issue order; after a SECOND step every recorded plan held in the model's states is printed, in the order they were recorded.  A call
+in issue order; after a SECOND step every recorded plan held in the model's states is printed, in the order they were recorded, and then
+the forward and backward plans the AASIST / ResNet back-ends keep themselves (resstack._PLANS, graph._PLANS).  A call
 prints as the entry-point name, every integer and float argument — each field of the descriptor and job structs passed by reference
 included — and every address as the index of its first appearance in the section.  Two versions issue the same launches when their
 outputs are equal (both on the same libscl_hip.so, SCL_LIB_PATH); the "# counts" lines give calls / scalar / address arguments.
+Python's cyclic collector is off while a case runs: when it runs depends on how many container objects the host code has allocated, and
+it decides when a temporary held in a reference cycle goes back to torch's caching allocator, that is, which later buffer aliases it.
 
     python tools/launch_log.py [--cases small,other,resnet,aasist,xlsr] > launches.txt
 """
 import argparse
 import ctypes
+import gc
 import os
 import sys
 
@@ -18,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from scl_amd import encoder as ENC  # noqa: E402
+from scl_amd import graph, resstack  # noqa: E402
 from scl_amd import model_front as MF  # noqa: E402
 from scl_amd import model_linear as ML  # noqa: E402
 from scl_amd import ops  # noqa: E402
@@ -63,9 +68,27 @@ class Canon:
         return "# counts: %d calls, %d scalar arguments, %d address arguments" % (self.calls, self.scalars, self.addrs)
 
 
+def print_plan(header, plan):
+    c = Canon()
+    print(header)
+    for fn, args, name, _ in plan:
+        print(c.call(name, fn, args))
+    print(c.counts())
+
+
 def run(title, model, step):
-    """First step under the wrapped ops._call, second step, then the plans of every state of the model."""
+    """First step under the wrapped ops._call, second step, then the plans of every state of the model and of the back-ends."""
     print("== %s: first step" % title)
+    del resstack._PLANS[:], graph._PLANS[:]      # the back-ends' plans outlive a model: only this case's
+    gc.collect()
+    gc.disable()
+    try:
+        _run(title, model, step)
+    finally:
+        gc.enable()
+
+
+def _run(title, model, step):
     torch.manual_seed(0)
     first, real = Canon(), ops._call
 
@@ -86,12 +109,13 @@ def run(title, model, step):
     for store in ("_states", "_vstates_train", "_vstates"):
         for st in getattr(model, store, {}).values():
             for plan in st["plans"].values():
-                c = Canon()
-                print("== %s: plan %d after the second step" % (title, k))
-                for fn, args, name, _ in (plan["calls"] if isinstance(plan, dict) else plan):
-                    print(c.call(name, fn, args))
-                print(c.counts())
+                print_plan("== %s: plan %d after the second step" % (title, k), plan["calls"] if isinstance(plan, dict) else plan)
                 k += 1
+    for mod in (resstack, graph):
+        for i, pl in enumerate(mod._PLANS):
+            for which in ("fwd_calls", "bwd_calls"):
+                if getattr(pl, which) is not None:
+                    print_plan("== %s: %s plan %d %s after the second step" % (title, mod.__name__.split(".")[-1], i, which), getattr(pl, which))
 
 
 def batch(B, L, lengths=None, seed=0):
