@@ -77,6 +77,18 @@ class VarlenSets(collections.OrderedDict):
         return self[key]
 
 
+def shape_entry(key, make, layout, train, kept, lru, kept_train):
+    """What is kept per batch shape (an encoder buffer set, a model's boundary state) under `key`, made on first use, in the store of its
+    kind: a fixed shape's is kept for ever (`kept`); a variable-length scoring batch's lives in a VarlenSets (`lru`: every padded length is a
+    shape of its own); a variable-length training batch's (train: what it saved waits for the backward) is kept (`kept_train`)."""
+    if not layout.fixed and not train:
+        return lru.get_or_make(key, make)
+    store = kept if layout.fixed else kept_train
+    if key not in store:
+        store[key] = make()
+    return store[key]
+
+
 class RowLayout(collections.namedtuple("RowLayout", "frames row0 Mq", defaults=(None, None, None))):
     """How the rows of a [B, T] batch are laid out, the host-side twin of `enum class Rows` (csrc/attn_stream_body.h): fixed (every frame of
     every utterance counts), padded (frames: int32 [B] on the device, the valid frames of each zero-padded utterance) or packed (row0 besides:
@@ -328,15 +340,8 @@ class Encoder:
 
     # ---- buffers ---------------------------------------------------------------------------------
     def _set(self, key, make, layout, train=False, f32=False):
-        """The buffer set under `key`, made on first use, in the store of its kind: a fixed shape's is kept for ever (_bufs); a variable-length
-        scoring batch's lives in the LRU of its precision (_vbufs, _vbufs_f32); a variable-length training batch's (train: its saved activations
-        wait for the backward) is kept (_vbufs_train)."""
-        if not layout.fixed and not train:
-            return (self._vbufs_f32 if f32 else self._vbufs).get_or_make(key, make)
-        store = self._bufs if layout.fixed else self._vbufs_train
-        if key not in store:
-            store[key] = make()
-        return store[key]
+        """The buffer set under `key` in the store of its kind (shape_entry); the LRU of a scoring batch is the one of its precision."""
+        return shape_entry(key, make, layout, train, self._bufs, self._vbufs_f32 if f32 else self._vbufs, self._vbufs_train)
 
     def bufs(self, B, L, layout=FIXED, train=False):
         """The buffer set of a [B, L] batch on the bf16 path.  A variable-length batch's runs the streaming attention whatever T is (lse,

@@ -10,12 +10,12 @@ dropout probabilities and the training flag.  Dropout masks are counter hashes o
 training and recomputed in the backward; in eval mode BatchNorm uses the running statistics.
 """
 import ctypes
-import weakref
 
 import torch
 
 from . import lib as L
 from . import ops
+from .plan_pool import PlanPool, _storages
 
 _SEED = [0x3C6EF372]
 
@@ -85,68 +85,8 @@ class _Plan:
         self.sig, self.fwd_calls, self.bwd_calls = None, None, None
 
 
-_PLANS = []
-
-
-def _acquire(head, B, nS, nT, dev, hold):
-    key = (B, nS, nT)
-    for pl in _PLANS:
-        if pl.key == key and pl.dev == dev and not pl.busy:
-            pl.busy = hold
-            pl.gen = getattr(pl, "gen", 0) + 1
-            return pl
-    # never hand out a plan whose backward is still pending (its saved maps, statistics, dropout seeds and recorded pointers belong to
-    # that node): a further forward of the same shape gets a fresh plan, up to a hard cap.  Plans of nodes that are freed without a
-    # backward are released by the finalizer _hold() attaches to the node.
-    same = [pl for pl in _PLANS if pl.key == key and pl.dev == dev]
-    if len(same) >= MAX_LIVE_PLANS:
-        raise RuntimeError("%d forward passes of shape %r are waiting for their backward; run the backwards (or drop the graphs) "
-                           "before another forward of this shape" % (len(same), key))
-    idle = [pl for pl in _PLANS if not pl.busy]
-    if len(_PLANS) >= 8 and idle:
-        _PLANS.remove(idle[0])
-    pl = _Plan(head, B, nS, nT, dev)
-    pl.busy = hold
-    pl.gen = 1
-    _PLANS.append(pl)
-    return pl
-
-
-MAX_LIVE_PLANS = 16
-
-
-def _storages(*ts):
-    """What a plan keeps of the tensors its in-flight kernels read / write: the STORAGE (the memory stays allocated), never the tensor
-    object — an output tensor carries its grad_fn, and a plan that held it would keep its own autograd node (and through ctx.pl itself)
-    alive until the next forward of the shape, so a graph dropped without a backward could never hand its plan back."""
-    out = []
-    for t in ts:
-        if isinstance(t, (tuple, list)):
-            out.append(_storages(*t))
-        elif torch.is_tensor(t):
-            out.append(t.untyped_storage())
-        else:
-            out.append(t)
-    return tuple(out)
-
-
-def _release(pl, gen):
-    if pl.gen == gen:
-        pl.busy = False
-
-
-def _hold(ctx, pl):
-    """Ties the plan to the autograd node: generation stamp for the backward's ownership check, release when the node dies unused."""
-    ctx.pl, ctx.gen = pl, pl.gen
-    if pl.busy:
-        weakref.finalize(ctx, _release, pl, pl.gen)
-
-
-def _owned(ctx):
-    pl = ctx.pl
-    if pl.gen != ctx.gen:
-        raise RuntimeError("this node's plan was re-used by a later forward (generation %d, node holds %d): its saved activations are gone" % (pl.gen, ctx.gen))
-    return pl
+_POOL = PlanPool()
+_PLANS = _POOL.plans
 
 
 def _ptr(t):
@@ -484,15 +424,16 @@ def _backward(pl, head, d_logits, d_hidden, training):
 class _GraphFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, e_S, e_T, head, training, hold, *params):
-        pl = _acquire(head, e_S.shape[0], e_S.shape[1], e_T.shape[1], e_S.device, hold)
+        B, nS, nT, dev = e_S.shape[0], e_S.shape[1], e_T.shape[1], e_S.device
+        pl = _POOL.acquire((B, nS, nT), dev, hold, lambda: _Plan(head, B, nS, nT, dev))
         logits, hidden = _forward(pl, head, e_S.contiguous().float(), e_T.contiguous().float(), training)
-        _hold(ctx, pl)
+        _POOL.hold(ctx, pl)
         ctx.head, ctx.training = head, training
         return logits, hidden
 
     @staticmethod
     def backward(ctx, d_logits, d_hidden):
-        pl = _owned(ctx)
+        pl = _POOL.owned(ctx)
         try:
             deS, deT = _backward(pl, ctx.head, d_logits, d_hidden, ctx.training)
         finally:

@@ -19,13 +19,15 @@ import torch
 from torch import nn
 
 from . import encoder as ENC
+from . import hipnn
 from . import ops
-from .encoder import FIXED, Encoder, RowLayout, VarlenSets, W2VConfig, param_specs
-from .model_linear import SCORE_FP32, dropout_stream_seed, init_parameters_, loss_custom, maybe_load_pretrained
+from .encoder import FIXED, param_specs
+from .model_base import FlatModel, dropout_stream_seed, init_parameters_, run_plan
 from .ops import Op
-from .params import FlatParams, register_by_name
+from .params import register_by_name
 
 FEAT_DIM = 128
+SCORE_FP32 = os.environ.get("SCL_SCORE_FP32", "1") != "0"      # scoring runs fp32 end to end unless SCL_SCORE_FP32=0 (the linear plugin keeps a switch of its own)
 
 
 class _FrontFn(torch.autograd.Function):
@@ -59,7 +61,7 @@ class _HeadRunner(nn.Module):
         return self._fwd(self, feats)
 
 
-class FrontHeadModel(nn.Module):
+class FrontHeadModel(FlatModel):
     flag_fix_ssl = False
     head_takes_frames = False      # the back-end masks the padding of a variable-length batch: _head_forward(mod, feats, frames)
     front_prefix = ""        # module path of `ssl_model` / `LL` in the state dict ("backend." for wav2vec2_btse, backend.py:31-33)
@@ -83,26 +85,19 @@ class FrontHeadModel(nn.Module):
         return self.cfg.samples_for(self.head_min_frames())
 
     def __init__(self, args, device, is_train=True, w2v_cfg=None, seed=0, rank=0):
-        super().__init__()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("scl_amd.Model needs an MI355X device: the product path has no CPU fallback")
-        self.is_train = is_train
+        super().__init__(args, device, is_train, w2v_cfg)
         self.contra_mode = args.get("contra_mode", "all")
         self.loss_type = args.get("loss_type", 1)
-        if w2v_cfg is None:
-            w2v_cfg = W2VConfig.tiny() if args.get("w2v_arch", "xlsr_300m") == "tiny" else \
-                W2VConfig(encoder_layerdrop=float(args.get("encoder_layerdrop", 0.0)))
-        self.cfg = w2v_cfg
         rng_state = torch.get_rng_state()          # seeded head init without disturbing the caller's RNG stream
         torch.manual_seed(seed + 1)
         head = self._build_head(args)
         torch.set_rng_state(rng_state)
         head_params = list(head.named_parameters())
+        frozen = getattr(head, "frozen_names", ())      # no gradient in the reference
         specs = param_specs(self.cfg) + [("LL.weight", (FEAT_DIM, self.cfg.embed), True), ("LL.bias", (FEAT_DIM,), True)] + \
-            [(n, tuple(p.shape), n not in getattr(head, "frozen_names", ())) for n, p in head_params]      # frozen: no gradient in the reference
-        self.P = FlatParams(specs, self.device)
-        self._head_lo = self.P.off(next(n for n, _ in head_params if n not in getattr(head, "frozen_names", ())))
+            [(n, tuple(p.shape), n not in frozen) for n, p in head_params]
+        self._make_params(specs)
+        self._head_lo = self.P.off(next(n for n, _ in head_params if n not in frozen))
         init_parameters_(self.P, self.cfg, seed)
         for n, p in head_params:
             self.P.f32(n).copy_(p.detach().to(self.device))
@@ -123,48 +118,21 @@ class FrontHeadModel(nn.Module):
                     mod = mod._modules[part]
                 mod._parameters[parts[-1]] = p
         self.P.mark_dirty()
-        self.ssl = Encoder(self.cfg, self.P)
-        self._anchor = torch.zeros((), device=self.device, requires_grad=True)
-        self._states = {}
-        # variable-length scoring batches on the bf16 path: boundary buffers, frame counts and launch plans per padded shape, least
-        # recently used of at most encoder.VARLEN_SETS (every padded length of a --padding_type none run is a shape of its own); an
-        # evicted shape takes its encoder buffer set with it.  The fp32 scoring path keeps no state here (Encoder.forward_f32's own LRU).
-        self._vstates = VarlenSets(on_evict=lambda key: self.ssl._vbufs.pop(key, None))
-        self.out_dim = self.cfg.embed
-        self.grad_sync = None
         self._drop_step = dropout_stream_seed(seed, rank)      # encoder element-dropout masks differ per --seed and per data-parallel rank
         # Optional (SCL_HEAD_GRAPH=1): replay the back-end's training forward / backward as two captured hipGraphs per feature
         # shape.  Both HIP back-ends capture and replay correctly (tests/test_aasist_gpu.py), but the step is kernel-bound: AASIST
         # 45.9 -> 45.5 ms/step at batch 32, ResNet +-0.  Off by default.
         self.use_graphs = os.environ.get("SCL_HEAD_GRAPH", "0") == "1"
         self.__dict__["_graphed"] = {}
-        self.pretrained_loaded = maybe_load_pretrained(self, args)
+        self._finish_build(args)      # the fp32 scoring path keeps no state in the stores (Encoder.forward_f32's own LRU)
         if rank:      # torch dropout in the back-end: decorrelate the data-parallel ranks' masks
             torch.cuda.manual_seed(int(seed) * 1000003 + int(rank))
 
     def trainable_range(self):
         return 0, self.P.n_train
 
-    # nn.Module plumbing ----------------------------------------------------------------------------
-    def _apply(self, fn, recurse=True):
-        probe = fn(torch.zeros(1, device=self.device))
-        if probe.device != self.device or probe.dtype != torch.float32:
-            raise RuntimeError("scl_amd.Model lives in one flat fp32 device buffer; construct it on the target device")
-        return self
-
-    def load_state_dict(self, state_dict, strict=True):
-        from . import hipnn
-        r = super().load_state_dict(state_dict, strict=strict)
-        hipnn.weights_changed()
-        self.P.mark_dirty()
-        return r
-
-    def optimizer_stepped(self, bf16_fresh):
-        from . import hipnn
+    def _weights_changed(self):
         hipnn.weights_changed()      # the back-end's re-laid-out convolution weights are rebuilt on next use
-        self.P.mark_dirty()
-        if bf16_fresh:
-            self.P.bf16_version = self.P.version
 
     def zero_torch_grads(self):
         """The head's gradients are ACCUMULATED by torch autograd into the flat gradient buffer (the HIP backward
@@ -188,12 +156,7 @@ class FrontHeadModel(nn.Module):
             else:
                 st.update(frames=torch.ones(B, **i32), row0=torch.arange(B + 1, **i32) if layout.packed else None)
             return st
-        key = layout.key(B, L)
-        if not layout.fixed:
-            return self._vstates.get_or_make(key, make)
-        if key not in self._states:
-            self._states[key] = make()
-        return self._states[key]
+        return self._shape_state(layout.key(B, L), make, layout)
 
     def _front_forward(self, x, layout=FIXED):
         """Encoder (bf16 kernels) + LL on the shape's state, recorded once per plan key and replayed.  A variable-length batch is scored,
@@ -205,34 +168,28 @@ class FrontHeadModel(nn.Module):
         seed = 0
         if layout.fixed:
             self._drop_step = seed = (self._drop_step * 1664525 + 1013904223) & 0x7FFFFFFF
-        else:      # into the state's buffers, which the recorded plans read
-            st["frames"].copy_(layout.frames)
-            if layout.packed:
-                st["row0"].copy_(layout.row0)
-            layout = RowLayout(st["frames"], st["row0"], layout.Mq)
+        else:
+            layout = self._bind_layout(st, layout)
         self.ssl.refresh_weights()
         use_plan = self.cfg.encoder_layerdrop == 0 or not ssl_train
         pk = layout.plan_key("fwd", ssl_train)
-        plan = st["plans"].get(pk) if use_plan else None
-        if plan is not None:
-            ectx = plan["saved"]["ectx"]
-            self.ssl.apply_seeds(ectx["drop_slots"], seed)      # the encoder's element-dropout sites (none at p = 0)
-            ops.replay(plan["calls"])
-            return st["feats"], dict(plan["saved"], ectx=dict(ectx, step_seed=seed))
-        if use_plan:
-            ops.start_recording()
-        P, E = self.P, self.cfg.embed
-        enc_out, ectx = self.ssl.forward(st["x"], training=ssl_train, refresh=False, step_seed=seed,
-                                         grad=None if layout.fixed else False, **layout.args)
-        M = B * st["T"]
-        # the bf16 primary output of the GEMM is not needed here: it lands in dfe_bf, which the backward overwrites
-        ops.gemm(Op(enc_out, E), Op(P.bf16, E, offset=P.off("LL.weight")), st["dfe_bf"], M, FEAT_DIM, E, bias=P.f32("LL.bias"),
-                 c2=st["feats"])
-        if not layout.fixed:
-            ops.zero_tail_rows(st["feats"], layout.frames, B, st["T"], FEAT_DIM)
-        saved = dict(ectx=ectx, st=st, enc_out=enc_out, B=B)
-        if use_plan:
-            st["plans"][pk] = dict(calls=ops.stop_recording(), saved=saved)
+
+        def build():
+            P, E = self.P, self.cfg.embed
+            enc_out, ectx = self.ssl.forward(st["x"], training=ssl_train, refresh=False, step_seed=seed,
+                                             grad=None if layout.fixed else False, **layout.args)
+            M = B * st["T"]
+            # the bf16 primary output of the GEMM is not needed here: it lands in dfe_bf, which the backward overwrites
+            ops.gemm(Op(enc_out, E), Op(P.bf16, E, offset=P.off("LL.weight")), st["dfe_bf"], M, FEAT_DIM, E, bias=P.f32("LL.bias"),
+                     c2=st["feats"])
+            if not layout.fixed:
+                ops.zero_tail_rows(st["feats"], layout.frames, B, st["T"], FEAT_DIM)
+            return dict(saved=dict(ectx=ectx, st=st, enc_out=enc_out, B=B))
+        # replay: the encoder's element-dropout sites (none at p = 0) take this step's seed
+        plan, replayed = run_plan(st["plans"], pk, use_plan, lambda plan: self.ssl.apply_seeds(plan["saved"]["ectx"]["drop_slots"], seed), build)
+        saved = plan["saved"]
+        if replayed:
+            saved = dict(saved, ectx=dict(saved["ectx"], step_seed=seed))
         return st["feats"], saved
 
     def _front_f32(self, x, layout=FIXED):
@@ -254,25 +211,20 @@ class FrontHeadModel(nn.Module):
             self.ssl.on_grads_ready = self.grad_sync.ready_above
         use_plan = not sv["ectx"]["skipped"] and self.cfg.encoder_layerdrop == 0
         pk = ("bwd", self.grad_sync is not None)
-        plan = st["plans"].get(pk) if use_plan else None
-        if plan is not None:
-            self.ssl.apply_seeds(plan["enc_slots"], sv["ectx"]["step_seed"])
-            ops.replay(plan["calls"])
-            return
-        if use_plan:
-            ops.start_recording()
-        enc_slots = []
-        M = sv["B"] * st["T"]
-        ops.cast_bf16(st["d_feats"], st["dfe_bf"], M * FEAT_DIM)
-        ops.colsum_reduce(st["d_feats"], st["cs"], P.g("LL.bias"), M, FEAT_DIM)
-        self.ssl._wgrad(sv["ectx"]["d"], Op(st["dfe_bf"], FEAT_DIM), Op(sv["enc_out"], E), P.g("LL.weight"), FEAT_DIM, E, M)
-        if not self.flag_fix_ssl:
-            ops.gemm(Op(st["dfe_bf"], FEAT_DIM), Op(P.bf16, E, offset=P.off("LL.weight")), st["denc"], M, E, FEAT_DIM, b_t=True)
-            if self.grad_sync is not None:     # LL and the torch head's gradients (the END of the flat buffer) are final here
-                ops.host_callback(self.grad_sync.ready_above, P.off("LL.weight"))
-            enc_slots = self.ssl.backward(sv["ectx"], st["denc"])
-        if use_plan:
-            st["plans"][pk] = dict(calls=ops.stop_recording(), enc_slots=enc_slots)
+
+        def build():
+            enc_slots = []
+            M = sv["B"] * st["T"]
+            ops.cast_bf16(st["d_feats"], st["dfe_bf"], M * FEAT_DIM)
+            ops.colsum_reduce(st["d_feats"], st["cs"], P.g("LL.bias"), M, FEAT_DIM)
+            self.ssl._wgrad(sv["ectx"]["d"], Op(st["dfe_bf"], FEAT_DIM), Op(sv["enc_out"], E), P.g("LL.weight"), FEAT_DIM, E, M)
+            if not self.flag_fix_ssl:
+                ops.gemm(Op(st["dfe_bf"], FEAT_DIM), Op(P.bf16, E, offset=P.off("LL.weight")), st["denc"], M, E, FEAT_DIM, b_t=True)
+                if self.grad_sync is not None:     # LL and the torch head's gradients (the END of the flat buffer) are final here
+                    ops.host_callback(self.grad_sync.ready_above, P.off("LL.weight"))
+                enc_slots = self.ssl.backward(sv["ectx"], st["denc"])
+            return dict(enc_slots=enc_slots)
+        run_plan(st["plans"], pk, use_plan, lambda plan: self.ssl.apply_seeds(plan["enc_slots"], sv["ectx"]["step_seed"]), build)
 
     # forward / loss --------------------------------------------------------------------------------
     VARLEN_REFUSAL = ("variable-length batches (forward(x, lengths), main.py --padding_type none) are implemented for the "

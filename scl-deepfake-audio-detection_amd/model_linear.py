@@ -14,7 +14,6 @@ backend.m_frame_level.{0,3,6}.*, backend.m_utt_level.*), so its checkpoints load
 `train_loss.backward()` reaches the hand-written backward through two torch.autograd.Function
 boundaries (model, loss); parameter gradients are written straight into the flat gradient buffer.
 """
-import math
 import os
 
 import torch
@@ -22,12 +21,12 @@ from torch import nn
 
 from . import encoder as ENC
 from . import ops
-from .encoder import FIXED, Encoder, RowLayout, VarlenSets, W2VConfig, param_specs
+from .encoder import FIXED, param_specs
 from .lib import ACT_LEAKY, ACT_RELU
+from .model_base import HEAD_DIM, FlatModel, dropout_stream_seed, init_parameters_, maybe_load_pretrained, run_plan  # noqa: F401
 from .ops import Op
-from .params import FlatParams, register_by_name
+from .params import register_by_name
 
-HEAD_DIM = 128
 N_CLASS = 2
 # scoring (model.eval() under torch.no_grad(): main.py --eval / --predict / --emb, the validation pass) runs fp32 end to end unless
 # SCL_SCORE_FP32=0 asks for the bf16-operand training kernels (about 8x faster forward, scores to ~1e-2)
@@ -44,54 +43,6 @@ def head_specs(embed):
             ("backend.m_frame_level.3.weight", (HEAD_DIM, HEAD_DIM), True), ("backend.m_frame_level.3.bias", (HEAD_DIM,), True),
             ("backend.m_frame_level.6.weight", (HEAD_DIM, HEAD_DIM), True), ("backend.m_frame_level.6.bias", (HEAD_DIM,), True),
             ("backend.m_utt_level.weight", (N_CLASS, HEAD_DIM), True), ("backend.m_utt_level.bias", (N_CLASS,), True)]
-
-
-def init_parameters_(P, cfg, seed=0):
-    """Seeded random init at the right shapes (no checkpoint ships with the repo): kaiming-normal convs
-    and N(0, 0.02) linears for the encoder, torch's default uniform for the head."""
-    g = torch.Generator().manual_seed(seed)
-    for name, (o, n, shape, tr) in P.index.items():
-        short = name.split("ssl_model.model.")[-1]
-        if short.endswith("2.1.weight") or "layer_norm.weight" in short:
-            t = torch.ones(shape)
-        elif short.endswith("2.1.bias") or "layer_norm.bias" in short:
-            t = torch.zeros(shape)
-        elif "conv_layers" in short and short.endswith("0.weight"):
-            t = torch.randn(shape, generator=g) * math.sqrt(2.0 / (shape[1] * shape[2]))
-        elif short == "encoder.pos_conv.0.weight_v":
-            t = torch.randn(shape, generator=g) * math.sqrt(4.0 / (cfg.pos_k * cfg.embed))
-        elif short == "encoder.pos_conv.0.weight_g":
-            continue
-        elif name.startswith("LL.") or name.startswith("backend."):
-            fan_in = shape[-1] if len(shape) > 1 else HEAD_DIM
-            t = (torch.rand(shape, generator=g) * 2 - 1) / math.sqrt(fan_in)
-        elif short.endswith(".bias"):
-            t = torch.zeros(shape)
-        else:
-            t = 0.02 * torch.randn(shape, generator=g)
-        P.f32(name).copy_(t.to(P.device))
-    v = P.f32("ssl_model.model.encoder.pos_conv.0.weight_v")
-    P.f32("ssl_model.model.encoder.pos_conv.0.weight_g").copy_(v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt())
-    P.mark_dirty()
-
-
-def dropout_stream_seed(seed, rank):
-    return (int(seed) * 2654435761 + int(rank) * 40503 + 12345) & 0x7FFFFFFF
-
-
-def maybe_load_pretrained(model, args):
-    """The reference's SSLModel loads pretrained/xlsr2_300m.pt at construction (model/xlsr.py:14-16).  Do the same when the file
-    (or the YAML's optional `pretrained:` path) exists; take encoder_layerdrop from its cfg unless the YAML overrides it."""
-    from . import checkpoint
-    explicit = hasattr(args, "get") and args.get("pretrained")
-    path = explicit or checkpoint.DEFAULT_PRETRAINED
-    if not os.path.exists(path) or (not explicit and model.cfg.layers != 24):     # toy encoders never pick up the default file
-        return False
-    probs = checkpoint.load_pretrained_into(model, path)
-    if "encoder_layerdrop" in probs and "encoder_layerdrop" not in args:
-        model.cfg.encoder_layerdrop = probs["encoder_layerdrop"]
-    print("[scl] XLS-R weights loaded from %s (encoder_layerdrop %.3f)" % (path, model.cfg.encoder_layerdrop))
-    return True
 
 
 class _ModelFn(torch.autograd.Function):
@@ -112,67 +63,32 @@ class _ModelFn(torch.autograd.Function):
         return None, None, None, None
 
 
-class Model(nn.Module):
+class Model(FlatModel):
     def __init__(self, args, device, is_train=True, w2v_cfg=None, seed=0, rank=0):
-        super().__init__()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("scl_amd.Model needs an MI355X device: the product path has no CPU fallback")
-        self.is_train = is_train
+        super().__init__(args, device, is_train, w2v_cfg)
         self.flag_fix_ssl = args["flag_fix_ssl"]
         self.contra_mode = args["contra_mode"]
         self.loss_type = args["loss_type"]
         if self.contra_mode not in ("all", "one"):
             raise ValueError("Unknown mode: {}".format(self.contra_mode))     # loss_metrics.py:161
-        if w2v_cfg is None:
-            # optional YAML key `w2v_arch`: "xlsr_300m" (default, the reference's only encoder) or "tiny" (tests / plumbing)
-            w2v_cfg = W2VConfig.tiny() if args.get("w2v_arch", "xlsr_300m") == "tiny" else \
-                W2VConfig(encoder_layerdrop=float(args.get("encoder_layerdrop", 0.0)))
-        self.cfg = w2v_cfg
-        specs = param_specs(self.cfg) + head_specs(self.cfg.embed)
         # memory order: trainable encoder, head, then the checkpoint-only tensors (FlatParams puts those last)
-        self.P = FlatParams(specs, self.device)
+        self._make_params(param_specs(self.cfg) + head_specs(self.cfg.embed))
         for name, p in self.P.params.items():
             register_by_name(self, name, p)
         # defined-but-unused modules of the reference (linear_nll:108-109) — state-dict compatibility only
         self.first_bn = nn.BatchNorm2d(num_features=1).to(self.device)
         self.first_bn1 = nn.BatchNorm2d(num_features=64).to(self.device)
         init_parameters_(self.P, self.cfg, seed)
-        self.encoder = Encoder(self.cfg, self.P)
-        self._anchor = torch.zeros((), device=self.device, requires_grad=True)
         self._hbufs = {}
-        self._states = {}
-        # variable-length scoring batches (forward(x, lengths)): state, head buffers and launch plans per padded shape, least recently
-        # used of at most four; an evicted shape takes its encoder buffer set with it
-        self._vstates = VarlenSets(on_evict=lambda key: self.encoder._vbufs.pop(key, None))
-        self._vstates_train = {}      # variable-length training batches: one padded shape per run (the data path pads to trim_length), kept
         self._step_seed = dropout_stream_seed(seed, rank)   # head dropout masks differ per --seed and per data-parallel rank
-        self.out_dim = self.cfg.embed
-        self.grad_sync = None   # scl_amd.parallel.GradSync when data-parallel (set by FusedAdamW)
-        self.pretrained_loaded = maybe_load_pretrained(self, args)
+        self._finish_build(args)
+
+    encoder = property(lambda self: self.ssl)      # read-only alias of FlatModel.ssl: there is no setter, `m.encoder = ...` raises
 
     def trainable_range(self):
         """[lo, hi) of the flat buffer that receives gradients: with flag_fix_ssl the encoder backward is skipped, and
         torch.optim.AdamW in the reference leaves parameters whose .grad is None untouched (no weight decay, no all-reduce)."""
         return (self.P.off("LL.weight") if self.flag_fix_ssl else 0), self.P.n_train
-
-    # nn.Module plumbing ----------------------------------------------------------------------------
-    def _apply(self, fn, recurse=True):
-        # .to(device) / .cuda() on an already-placed model must not break the flat-buffer views
-        probe = fn(torch.zeros(1, device=self.device))
-        if probe.device != self.device or probe.dtype != torch.float32:
-            raise RuntimeError("scl_amd.Model lives in one flat fp32 device buffer; construct it on the target device")
-        return self
-
-    def load_state_dict(self, state_dict, strict=True):
-        r = super().load_state_dict(state_dict, strict=strict)
-        self.P.mark_dirty()
-        return r
-
-    def optimizer_stepped(self, bf16_fresh):
-        self.P.mark_dirty()
-        if bf16_fresh:
-            self.P.bf16_version = self.P.version
 
     # forward ---------------------------------------------------------------------------------------
     def _head_bufs(self, B, T, keep=True):
@@ -213,13 +129,7 @@ class Model(nn.Module):
                 st.update(frames=torch.ones(B, **i32), row0=torch.arange(B + 1, **i32) if layout.packed else None,
                           hb=self._head_bufs(B, T, keep=False))
             return st
-        key = layout.key(B, L)
-        if not layout.fixed and not train:
-            return self._vstates.get_or_make(key, make)
-        store = self._states if layout.fixed else self._vstates_train
-        if key not in store:
-            store[key] = make()
-        return store[key]
+        return self._shape_state(layout.key(B, L), make, layout, train)
 
     def min_samples(self):
         """The shortest row forward(x, lengths) takes (main.py --padding_type none pads shorter files to it): one frame."""
@@ -231,11 +141,8 @@ class Model(nn.Module):
         training = bool(self.training)
         ssl_train = False if self.flag_fix_ssl else bool(self.is_train and training)
         st = self._state(B, L, layout, train)
-        if not layout.fixed:      # into the state's buffers, which the recorded plans read
-            st["frames"].copy_(layout.frames)
-            if layout.packed:
-                st["row0"].copy_(layout.row0)
-            layout = RowLayout(st["frames"], st["row0"], layout.Mq)
+        if not layout.fixed:
+            layout = self._bind_layout(st, layout)
         st["x"].copy_(x)
         drop = DROP_P if training else 0.0
         self._step_seed = (self._step_seed * 1664525 + 1013904223) & 0x7FFFFFFF
@@ -243,20 +150,19 @@ class Model(nn.Module):
         self.encoder.refresh_weights()
         use_plan = self.cfg.encoder_layerdrop == 0 or not ssl_train
         pk = layout.plan_key("fwd", training, ssl_train)
-        plan = st["plans"].get(pk) if use_plan else None
-        if plan is not None:
+
+        def patch(plan):
             for dsc, sd in zip(plan["drop_descs"], seeds):
                 dsc.drop_seed = sd
-            ectx = plan["saved"]["ectx"]
-            self.encoder.apply_seeds(ectx["drop_slots"], self._step_seed)      # the encoder's element-dropout sites (none at p = 0)
-            ops.replay(plan["calls"])
-            saved = dict(plan["saved"], seeds=seeds, ectx=dict(ectx, step_seed=self._step_seed))
-            return st["logp"], st["feats"], st["emb"], saved
-        if use_plan:
-            ops.start_recording()
-        saved, drop_descs = self._forward_kernels(st, B, L, ssl_train, drop, seeds, layout)
-        if use_plan:
-            st["plans"][pk] = dict(calls=ops.stop_recording(), drop_descs=drop_descs, saved=saved)
+            self.encoder.apply_seeds(plan["saved"]["ectx"]["drop_slots"], self._step_seed)      # the encoder's element-dropout sites (none at p = 0)
+
+        def build():
+            saved, drop_descs = self._forward_kernels(st, B, L, ssl_train, drop, seeds, layout)
+            return dict(drop_descs=drop_descs, saved=saved)
+        plan, replayed = run_plan(st["plans"], pk, use_plan, patch, build)
+        saved = plan["saved"]
+        if replayed:      # the recorded step's context with this step's seed; a first run hands on the encoder's own
+            saved = dict(saved, ectx=dict(saved["ectx"], step_seed=self._step_seed))
         return st["logp"], st["feats"], st["emb"], dict(saved, seeds=seeds)
 
     def _forward_kernels(self, st, B, L, ssl_train, drop, seeds, layout):
@@ -300,19 +206,13 @@ class Model(nn.Module):
             self.encoder.on_grads_ready = self.grad_sync.ready_above
         use_plan = not sv["ectx"]["skipped"] and self.cfg.encoder_layerdrop == 0
         pk = sv["ectx"]["layout"].plan_key("bwd", sv["drop"] > 0, self.grad_sync is not None)      # the row offsets are the state's, already in place
-        plan = st["plans"].get(pk) if use_plan else None
-        if plan is not None:
+
+        def patch(plan):
             plan["drop_descs"][0].drop_seed = seeds[1]
             plan["drop_descs"][1].drop_seed = seeds[0]
             plan["meanpool_entry"][1][plan["meanpool_seed_pos"]] = seeds[2]
             self.encoder.apply_seeds(plan["enc_slots"], sv["ectx"]["step_seed"])
-            ops.replay(plan["calls"])
-            return
-        if use_plan:
-            ops.start_recording()
-        extra = self._backward_kernels(sv, st, seeds)
-        if use_plan:
-            st["plans"][pk] = dict(calls=ops.stop_recording(), **extra)
+        run_plan(st["plans"], pk, use_plan, patch, lambda: self._backward_kernels(sv, st, seeds))
 
     def _backward_kernels(self, sv, st, seeds):
         P, E = self.P, self.cfg.embed

@@ -13,12 +13,12 @@ still updated in training — here from the statistics the previous block's conv
 computed (it is round-off around zero: BatchNorm cancels the bias) because the reference computes it.
 """
 import ctypes
-import weakref
 
 import torch
 
 from . import lib as L
 from . import ops
+from .plan_pool import PlanPool, _storages
 
 _SIZES = {(16, 32), (32, 32), (32, 64), (64, 64)}
 
@@ -103,68 +103,15 @@ class _Plan:
         return self.at
 
 
-_PLANS = []
+_POOL = PlanPool()
+_PLANS = _POOL.plans
+MAX_LIVE_PLANS = PlanPool.MAX_LIVE_PLANS
 
 
-def _acquire(B, H, W, chans, dev, hold):
-    key = (B, H, W, tuple(chans))
-    for pl in _PLANS:
-        if pl.key == key and pl.dev == dev and not pl.busy:
-            pl.busy = hold
-            pl.gen = getattr(pl, "gen", 0) + 1
-            return pl
-    # never hand out a plan whose backward is still pending (its saved maps, statistics, dropout seeds and recorded pointers belong to
-    # that node): a further forward of the same shape gets a fresh plan, up to a hard cap.  Plans of nodes that are freed without a
-    # backward are released by the finalizer _hold() attaches to the node.
-    same = [pl for pl in _PLANS if pl.key == key and pl.dev == dev]
-    if len(same) >= MAX_LIVE_PLANS:
-        raise RuntimeError("%d forward passes of shape %r are waiting for their backward; run the backwards (or drop the graphs) "
-                           "before another forward of this shape" % (len(same), key))
-    idle = [pl for pl in _PLANS if not pl.busy]
-    if len(_PLANS) >= 8 and idle:
-        _PLANS.remove(idle[0])
-    pl = _Plan(B, H, W, chans, dev)
-    pl.busy = hold
-    pl.gen = 1
-    _PLANS.append(pl)
-    return pl
-
-
-MAX_LIVE_PLANS = 16
-
-
-def _storages(*ts):
-    """What a plan keeps of the tensors its in-flight kernels read / write: the STORAGE (the memory stays allocated), never the tensor
-    object — an output tensor carries its grad_fn, and a plan that held it would keep its own autograd node (and through ctx.pl itself)
-    alive until the next forward of the shape, so a graph dropped without a backward could never hand its plan back."""
-    out = []
-    for t in ts:
-        if isinstance(t, (tuple, list)):
-            out.append(_storages(*t))
-        elif torch.is_tensor(t):
-            out.append(t.untyped_storage())
-        else:
-            out.append(t)
-    return tuple(out)
-
-
-def _release(pl, gen):
-    if pl.gen == gen:
-        pl.busy = False
-
-
-def _hold(ctx, pl):
-    """Ties the plan to the autograd node: generation stamp for the backward's ownership check, release when the node dies unused."""
-    ctx.pl, ctx.gen = pl, pl.gen
-    if pl.busy:
-        weakref.finalize(ctx, _release, pl, pl.gen)
-
-
-def _owned(ctx):
-    pl = ctx.pl
-    if pl.gen != ctx.gen:
-        raise RuntimeError("this node's plan was re-used by a later forward (generation %d, node holds %d): its saved activations are gone" % (pl.gen, ctx.gen))
-    return pl
+def _plan_for(x0, blocks, hold):
+    B, H, W, _ = x0.shape
+    chans = [blocks[0].conv1.weight.shape[1]] + [b.conv1.weight.shape[0] for b in blocks]
+    return _POOL.acquire((B, H, W, tuple(chans)), x0.device, hold, lambda: _Plan(B, H, W, chans, x0.device))
 
 
 def _stream():
@@ -440,17 +387,15 @@ def _backward(pl, d_out, blocks, training, need_dx0, attn=None):
 class _ResStackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, blocks, training, hold, *params):
-        B, H, W, _ = x0.shape
-        chans = [blocks[0].conv1.weight.shape[1]] + [b.conv1.weight.shape[0] for b in blocks]
-        pl = _acquire(B, H, W, chans, x0.device, hold)
+        pl = _plan_for(x0, blocks, hold)
         out = _forward(pl, x0.contiguous().float(), blocks, training)
-        _hold(ctx, pl)
+        _POOL.hold(ctx, pl)
         ctx.blocks, ctx.training = blocks, training
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        pl = _owned(ctx)
+        pl = _POOL.owned(ctx)
         try:
             dx0 = _backward(pl, d_out, ctx.blocks, ctx.training, ctx.needs_input_grad[0])
         finally:
@@ -461,17 +406,15 @@ class _ResStackFn(torch.autograd.Function):
 class _StackPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, blocks, attn, training, hold, *params):
-        B, H, W, _ = x0.shape
-        chans = [blocks[0].conv1.weight.shape[1]] + [b.conv1.weight.shape[0] for b in blocks]
-        pl = _acquire(B, H, W, chans, x0.device, hold)
+        pl = _plan_for(x0, blocks, hold)
         e_S, e_T = _forward(pl, x0.contiguous().float(), blocks, training, attn)
-        _hold(ctx, pl)
+        _POOL.hold(ctx, pl)
         ctx.blocks, ctx.training, ctx.attn = blocks, training, attn
         return e_S, e_T
 
     @staticmethod
     def backward(ctx, deS, deT):
-        pl = _owned(ctx)
+        pl = _POOL.owned(ctx)
         try:
             dx0 = _backward(pl, (deS, deT), ctx.blocks, ctx.training, ctx.needs_input_grad[0], ctx.attn)
         finally:

@@ -8,7 +8,7 @@ outputs are equal (both on the same libscl_hip.so, SCL_LIB_PATH); the "# counts"
 Python's cyclic collector is off while a case runs: when it runs depends on how many container objects the host code has allocated, and
 it decides when a temporary held in a reference cycle goes back to torch's caching allocator, that is, which later buffer aliases it.
 
-    python tools/launch_log.py [--cases small,other,resnet,aasist,xlsr] > launches.txt
+    python tools/launch_log.py [--cases small,other,resnet,aasist,btse,xlsr] > launches.txt
 """
 import argparse
 import ctypes
@@ -125,9 +125,9 @@ def batch(B, L, lengths=None, seed=0):
     return x.cuda()
 
 
-def train(m, x, lengths=None):
+def train(m, x, lengths=None, extra=()):
     def step():
-        out = m(x, lengths=lengths) if lengths is not None else m(x)
+        out = m(x, lengths=lengths) if lengths is not None else m(x, *extra)
         torch.autograd.backward(list(out), [torch.ones_like(o) for o in out])
     m.train()
     return step
@@ -203,6 +203,18 @@ def case_aasist(dev):
     run("aasist tiny 4x20000 train", m, train(m, batch(4, 20000)))
 
 
+def case_btse(dev):
+    import numpy as np
+    from oracle import btse as OB
+    from scl_amd.model_btse import Model
+    switches(False, True)
+    m = Model(dict(OB.default_args(), name="wav2vec2_btse"), dev, w2v_cfg=W2VConfig.tiny())
+    B, Lt = 6, 23      # tests/test_btse_gpu.py: 23-token bio sequences, two of them shorter
+    bio = torch.from_numpy(np.random.RandomState(3).randint(0, 3, size=(B, Lt)).astype(np.int32))
+    lens = torch.tensor([Lt, Lt, 7, Lt, 1, Lt], dtype=torch.int32)
+    run("btse tiny 6x8000 train", m, train(m, batch(B, 8000), extra=(bio, lens)))
+
+
 def case_xlsr(dev):
     switches(False, True)
     m = ML.Model(LINEAR, dev, w2v_cfg=W2VConfig())
@@ -211,7 +223,7 @@ def case_xlsr(dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cases", default="small,other,resnet,aasist,xlsr")
+    ap.add_argument("--cases", default="small,other,resnet,aasist,btse,xlsr")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     for name in args.cases.split(","):
