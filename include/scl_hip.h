@@ -234,6 +234,27 @@ int scl_bn_bwd(const float* dy, const float* y, const float* x, const float* mea
  * there (it may hold NaN / Inf).  mean / rstd [C]: scratch, written.  One apply launch, no zeroing pass.  C a power of two <= 2048; C % 4 == 0: 16-byte aligned pointers. */
 int scl_bn_eval_masked(const float* x, int B, int H, int W, int C, const float* gamma, const float* beta, const float* running_mean,
                        const float* running_var, float eps, int act, const int32_t* valid, float* mean, float* rstd, float* y, void* stream);
+/* Train-mode BatchNorm + activation of a zero-padded variable-length batch of maps x [B, H, W, C]: utterance b owns the rows h < valid[b]
+ * (int32 [B] on the GPU, clamped to 0..H as scl_bn_eval_masked clamps) and N_v = W * sum_b valid[b] is counted on the device from that array.
+ * Mean and biased variance per channel over the N_v valid positions only (fixed-order reduction, fp64 partials, no atomics: two runs give the
+ * same bits; rows at or beyond valid[b] are not loaded, so NaN / Inf there reach nothing); y = act((x - mean) * rstd * gamma + beta) for
+ * h < valid[b] and exactly +0.0f beyond, by selection.  running_mean / running_var (may be NULL) move with `momentum` and the unbiased variance
+ * N_v / (N_v - 1) (the plain variance when N_v == 1), num_batches_tracked (may be NULL) goes up by 1: scl_bn_fwd's finish with N = N_v.
+ * valid_host: the same B counts in host memory, read by this call only to refuse a batch without any valid position (every count <= 0).
+ * part: scratch of scl_bn_masked_nslabs(B, H, W) * 2 * C DOUBLES (8-byte aligned): blockIdx.y is the utterance, a slab is bn_slab_rows of the
+ * padded batch and ends where the utterance's valid rows end.  mean / rstd [C]: written, kept for the backward.  C divides 256 or is 512;
+ * C % 4 == 0: 16-byte aligned pointers; B <= 65535; H * W * C and B * H * W below 2^31. */
+int scl_bn_masked_nslabs(int B, int H, int W);
+int scl_bn_fwd_masked(const float* x, int B, int H, int W, int C, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, long long* num_batches_tracked, float momentum, float eps, int act, const int32_t* valid,
+                      const int32_t* valid_host, float* part, float* mean, float* rstd, float* y, void* stream);
+/* backward of the above: dz = dy * act'(y) on the valid positions; dbeta = sum dz and dgamma = sum dz * xhat over them (either may be NULL;
+ * accumulate != 0: ADDED to, as scl_bn_bwd); dx = gamma * rstd * (dz - (sum dz + xhat * sum dz*xhat) / N_v) for h < valid[b] and exactly
+ * 0.0f beyond, selected by row (never by y == 0: SELU's derivative there is not 0).  dy, y and x are not read at or beyond valid[b].
+ * part: as above; sums: f32 [2 * C + 1] scratch (the two sums and 1 / N_v).  y may be NULL when act == 0. */
+int scl_bn_bwd_masked(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* gamma, int B,
+                      int H, int W, int C, int act, const int32_t* valid, const int32_t* valid_host, float* part, float* sums,
+                      float* dgamma, float* dbeta, float* dx, int accumulate, void* stream);
 /* src [rows, C] contiguous f32 -> mapped (padded / dilated) destination, f32 or bf16 (row mapping as scl_bn_fwd's y2) */
 int scl_pad_nhwc_f32(const float* src, int64_t rows, int C, void* dst, int dst_bf16, int m_W, int m_HW, int64_t m_bs, int64_t m_rs,
                      int64_t m_cs, int64_t m_base, void* stream);
@@ -253,6 +274,9 @@ int scl_avgpool_bwd(const float* dy, int B, int R, int C, float* dx, void* strea
 /* y[b][c] = sum_{h < valid[b], w} x[b][h][w][c] / (valid[b] * W) over x [B, H, W, C], valid as above with valid[b] >= 1 (validate on the host:
  * scl_varlen_check_lengths; a count of 0 yields 0).  Fixed order, no atomics: the bits of scl_avgpool_fwd on the slice [1, valid[b] * W, C] alone. */
 int scl_avgpool_fwd_masked(const float* x, const int32_t* valid, int B, int H, int W, int C, float* y, void* stream);
+/* its backward: dx[b][h][w][c] = dy[b][c] / (valid[b] * W) for h < valid[b] and exactly 0.0f beyond (dx [B, H, W, C], every element written).
+ * valid_host: the same counts in host memory; every one must be in 1..H.  C % 4 == 0: 16-byte aligned dy, dx; B <= 65535; H * W * C < 2^31. */
+int scl_avgpool_bwd_masked(const float* dy, const int32_t* valid, const int32_t* valid_host, int B, int H, int W, int C, float* dx, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* LayerNorm (+GELU), column reductions                                                        */

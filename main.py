@@ -31,7 +31,7 @@ from model.wav2vec2_btse import wav2vec2_btse
 
 MODEL_REGISTRY = {"wav2vec2_linear_nll": wav2vec2_linear_nll, "wav2vec2_aasist": wav2vec2_aasist, "wav2vec2_resnet_nll": wav2vec2_resnet_nll,
                   "wav2vec2_btse": wav2vec2_btse}
-VARLEN_MODELS = ("wav2vec2_linear_nll", "wav2vec2_resnet_nll")      # --padding_type none: the plugins whose forward takes `lengths`
+VARLEN_MODELS = ("wav2vec2_linear_nll", "wav2vec2_resnet_nll")      # --padding_type none / zero with --batch_size k: the plugins whose forward takes `lengths`
 
 
 class EarlyStop:
@@ -466,15 +466,16 @@ def main(argv=None):
     repeat = args.padding_type == "repeat"
     # --padding_type zero with several packs per step: the default collate cannot stack packs of different lengths, so every pack is
     # zero-padded to trim_length and comes with per-view sample counts; run_epoch hands them to the model, which masks the padding in the
-    # forward and the backward (training) or scores under the mask (validation).  The linear plugin only: the others take no lengths and
-    # keep their behaviour.  One pack per step needs no mask (a pack at its own length), --padding_type repeat has no padding.
+    # forward and the backward (training) or scores under the mask (validation).  The linear and the ResNet plugin (VARLEN_MODELS; the
+    # latter's clips are padded to the 17,680 samples its back-end needs): the others take no lengths and keep their behaviour.  One pack
+    # per step needs no mask (a pack at its own length), --padding_type repeat has no padding.
     pad_kw = {}
-    if args.padding_type == "zero" and args.batch_size > 1 and config["model"]["name"] == "wav2vec2_linear_nll":
+    if args.padding_type == "zero" and args.batch_size > 1 and config["model"]["name"] in VARLEN_MODELS:
         if model.cfg.embed // model.cfg.heads != 64:
             sys.exit("main.py: --padding_type zero with --batch_size %d masks the padding in the streaming attention, which takes 64-wide "
                      "heads (this encoder's are %d wide); use --padding_type repeat or --batch_size 1"
                      % (args.batch_size, model.cfg.embed // model.cfg.heads))
-        pad_kw = dict(pad_to_trim=True, min_samples=model.cfg.min_samples())
+        pad_kw = dict(pad_to_trim=True, min_samples=model.min_samples())
     # RawBoost parameter draws of the pack builder: "fast" = every builder thread's own numpy Generator, batched closed-form filter design,
     # ISD positions without a 64000-element permutation per clip (same distributions; scl_amd/augment.py); SCL_PACK_SAMPLER=reference =
     # the reference's draw-for-draw order on the global np.random stream (what the pack goldens pin; 0.5 ms more host time per clip), i.e.

@@ -5,6 +5,8 @@
 // F.adaptive_avg_pool2d of model/wav2vec2_aasist.py:377-433, 436-604, model/resnet.py:47-191, model/wav2vec2_resnet_nll.py:51-74 and
 // their autograd backward (main.py:79).  HBM-bound streaming kernels: 16-byte accesses when C % 4 == 0, fp32 throughout; statistics
 // are accumulated per 512-row slab in fp32 and combined over slabs in fp64 (the reference's CPU path accumulates in double).
+// Zero-padded variable-length batches [B][H][W][C] (utterance b owns the rows h < valid[b]): eval-mode BatchNorm and the average for scoring,
+// train-mode BatchNorm (statistics, running statistics and the backward sums over the valid rows only) and the average's backward for training.
 #include "common.h"
 
 namespace {
@@ -32,13 +34,13 @@ __device__ __forceinline__ float nn_act_grad_from_y(int act, float y) {
     return 1.f;
 }
 
-// partial (sum a, sum a*b) per slab and channel; a = f(row, c), b = g(row, c).  Thread t owns channel (t % C) when C <= 256 (C divides
+// partial (sum a, sum a*b) per slab and channel over the elements e0 <= e < e1 (both multiples of C; an empty range writes zeros), into slot
+// `slab` of part; a = f(row, c), b = g(row, c).  Thread t owns channel (t % C) when C <= 256 (C divides
 // 256), channels t and t + 256 when C == 512: consecutive threads read consecutive addresses.
 template <class F>
-__device__ __forceinline__ void slab_reduce(int N, int C, double* part, int slab_rows, F f) {
+__device__ __forceinline__ void slab_reduce(long long e0, long long e1, int C, double* part, int slab, F f) {
     __shared__ double red[2][256];
-    const int slab = blockIdx.x, t = threadIdx.x;
-    const long long e0 = (long long)slab * slab_rows * C, e1 = min((long long)(slab + 1) * slab_rows, (long long)N) * C;
+    const int t = threadIdx.x;
     const int nacc = C > 256 ? C / 256 : 1;
     for (int a = 0; a < nacc; ++a) {
         double s0 = 0.0, s1 = 0.0;      // fp64 from the first add: a scalar gradient such as first_bn.weight cancels 1e4 : 1
@@ -72,10 +74,9 @@ __device__ __forceinline__ void slab_reduce(int N, int C, double* part, int slab
 // (1024 / C rows) per trip, four trips in flight.  Round 5: the scalar form read three maps with 4-byte loads and ran the ResNet back-end's
 // BatchNorm backward statistics at 2.5 TB/s (19 launches x 82 us per step at batch 32).
 template <class F>
-__device__ __forceinline__ void slab_reduce4(int N, int C, double* part, int slab_rows, F f) {
+__device__ __forceinline__ void slab_reduce4(long long e0, long long e1, int C, double* part, int slab, F f) {
     __shared__ double red4[2][4][256];
-    const int slab = blockIdx.x, t = threadIdx.x;
-    const long long e0 = (long long)slab * slab_rows * C, e1 = min((long long)(slab + 1) * slab_rows, (long long)N) * C;
+    const int t = threadIdx.x;
     const int ch = (4 * t) & (C - 1);
     const long long step = 1024;
     double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
@@ -107,20 +108,22 @@ __device__ __forceinline__ void slab_reduce4(int N, int C, double* part, int sla
 }
 
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int N, int C, double* __restrict__ part, int slab_rows) {
+    const int slab = blockIdx.x;
+    const long long e0 = (long long)slab * slab_rows * C, e1 = min((long long)(slab + 1) * slab_rows, (long long)N) * C;
     if (C >= 4) {
-        slab_reduce4(N, C, part, slab_rows, [&](long long e, int, float4& u, float4& v) {
+        slab_reduce4(e0, e1, C, part, slab, [&](long long e, int, float4& u, float4& v) {
             u = *reinterpret_cast<const float4*>(x + e);
             v = make_float4(u.x * u.x, u.y * u.y, u.z * u.z, u.w * u.w);
         });
         return;
     }
-    slab_reduce(N, C, part, slab_rows, [&](long long e, int, float& u, float& v) { const float a = x[e]; u = a; v = a * a; });
+    slab_reduce(e0, e1, C, part, slab, [&](long long e, int, float& u, float& v) { const float a = x[e]; u = a; v = a * a; });
 }
 
 // mean / rstd from the slab partials (training) or from the running statistics (eval); training also updates the running
 // statistics with momentum (unbiased variance, as torch) and num_batches_tracked
 // 64 channels per block x 16 slab lanes: the slab loop is split sixteen ways and combined through LDS (fp64)
-__global__ __launch_bounds__(1024) void bn_finish_kernel(const double* __restrict__ part, int nslab, int N, int C, float eps, float momentum, int training,
+__device__ __forceinline__ void bn_finish_body(const double* __restrict__ part, int nslab, long long N, int C, float eps, float momentum, int training,
                                  float* __restrict__ running_mean, float* __restrict__ running_var, long long* __restrict__ nbt,
                                  float* __restrict__ mean, float* __restrict__ rstd) {
     __shared__ double red[2][16][64];
@@ -150,6 +153,66 @@ __global__ __launch_bounds__(1024) void bn_finish_kernel(const double* __restric
         running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
     }
     if (nbt && c == 0) *nbt += 1;
+}
+__global__ __launch_bounds__(1024) void bn_finish_kernel(const double* __restrict__ part, int nslab, int N, int C, float eps, float momentum, int training,
+                                 float* __restrict__ running_mean, float* __restrict__ running_var, long long* __restrict__ nbt,
+                                 float* __restrict__ mean, float* __restrict__ rstd) {
+    bn_finish_body(part, nslab, N, C, eps, momentum, training, running_mean, running_var, nbt, mean, rstd);
+}
+
+// ---- batch statistics over the VALID rows of a zero-padded variable-length batch [B][H][W][C] (utterance b owns the rows h < valid[b]) ----
+// One clamp and one count for every masked kernel: the apply kernels, the statistics and the finishing kernels all go through these two.
+__device__ __forceinline__ int valid_rows(const int* __restrict__ valid, int b, int H) {
+    const int v = valid[b];
+    return v < 0 ? 0 : (v > H ? H : v);          // the host validates; a stale count must still stay inside the map
+}
+// N_v = W * sum_b valid[b], by all 1024 threads of a finishing block (fixed order: integers); at least 1, so that nothing divides by zero
+// if the device counts are all zero against the host's check
+__device__ __forceinline__ long long valid_positions(const int* __restrict__ valid, int B, int H, int W) {
+    __shared__ long long cnt[1024];
+    long long n = 0;
+    for (int b = threadIdx.x; b < B; b += 1024) n += valid_rows(valid, b, H);
+    cnt[threadIdx.x] = n;
+    __syncthreads();
+    for (int k = 512; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) cnt[threadIdx.x] += cnt[threadIdx.x + k];
+        __syncthreads();
+    }
+    n = cnt[0] * W;
+    return n < 1 ? 1 : n;
+}
+// The statistics partition: blockIdx.y is the utterance, blockIdx.x one of its nslab_u slabs of slab_rows rows (bn_slab_rows of the whole
+// padded batch, so the finishing kernels walk about as many partials as for the fixed-length map).  A slab ends where the utterance's valid
+// rows end: rows at or beyond valid[b] are not loaded, and a slab that lies wholly beyond writes zero partials.
+__device__ __forceinline__ void masked_slab(const int* __restrict__ valid, int H, int W, int C, int slab_rows, long long& base, long long& e0,
+                                            long long& e1, int& slot) {
+    const int b = blockIdx.y;
+    const long long rows = (long long)valid_rows(valid, b, H) * W;
+    base = (long long)b * H * W * C;
+    e0 = (long long)blockIdx.x * slab_rows * C;
+    e1 = min((long long)(blockIdx.x + 1) * slab_rows, rows) * C;
+    slot = b * gridDim.x + blockIdx.x;
+}
+__global__ __launch_bounds__(256) void bn_stats_masked_kernel(const float* __restrict__ x, const int* __restrict__ valid, int H, int W, int C,
+                                                              double* __restrict__ part, int slab_rows) {
+    long long base, e0, e1; int slot;
+    masked_slab(valid, H, W, C, slab_rows, base, e0, e1, slot);
+    const float* __restrict__ xb = x + base;
+    if (C >= 4) {
+        slab_reduce4(e0, e1, C, part, slot, [&](long long e, int, float4& u, float4& v) {
+            u = *reinterpret_cast<const float4*>(xb + e);
+            v = make_float4(u.x * u.x, u.y * u.y, u.z * u.z, u.w * u.w);
+        });
+        return;
+    }
+    slab_reduce(e0, e1, C, part, slot, [&](long long e, int, float& u, float& v) { const float a = xb[e]; u = a; v = a * a; });
+}
+// bn_finish_kernel in training mode with N = N_v counted here from `valid`
+__global__ __launch_bounds__(1024) void bn_finish_masked_kernel(const double* __restrict__ part, int nslab, const int* __restrict__ valid, int B, int H, int W,
+                                 int C, float eps, float momentum, float* __restrict__ running_mean, float* __restrict__ running_var,
+                                 long long* __restrict__ nbt, float* __restrict__ mean, float* __restrict__ rstd) {
+    const long long N = valid_positions(valid, B, H, W);
+    bn_finish_body(part, nslab, N, C, eps, momentum, 1, running_mean, running_var, nbt, mean, rstd);
 }
 
 struct RowMap { int W, HW; long long bs, rs, cs, base; };    // row r = (b, i, j): element offset base + b*bs + i*rs + j*cs (+ c)
@@ -206,9 +269,7 @@ __global__ __launch_bounds__(256) void bn_apply_masked_kernel(const float* __res
                                                               const int* __restrict__ valid, long long per, int rowc, int H, int C, int act,
                                                               float* __restrict__ y) {
     const int b = blockIdx.y;
-    int v = valid[b];
-    v = v < 0 ? 0 : (v > H ? H : v);          // the host validates; a stale count must still stay inside the map
-    const long long lim = (long long)v * rowc;
+    const long long lim = (long long)valid_rows(valid, b, H) * rowc;
     const float* __restrict__ xb = x + (long long)b * per;
     float* __restrict__ yb = y + (long long)b * per;
     if ((C & 3) == 0) {       // per, lim and every row start are multiples of 4 elements: a 16-byte vector is valid or padding as a whole
@@ -234,8 +295,10 @@ __global__ __launch_bounds__(256) void bn_apply_masked_kernel(const float* __res
 __global__ __launch_bounds__(256) void bn_bwd_stats_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd, int N, int C, int act,
                                                            double* __restrict__ part, int slab_rows) {
+    const int slab = blockIdx.x;
+    const long long e0 = (long long)slab * slab_rows * C, e1 = min((long long)(slab + 1) * slab_rows, (long long)N) * C;
     if (C >= 4) {
-        slab_reduce4(N, C, part, slab_rows, [&](long long e, int c, float4& u, float4& v) {
+        slab_reduce4(e0, e1, C, part, slab, [&](long long e, int c, float4& u, float4& v) {
             float4 dz = *reinterpret_cast<const float4*>(dy + e);
             if (act) {
                 const float4 yv = *reinterpret_cast<const float4*>(y + e);
@@ -247,7 +310,7 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_kernel(const float* __restri
         });
         return;
     }
-    slab_reduce(N, C, part, slab_rows, [&](long long e, int c, float& u, float& v) {
+    slab_reduce(e0, e1, C, part, slab, [&](long long e, int c, float& u, float& v) {
         const float dz = dy[e] * (act ? nn_act_grad_from_y(act, y[e]) : 1.f);
         u = dz; v = dz * (x[e] - mean[c]) * rstd[c];
     });
@@ -307,6 +370,108 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
         float v = dz;
         if (training) v -= (sums[c] + xh * sums[C + c]) * invN;
         dx[e] = g * rstd[c] * v;
+    }
+}
+
+// The backward over the valid rows only.  Pass 1: bn_bwd_stats_kernel's sums on the partition of bn_stats_masked_kernel - a slab ends at the
+// utterance's last valid row, so dy, y and x of the padding are not loaded.
+__global__ __launch_bounds__(256) void bn_bwd_stats_masked_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x,
+                                                                  const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                  const int* __restrict__ valid, int H, int W, int C, int act,
+                                                                  double* __restrict__ part, int slab_rows) {
+    long long base, e0, e1; int slot;
+    masked_slab(valid, H, W, C, slab_rows, base, e0, e1, slot);
+    const float* __restrict__ dyb = dy + base;
+    const float* __restrict__ yb = y ? y + base : nullptr;
+    const float* __restrict__ xb = x + base;
+    if (C >= 4) {
+        slab_reduce4(e0, e1, C, part, slot, [&](long long e, int c, float4& u, float4& v) {
+            float4 dz = *reinterpret_cast<const float4*>(dyb + e);
+            if (act) {
+                const float4 yv = *reinterpret_cast<const float4*>(yb + e);
+                dz.x *= nn_act_grad_from_y(act, yv.x); dz.y *= nn_act_grad_from_y(act, yv.y); dz.z *= nn_act_grad_from_y(act, yv.z); dz.w *= nn_act_grad_from_y(act, yv.w);
+            }
+            const float4 xv = *reinterpret_cast<const float4*>(xb + e), mv = *reinterpret_cast<const float4*>(mean + c), rv = *reinterpret_cast<const float4*>(rstd + c);
+            u = dz;
+            v = make_float4(dz.x * (xv.x - mv.x) * rv.x, dz.y * (xv.y - mv.y) * rv.y, dz.z * (xv.z - mv.z) * rv.z, dz.w * (xv.w - mv.w) * rv.w);
+        });
+        return;
+    }
+    slab_reduce(e0, e1, C, part, slot, [&](long long e, int c, float& u, float& v) {
+        const float dz = dyb[e] * (act ? nn_act_grad_from_y(act, yb[e]) : 1.f);
+        u = dz; v = dz * (xb[e] - mean[c]) * rstd[c];
+    });
+}
+// bn_bwd_finish_kernel, plus 1 / N_v (counted from `valid` as in the forward) in sums[2 * C] for the apply kernel
+__global__ __launch_bounds__(1024) void bn_bwd_finish_masked_kernel(const double* __restrict__ part, int nslab, const int* __restrict__ valid, int B, int H,
+                                                                   int W, int C, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                   float* __restrict__ sums, int accumulate) {
+    __shared__ double red[2][16][64];
+    const long long N = valid_positions(valid, B, H, W);
+    const int cl = threadIdx.x & 63, lane4 = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    double s = 0.0, q = 0.0;
+    if (c < C)
+        for (int k = lane4; k < nslab; k += 16) { s += part[((long long)k * 2) * C + c]; q += part[((long long)k * 2 + 1) * C + c]; }
+    red[0][lane4][cl] = s; red[1][lane4][cl] = q;
+    __syncthreads();
+    if (lane4 != 0 || c >= C) return;
+    s = 0.0; q = 0.0;
+    for (int k = 0; k < 16; ++k) { s += red[0][k][cl]; q += red[1][k][cl]; }
+    if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)s : (float)s;
+    if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)q : (float)q;
+    sums[c] = (float)s; sums[C + c] = (float)q;
+    if (c == 0) sums[2 * C] = 1.0f / (float)N;
+}
+// pass 2: bn_bwd_apply_kernel's training expression on the rows h < valid[b], exactly 0 beyond - selected by ROW, never by y == 0 (SELU's
+// derivative at y == 0 is scale * alpha, not 0); dy, y and x of the padding are not read.  The launch shape of bn_apply_masked_kernel.
+__global__ __launch_bounds__(256) void bn_bwd_apply_masked_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x,
+                                                                  const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ sums,
+                                                                  const int* __restrict__ valid, long long per, int rowc, int H, int C, int act,
+                                                                  float* __restrict__ dx) {
+    const int b = blockIdx.y;
+    const long long lim = (long long)valid_rows(valid, b, H) * rowc;
+    const float invN = sums[2 * C];
+    const float* __restrict__ dyb = dy + (long long)b * per;
+    const float* __restrict__ yb = y ? y + (long long)b * per : nullptr;
+    const float* __restrict__ xb = x + (long long)b * per;
+    float* __restrict__ dxb = dx + (long long)b * per;
+    if ((C & 3) == 0) {
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < (per >> 2); q += (long long)gridDim.x * 256) {
+            const long long e = q << 2;
+            float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e < lim) {
+                const int c = (int)(e & (C - 1));
+                const float4 dv = *reinterpret_cast<const float4*>(dyb + e), xv = *reinterpret_cast<const float4*>(xb + e);
+                const float4 mv = *reinterpret_cast<const float4*>(mean + c), rv = *reinterpret_cast<const float4*>(rstd + c);
+                float4 yv = make_float4(0.f, 0.f, 0.f, 0.f), gv = make_float4(1.f, 1.f, 1.f, 1.f);
+                if (act) yv = *reinterpret_cast<const float4*>(yb + e);
+                if (gamma) gv = *reinterpret_cast<const float4*>(gamma + c);
+                const float d4[4] = {dv.x, dv.y, dv.z, dv.w}, x4[4] = {xv.x, xv.y, xv.z, xv.w}, m4[4] = {mv.x, mv.y, mv.z, mv.w};
+                const float r4[4] = {rv.x, rv.y, rv.z, rv.w}, y4[4] = {yv.x, yv.y, yv.z, yv.w}, g4[4] = {gv.x, gv.y, gv.z, gv.w};
+                float o[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float dz = d4[i] * (act ? nn_act_grad_from_y(act, y4[i]) : 1.f);
+                    const float xh = (x4[i] - m4[i]) * r4[i];
+                    o[i] = g4[i] * r4[i] * (dz - (sums[c + i] + xh * sums[C + c + i]) * invN);
+                }
+                out = make_float4(o[0], o[1], o[2], o[3]);
+            }
+            *reinterpret_cast<float4*>(dxb + e) = out;
+        }
+        return;
+    }
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long long)gridDim.x * 256) {
+        float out = 0.f;
+        if (e < lim) {
+            const int c = (int)(e & (C - 1));
+            const float dz = dyb[e] * (act ? nn_act_grad_from_y(act, yb[e]) : 1.f);
+            const float xh = (xb[e] - mean[c]) * rstd[c];
+            out = (gamma ? gamma[c] : 1.f) * rstd[c] * (dz - (sums[c] + xh * sums[C + c]) * invN);
+        }
+        dxb[e] = out;
     }
 }
 
@@ -375,9 +540,7 @@ __global__ __launch_bounds__(256) void avgpool_fwd_kernel(const float* __restric
 __global__ __launch_bounds__(256) void avgpool_fwd_masked_kernel(const float* __restrict__ x, const int* __restrict__ valid, int H, int W, int C,
                                                                  float* __restrict__ y) {
     const int b = blockIdx.x;
-    int v = valid[b];
-    v = v < 0 ? 0 : (v > H ? H : v);
-    const int R = v * W;
+    const int R = valid_rows(valid, b, H) * W;
     const float* __restrict__ xb = x + (long long)b * H * W * C;
     for (int c = threadIdx.x; c < C; c += 256) {
         float s = 0.f;
@@ -390,6 +553,31 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float* __restric
         const long long b = e / ((long long)R * C);
         dx[e] = dy[b * C + (e % C)] / (float)R;
     }
+}
+
+// dx[b][h][w][c] = dy[b][c] / (valid[b] * W) for h < valid[b], exactly 0 beyond: the backward of avgpool_fwd_masked_kernel
+__global__ __launch_bounds__(256) void avgpool_bwd_masked_kernel(const float* __restrict__ dy, const int* __restrict__ valid, long long per, int rowc, int H,
+                                                                 int W, int C, float* __restrict__ dx) {
+    const int b = blockIdx.y;
+    const int v = valid_rows(valid, b, H);
+    const long long lim = (long long)v * rowc;
+    const float R = (float)(v * W);
+    const float* __restrict__ dyb = dy + (long long)b * C;
+    float* __restrict__ dxb = dx + (long long)b * per;
+    if ((C & 3) == 0) {
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < (per >> 2); q += (long long)gridDim.x * 256) {
+            const long long e = q << 2;
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e < lim) {
+                const float4 d = *reinterpret_cast<const float4*>(dyb + (e % C));
+                o = make_float4(d.x / R, d.y / R, d.z / R, d.w / R);
+            }
+            *reinterpret_cast<float4*>(dxb + e) = o;
+        }
+        return;
+    }
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long long)gridDim.x * 256)
+        dxb[e] = e < lim ? dyb[e % C] / R : 0.f;
 }
 
 int grid_for(long long n) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
@@ -439,6 +627,72 @@ extern "C" int scl_bn_eval_masked(const float* x, int B, int H, int W, int C, co
     if (gx > cap) gx = cap;
     hipLaunchKernelGGL(bn_apply_masked_kernel, dim3(gx, B), dim3(256), 0, s, x, mean, rstd, gamma, beta, valid, per, W * C, H, C, act, y);
     return scl_check_launch("scl_bn_eval_masked");
+}
+
+namespace {
+// the launch shape of the masked apply kernels: blockIdx.y the utterance, the unmasked launch's block budget shared among them
+dim3 masked_grid(long long per, int B, int C) {
+    int gx = grid_for(per >> ((C & 3) == 0 ? 2 : 0));
+    const int cap = (8192 + B - 1) / B;
+    return dim3(gx > cap ? cap : gx, B);
+}
+bool any_valid_row(const int32_t* valid_host, int B) {
+    for (int b = 0; b < B; ++b)
+        if (valid_host[b] > 0) return true;
+    return false;
+}
+}  // namespace
+
+extern "C" int scl_bn_masked_nslabs(int B, int H, int W) {
+    if (B < 1 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31)) return 0;
+    const int r = bn_slab_rows(B * H * W);
+    return B * (int)(((long long)H * W + r - 1) / r);
+}
+
+extern "C" int scl_bn_fwd_masked(const float* x, int B, int H, int W, int C, const float* gamma, const float* beta, float* running_mean,
+                                 float* running_var, long long* num_batches_tracked, float momentum, float eps, int act, const int32_t* valid,
+                                 const int32_t* valid_host, float* part, float* mean, float* rstd, float* y, void* stream) {
+    SCL_REQUIRE(x && valid && valid_host && part && mean && rstd && y, "bn_fwd_masked: null argument");
+    SCL_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && bn_channels_ok(C), "bn_fwd_masked: need 1 <= B <= 65535, H, W >= 1, C dividing 256 or 512");
+    SCL_REQUIRE((long long)H * W * C < (1ll << 31) && (long long)B * H * W < (1ll << 31),
+                "bn_fwd_masked: H * W * C of one utterance and the B * H * W rows of the batch must stay below 2^31");
+    SCL_REQUIRE(act >= 0 && act <= 2, "bn_fwd_masked: act");
+    SCL_REQUIRE((C & 3) != 0 || ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0),
+                "bn_fwd_masked: C % 4 == 0 takes 16-byte aligned x, y, mean, rstd, gamma, beta");
+    SCL_REQUIRE(((uintptr_t)part & 7) == 0, "bn_fwd_masked: part holds doubles (8-byte aligned)");
+    SCL_REQUIRE(any_valid_row(valid_host, B), "bn_fwd_masked: no valid position (every valid[b] is 0): batch statistics over nothing");
+    hipStream_t s = (hipStream_t)stream;
+    const int slab_rows = bn_slab_rows(B * H * W), nslab = scl_bn_masked_nslabs(B, H, W);
+    hipLaunchKernelGGL(bn_stats_masked_kernel, dim3(nslab / B, B), dim3(256), 0, s, x, valid, H, W, C, (double*)part, slab_rows);
+    hipLaunchKernelGGL(bn_finish_masked_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, (const double*)part, nslab, valid, B, H, W, C, eps, momentum,
+                       running_mean, running_var, num_batches_tracked, mean, rstd);
+    const long long per = (long long)H * W * C;
+    hipLaunchKernelGGL(bn_apply_masked_kernel, masked_grid(per, B, C), dim3(256), 0, s, x, mean, rstd, gamma, beta, valid, per, W * C, H, C, act, y);
+    return scl_check_launch("scl_bn_fwd_masked");
+}
+
+extern "C" int scl_bn_bwd_masked(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* gamma, int B,
+                                 int H, int W, int C, int act, const int32_t* valid, const int32_t* valid_host, float* part, float* sums,
+                                 float* dgamma, float* dbeta, float* dx, int accumulate, void* stream) {
+    SCL_REQUIRE(dy && x && mean && rstd && valid && valid_host && part && sums && dx, "bn_bwd_masked: null argument");
+    SCL_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && bn_channels_ok(C), "bn_bwd_masked: need 1 <= B <= 65535, H, W >= 1, C dividing 256 or 512");
+    SCL_REQUIRE((long long)H * W * C < (1ll << 31) && (long long)B * H * W < (1ll << 31),
+                "bn_bwd_masked: H * W * C of one utterance and the B * H * W rows of the batch must stay below 2^31");
+    SCL_REQUIRE(act >= 0 && act <= 2, "bn_bwd_masked: act");
+    SCL_REQUIRE(act == 0 || y, "bn_bwd_masked: the activation gradient needs the forward output y");
+    SCL_REQUIRE((C & 3) != 0 || ((((uintptr_t)dy | (uintptr_t)y | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma) & 15) == 0),
+                "bn_bwd_masked: C % 4 == 0 takes 16-byte aligned dy, y, x, dx, mean, rstd, gamma");
+    SCL_REQUIRE(((uintptr_t)part & 7) == 0, "bn_bwd_masked: part holds doubles (8-byte aligned)");
+    SCL_REQUIRE(any_valid_row(valid_host, B), "bn_bwd_masked: no valid position (every valid[b] is 0)");
+    hipStream_t s = (hipStream_t)stream;
+    const int slab_rows = bn_slab_rows(B * H * W), nslab = scl_bn_masked_nslabs(B, H, W);
+    hipLaunchKernelGGL(bn_bwd_stats_masked_kernel, dim3(nslab / B, B), dim3(256), 0, s, dy, y, x, mean, rstd, valid, H, W, C, act, (double*)part, slab_rows);
+    hipLaunchKernelGGL(bn_bwd_finish_masked_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, (const double*)part, nslab, valid, B, H, W, C, dgamma, dbeta, sums,
+                       accumulate);
+    const long long per = (long long)H * W * C;
+    hipLaunchKernelGGL(bn_bwd_apply_masked_kernel, masked_grid(per, B, C), dim3(256), 0, s, dy, y, x, mean, rstd, gamma, sums, valid, per, W * C, H, C, act,
+                       dx);
+    return scl_check_launch("scl_bn_bwd_masked");
 }
 
 extern "C" int scl_bn_bwd(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* gamma, int N, int C,
@@ -562,4 +816,15 @@ extern "C" int scl_avgpool_bwd(const float* dy, int B, int R, int C, float* dx, 
     SCL_REQUIRE(dy && dx && B >= 1 && R >= 1 && C >= 1, "avgpool_bwd: bad args");
     hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for((long long)B * R * C)), dim3(256), 0, (hipStream_t)stream, dy, R, C, (long long)B * R * C, dx);
     return scl_check_launch("scl_avgpool_bwd");
+}
+extern "C" int scl_avgpool_bwd_masked(const float* dy, const int32_t* valid, const int32_t* valid_host, int B, int H, int W, int C, float* dx, void* stream) {
+    SCL_REQUIRE(dy && valid && valid_host && dx, "avgpool_bwd_masked: null argument");
+    SCL_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && C >= 1, "avgpool_bwd_masked: need 1 <= B <= 65535, H, W, C >= 1");
+    SCL_REQUIRE((long long)H * W * C < (1ll << 31), "avgpool_bwd_masked: H * W * C of one utterance must stay below 2^31");
+    SCL_REQUIRE((C & 3) != 0 || ((((uintptr_t)dy | (uintptr_t)dx) & 15) == 0), "avgpool_bwd_masked: C % 4 == 0 takes 16-byte aligned dy, dx");
+    for (int b = 0; b < B; ++b)
+        SCL_REQUIRE(valid_host[b] >= 1 && valid_host[b] <= H, "avgpool_bwd_masked: every valid[b] must be in 1..H (an average over no rows has no backward)");
+    const long long per = (long long)H * W * C;
+    hipLaunchKernelGGL(avgpool_bwd_masked_kernel, masked_grid(per, B, C), dim3(256), 0, (hipStream_t)stream, dy, valid, per, W * C, H, W, C, dx);
+    return scl_check_launch("scl_avgpool_bwd_masked");
 }

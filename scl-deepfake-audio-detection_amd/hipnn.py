@@ -287,19 +287,67 @@ class _BatchNormFn(torch.autograd.Function):
         return dx, dg, db, None, None, None, None, None, None, None, None
 
 
-def batch_norm(x, bn, act=ACT_NONE, grad_in_place=False, valid=None):
+class _BatchNormMaskedFn(torch.autograd.Function):
+    """Train-mode BatchNorm + activation over the valid rows of a zero-padded variable-length batch (scl_bn_fwd_masked / scl_bn_bwd_masked)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, nbt, momentum, eps, act, grad_in_place, valid, counts):
+        B, H, W, C = x.shape
+        xc = x.contiguous().float()
+        dev = x.device
+        part = torch.empty(ops.bn_masked_nslabs(B, H, W) * 2 * C, dtype=torch.float64, device=dev)
+        mean, rstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
+        y = torch.empty_like(xc)
+        ops.bn_fwd_masked(xc, B, H, W, C, weight, bias, running_mean, running_var, nbt, momentum, eps, act, valid, counts, part, mean, rstd, y)
+        ctx.save_for_backward(xc, y, mean, rstd, weight, valid)
+        ctx.cfg = (B, H, W, C, act, weight is not None, bias is not None, counts)
+        ctx.in_place = (weight, bias) if grad_in_place else None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xc, y, mean, rstd, weight, valid = ctx.saved_tensors
+        B, H, W, C, act, has_w, has_b, counts = ctx.cfg
+        dev = dy.device
+        dyc = dy.contiguous().float()
+        part = torch.empty(ops.bn_masked_nslabs(B, H, W) * 2 * C, dtype=torch.float64, device=dev)
+        sums = torch.empty(2 * C + 4, device=dev)
+        dx = torch.empty_like(xc)
+        none = (None,) * 9
+        if ctx.in_place is not None and has_w and has_b and not torch.cuda.is_current_stream_capturing():
+            gw, gb = ctx.in_place[0].grad, ctx.in_place[1].grad      # as _BatchNormFn.backward: the finishing kernel adds into attached .grad views
+            if all(g is not None and g.dtype == torch.float32 and g.is_contiguous() for g in (gw, gb)):
+                ops.bn_bwd_masked(dyc, y, xc, mean, rstd, weight, B, H, W, C, act, valid, counts, part, sums, gw, gb, dx, accumulate=True)
+                return (dx, None, None) + none
+        dg = torch.empty(C, device=dev) if has_w else None
+        db = torch.empty(C, device=dev) if has_b else None
+        ops.bn_bwd_masked(dyc, y, xc, mean, rstd, weight, B, H, W, C, act, valid, counts, part, sums, dg, db, dx)
+        return (dx, dg, db) + none
+
+
+def batch_norm(x, bn, act=ACT_NONE, grad_in_place=False, valid=None, counts=None):
     """nn.BatchNorm1d / 2d semantics over the LAST dimension of x (channels-last), fused with `act`; `bn` supplies weight, bias, the
     running statistics and the training flag (its forward is never called).  grad_in_place: as conv2d's.
     valid: int32 [B] on the GPU with x [B, H, W, C], the rows h < valid[b] that utterance b of a zero-padded variable-length batch owns
-    (0 <= valid[b] <= H, validated by the caller on the host).  Eval mode under torch.no_grad() only: in eval mode a BatchNorm is a
-    per-element map, so the valid rows get the bits they get without `valid`, and the rest is exactly 0 whatever x holds there."""
+    (0 <= valid[b] <= H, validated by the caller on the host).  Two modes.  Eval mode under torch.no_grad(): a BatchNorm is a per-element
+    map, so the valid rows get the bits they get without `valid`, and the rest is exactly 0 whatever x holds there.  Train mode with
+    autograd on: batch statistics (and the running statistics' update) over the valid positions only, exactly 0 beyond, and a backward whose
+    sums run over the valid positions and whose dx is exactly 0 beyond.  counts: the same counts on the host (a list of ints: the entry
+    points refuse a batch without any valid position before they launch); left out, they are read back from `valid`.  The mixed
+    combinations (eval mode with autograd on, train mode under torch.no_grad()) are refused."""
     training = bn.training or bn.running_mean is None
     if valid is not None:
+        if x.dim() != 4:
+            raise ValueError("hipnn.batch_norm: `valid` needs a [B, H, W, C] map, got %r" % (tuple(x.shape),))
+        if training and torch.is_grad_enabled():
+            if counts is None:
+                counts = valid.tolist()
+            momentum = 0.1 if bn.momentum is None else bn.momentum
+            return _BatchNormMaskedFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, momentum, bn.eps,
+                                            act, grad_in_place, valid, tuple(int(v) for v in counts))
         if training or torch.is_grad_enabled():
             raise NotImplementedError("hipnn.batch_norm: `valid` is a scoring mode (a BatchNorm in eval mode under torch.no_grad()); "
                                       "batch statistics over the valid positions and a backward are not implemented")
-        if x.dim() != 4:
-            raise ValueError("hipnn.batch_norm: `valid` needs a [B, H, W, C] map, got %r" % (tuple(x.shape),))
         B, H, W, C = x.shape
         xc = x.contiguous().float()
         mean, rstd = torch.empty(C, device=x.device), torch.empty(C, device=x.device)
@@ -462,15 +510,38 @@ def avg_pool_rows(x):
     return _AvgPoolFn.apply(x)
 
 
+class _AvgPoolMaskedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, valid, counts):
+        B, H, W, C = x.shape
+        y = torch.empty(B, C, device=x.device)
+        ops.avgpool_fwd_masked(x.contiguous().float(), valid, B, H, W, C, y)
+        ctx.save_for_backward(valid)
+        ctx.cfg = (B, H, W, C, counts)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (valid,) = ctx.saved_tensors
+        B, H, W, C, counts = ctx.cfg
+        dx = torch.empty(B, H, W, C, device=dy.device)
+        ops.avgpool_bwd_masked(dy.contiguous().float(), valid, counts, B, H, W, C, dx)
+        return dx, None, None
+
+
 def avg_pool_rows_masked(x, valid, counts=None):
     """x [B, H, W, C] of a zero-padded variable-length batch -> [B, C]: the mean over the rows h < valid[b] (int32 [B] on the GPU) and all of
     W, the bits avg_pool_rows gives for the utterance's [1, valid[b] * W, C] slice alone.  counts: the same counts on the host, checked to be
-    in 1..H before anything is launched (a caller that validated them already leaves it out).  Forward only."""
-    if torch.is_grad_enabled() and x.requires_grad:
-        raise NotImplementedError("hipnn.avg_pool_rows_masked: forward only (scoring mode)")
+    in 1..H before anything is launched (a forward-only caller that validated them already leaves it out).  Under autograd the backward
+    spreads dy[b] / (valid[b] * W) over the utterance's own rows and writes exact zeros beyond; its entry point takes the host counts, which
+    are read back from `valid` when the caller gave none."""
     B, H, W, C = x.shape
     if counts is not None:
-        ops.check_lengths(counts, H)
+        counts = tuple(ops.check_lengths(counts, H))
+    if torch.is_grad_enabled() and x.requires_grad:
+        if counts is None:
+            counts = tuple(ops.check_lengths(valid.tolist(), H))
+        return _AvgPoolMaskedFn.apply(x, valid, counts)
     y = torch.empty(B, C, device=x.device)
     ops.avgpool_fwd_masked(x.contiguous().float(), valid, B, H, W, C, y)
     return y

@@ -142,6 +142,10 @@ def _protos():
         "scl_avgpool_fwd": ([_vp, _i32, _i32, _i32, _vp, _vp], _i32),
         "scl_avgpool_bwd": ([_vp, _i32, _i32, _i32, _vp, _vp], _i32),
         "scl_avgpool_fwd_masked": ([_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
+        "scl_bn_masked_nslabs": ([_i32, _i32, _i32], _i32),
+        "scl_bn_fwd_masked": ([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+        "scl_bn_bwd_masked": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp], _i32),
+        "scl_avgpool_bwd_masked": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
         # norm.hip
         "scl_layernorm_fwd": ([_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _f32, _i32, _vp], _i32),
         "scl_layernorm_bwd_nparts": ([_i32], _i32),

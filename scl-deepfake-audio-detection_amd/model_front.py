@@ -10,6 +10,9 @@ default: the HIP back-ends are a few dozen launches).
 Variable-length scoring batches (forward(x, lengths), eval mode under torch.no_grad()) for a back-end that declares `head_takes_frames`
 and whose `_head_forward(mod, feats, frames)` masks the padding itself (resnet_head.py): the encoder runs with its padding mask on either
 scoring precision and either row layout, feats rows beyond an utterance's frames are zeroed, and the back-end gets the host-side frame counts.
+Variable-length TRAINING batches (train mode, autograd on) for a back-end that declares `head_trains_frames` besides: the autograd boundary
+carries the row layout, the encoder trains under its padding mask or on packed rows (SCL_VARLEN_PACK=1; the back-end stays padded), and the
+rows of d(feats) beyond an utterance's frames are zeroed before LL's gradients and the encoder backward; the back-end runs eagerly.
 Sub-classes supply `_build_head(args)` (an nn.Module whose children / parameters are grafted at the root under the
 reference's state-dict names) and `_head_forward(mod, feats) -> (output, emb)`.
 """
@@ -34,15 +37,15 @@ class _FrontFn(torch.autograd.Function):
     """Autograd boundary around encoder + LL: waveform -> feats [bz, T, 128] fp32."""
 
     @staticmethod
-    def forward(ctx, model, x, anchor):
-        feats, saved = model._front_forward(x)
+    def forward(ctx, model, x, anchor, layout=FIXED):
+        feats, saved = model._front_forward(x, layout, train=True)      # layout: the rows of a variable-length training batch
         ctx.model, ctx.saved = model, saved
         return feats.clone()
 
     @staticmethod
     def backward(ctx, d_feats):
         ctx.model._front_backward(ctx.saved, d_feats)
-        return None, None, None
+        return None, None, None, None
 
 
 class _HeadRunner(nn.Module):
@@ -64,6 +67,7 @@ class _HeadRunner(nn.Module):
 class FrontHeadModel(FlatModel):
     flag_fix_ssl = False
     head_takes_frames = False      # the back-end masks the padding of a variable-length batch: _head_forward(mod, feats, frames)
+    head_trains_frames = False     # ... in train mode with autograd on too (masked batch statistics and a masked backward)
     front_prefix = ""        # module path of `ssl_model` / `LL` in the state dict ("backend." for wav2vec2_btse, backend.py:31-33)
 
     def _build_head(self, args):
@@ -141,9 +145,10 @@ class FrontHeadModel(FlatModel):
         self.P.grad[self._head_lo:].zero_()
 
     # encoder + LL ----------------------------------------------------------------------------------
-    def _state(self, B, L, layout=FIXED):
-        """Boundary buffers and launch plans of a [B, L] batch.  A variable-length (scoring) batch: forward-only, with the frame counts and,
-        packed, the row offsets besides — device buffers of fixed address, overwritten before every replay; a state of its own per layout."""
+    def _state(self, B, L, layout=FIXED, train=False):
+        """Boundary buffers and launch plans of a [B, L] batch.  A variable-length batch: the frame counts and, packed, the row offsets
+        besides — device buffers of fixed address, overwritten before every replay; a state of its own per layout.  Forward-only for a
+        scoring batch (least recently used of a few); with the backward's buffers for a training one (train: kept)."""
         def make():
             T = self.cfg.conv_lens(L)[-1]
             M, E, dev = B * T, self.cfg.embed, self.device
@@ -151,24 +156,26 @@ class FrontHeadModel(FlatModel):
             bf = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
             i32 = dict(dtype=torch.int32, device=dev)
             st = dict(T=T, x=f32(B, L), feats=f32(B, T, FEAT_DIM), dfe_bf=bf(M * FEAT_DIM + 1024), plans={})
-            if layout.fixed:
+            if layout.fixed or train:
                 st.update(d_feats=f32(B, T, FEAT_DIM), denc=bf(M * E), cs=f32(ops.colsum_reduce_nparts(M, 8) * FEAT_DIM))
-            else:
+            if not layout.fixed:
                 st.update(frames=torch.ones(B, **i32), row0=torch.arange(B + 1, **i32) if layout.packed else None)
             return st
-        return self._shape_state(layout.key(B, L), make, layout)
+        return self._shape_state(layout.key(B, L), make, layout, train)
 
-    def _front_forward(self, x, layout=FIXED):
-        """Encoder (bf16 kernels) + LL on the shape's state, recorded once per plan key and replayed.  A variable-length batch is scored,
-        never trained on: padding mask (or packed rows) in the encoder, feats rows beyond an utterance's frames zeroed, no dropout mask drawn."""
+    def _front_forward(self, x, layout=FIXED, train=False):
+        """Encoder (bf16 kernels) + LL on the shape's state, recorded once per plan key and replayed.  A variable-length batch: padding mask
+        (or packed rows) in the encoder, feats rows beyond an utterance's frames zeroed.  train: a backward follows (_FrontFn) — a
+        variable-length batch then takes the shape's training state and the encoder its dropout seeds, as a fixed-length one; without it
+        a variable-length batch is scored (no dropout mask drawn)."""
         B, L = x.shape
-        ssl_train = layout.fixed and self._ssl_train()
-        st = self._state(B, L, layout)
+        ssl_train = (layout.fixed or train) and self._ssl_train()
+        st = self._state(B, L, layout, train)
         st["x"].copy_(x)
         seed = 0
-        if layout.fixed:
+        if layout.fixed or train:
             self._drop_step = seed = (self._drop_step * 1664525 + 1013904223) & 0x7FFFFFFF
-        else:
+        if not layout.fixed:
             layout = self._bind_layout(st, layout)
         self.ssl.refresh_weights()
         use_plan = self.cfg.encoder_layerdrop == 0 or not ssl_train
@@ -177,7 +184,7 @@ class FrontHeadModel(FlatModel):
         def build():
             P, E = self.P, self.cfg.embed
             enc_out, ectx = self.ssl.forward(st["x"], training=ssl_train, refresh=False, step_seed=seed,
-                                             grad=None if layout.fixed else False, **layout.args)
+                                             grad=None if layout.fixed else train, **layout.args)
             M = B * st["T"]
             # the bf16 primary output of the GEMM is not needed here: it lands in dfe_bf, which the backward overwrites
             ops.gemm(Op(enc_out, E), Op(P.bf16, E, offset=P.off("LL.weight")), st["dfe_bf"], M, FEAT_DIM, E, bias=P.f32("LL.bias"),
@@ -210,11 +217,16 @@ class FrontHeadModel(FlatModel):
         if self.grad_sync is not None:
             self.ssl.on_grads_ready = self.grad_sync.ready_above
         use_plan = not sv["ectx"]["skipped"] and self.cfg.encoder_layerdrop == 0
-        pk = ("bwd", self.grad_sync is not None)
+        layout = sv["ectx"]["layout"]      # the row offsets and frame counts are the state's, already in place
+        pk = layout.plan_key("bwd", self.grad_sync is not None)
 
         def build():
             enc_slots = []
             M = sv["B"] * st["T"]
+            if layout.frames is not None:
+                # the forward zeroed feats beyond the frames (zero_tail_rows), so whatever the loss hands back there (SupCon's gradient is
+                # not 0) stops here, before LL's gradients and the encoder backward
+                ops.zero_tail_rows(st["d_feats"], layout.frames, sv["B"], st["T"], FEAT_DIM)
             ops.cast_bf16(st["d_feats"], st["dfe_bf"], M * FEAT_DIM)
             ops.colsum_reduce(st["d_feats"], st["cs"], P.g("LL.bias"), M, FEAT_DIM)
             self.ssl._wgrad(sv["ectx"]["d"], Op(st["dfe_bf"], FEAT_DIM), Op(sv["enc_out"], E), P.g("LL.weight"), FEAT_DIM, E, M)
@@ -227,9 +239,9 @@ class FrontHeadModel(FlatModel):
         run_plan(st["plans"], pk, use_plan, lambda plan: self.ssl.apply_seeds(plan["enc_slots"], sv["ectx"]["step_seed"]), build)
 
     # forward / loss --------------------------------------------------------------------------------
-    VARLEN_REFUSAL = ("variable-length batches (forward(x, lengths), main.py --padding_type none) are implemented for the "
-                      "wav2vec2_linear_nll plugin and, for scoring, wav2vec2_resnet_nll: this back-end has no padding mask; score "
-                      "fixed-length clips (--padding_type zero / repeat) or one utterance per call")
+    VARLEN_REFUSAL = ("variable-length batches (forward(x, lengths), main.py --padding_type none, --padding_type zero --batch_size k) "
+                      "are implemented for the wav2vec2_linear_nll and wav2vec2_resnet_nll plugins: this back-end has no padding mask; "
+                      "use fixed-length clips (--padding_type zero / repeat at --batch_size 1) or one utterance per call")
 
     def forward(self, x, lengths=None):
         if lengths is not None and not self.head_takes_frames:
@@ -239,14 +251,18 @@ class FrontHeadModel(FlatModel):
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         counts, layout = None, FIXED
         if lengths is not None:
-            if self.training or torch.is_grad_enabled():
-                raise NotImplementedError("%s: forward(x, lengths) is a scoring mode on model.eval() under torch.no_grad(); training on "
-                                          "zero-padded batches is implemented for the wav2vec2_linear_nll plugin only"
-                                          % type(self).__module__.split(".")[-1])
+            train = bool(self.training) and torch.is_grad_enabled() and self.head_trains_frames
+            if not train and (self.training or torch.is_grad_enabled()):
+                raise NotImplementedError("%s: forward(x, lengths) is a scoring mode on model.eval() under torch.no_grad()%s; eval with "
+                                          "autograd on, or train mode under torch.no_grad(), is neither"
+                                          % (type(self).__module__.split(".")[-1],
+                                             " and a training mode on model.train() with autograd on" if self.head_trains_frames else
+                                             " (training on zero-padded batches: wav2vec2_linear_nll and wav2vec2_resnet_nll)"))
+            # the packed layout: encoder.VARLEN_PACK serves the bf16 encoder path (training, bf16 scoring), encoder.SCORE_PACK fp32 scoring
             counts, layout = ENC.row_layout(self.cfg, lengths, *x.shape, min_samples=self.min_samples(), refuse_short=True,
-                                            score_f32=SCORE_FP32, device=self.device)
+                                            score_f32=not train and SCORE_FP32, device=self.device)
         if torch.is_grad_enabled():
-            feats = _FrontFn.apply(self, x, self._anchor)
+            feats = _FrontFn.apply(self, x, self._anchor, layout)
         elif not self.training and SCORE_FP32:
             feats = self._front_f32(x, layout)
         else:

@@ -4,6 +4,8 @@
     forward(x [bz, L]) -> (logits [bz, 2], feats [bz, T, 128], emb [bz, 256])   (logits only when not is_train)
     forward(x, lengths=[n_0, ...])   scoring mode (eval, no grad): row b holds n_b >= min_samples() samples followed by padding and gets the
                                      result it gets alone at its own length; feats rows beyond an utterance's frames are 0
+                                     training mode (train, autograd on): every BatchNorm of the back-end takes its batch statistics over
+                                     the valid positions of the batch; no gradient depends on what x holds beyond the lengths
     loss(output, feats, emb, labels, config, info=None) -> dict of 0-d tensors
 
 Encoder + LL + losses: HIP kernels; back-end: `resnet_head.ResNetHead` on flat-buffer parameter views, replayed as hipGraphs in
@@ -18,6 +20,7 @@ from .resnet_head import DEFAULT_RESNET, ResNetHead, min_frames
 
 class Model(FrontHeadModel):
     head_takes_frames = True      # forward(x, lengths) in scoring mode: the back-end masks the padding (resnet_head.py)
+    head_trains_frames = True     # ... and in train mode with autograd on: masked batch statistics in every BatchNorm
 
     def __init__(self, args, device, is_train=True, w2v_cfg=None, seed=0, rank=0):
         super().__init__(args, device, is_train=is_train, w2v_cfg=w2v_cfg, seed=seed, rank=rank)

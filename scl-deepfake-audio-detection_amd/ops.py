@@ -812,6 +812,32 @@ def bn_bwd(dy, y, x, mean, rstd, gamma, N, C, act, training, part, sums, dgamma,
           _p(dbeta), _p(dx), 1 if accumulate else 0, _stream())
 
 
+def bn_masked_nslabs(B, H, W):
+    return L.load().scl_bn_masked_nslabs(B, H, W)
+
+
+def _host_counts(counts, B):
+    """Host-side copy of the per-utterance row counts, for the entry points' own refusals (the kernels read the device copy)."""
+    counts = [int(v) for v in counts]
+    assert len(counts) >= B, "row counts: one per utterance"
+    return (ctypes.c_int32 * max(len(counts), 1))(*counts)
+
+
+def bn_fwd_masked(x, B, H, W, C, gamma, beta, running_mean, running_var, nbt, momentum, eps, act, valid, counts, part, mean, rstd, y):
+    """Train-mode BatchNorm + activation of x [B, H, W, C] over the rows h < valid[b] (int32 [B] on the GPU; counts: the same on the host):
+    batch statistics over the valid positions only, y exactly 0 beyond, running statistics updated.  part: bn_masked_nslabs * 2 * C doubles."""
+    assert valid.numel() >= B
+    _call("scl_bn_fwd_masked", _p(x), B, H, W, C, _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(nbt), momentum, eps, act,
+          _p(_klen(valid)), _host_counts(counts, B), _p(part), _p(mean), _p(rstd), _p(y), _stream())
+
+
+def bn_bwd_masked(dy, y, x, mean, rstd, gamma, B, H, W, C, act, valid, counts, part, sums, dgamma, dbeta, dx, accumulate=False):
+    """Backward of bn_fwd_masked: sums over the valid positions only, dx exactly 0 beyond.  sums: f32 [2 * C + 1]."""
+    assert valid.numel() >= B and sums.numel() >= 2 * C + 1
+    _call("scl_bn_bwd_masked", _p(dy), _p(y), _p(x), _p(mean), _p(rstd), _p(gamma), B, H, W, C, act, _p(_klen(valid)), _host_counts(counts, B),
+          _p(part), _p(sums), _p(dgamma), _p(dbeta), _p(dx), 1 if accumulate else 0, _stream())
+
+
 def pad_nhwc(src, rows, C, dst, rowmap):
     W_, HW, bs, rs, cs, base = rowmap
     _call("scl_pad_nhwc_f32", _p(src), rows, C, _p(dst), 1 if dst.dtype == torch.bfloat16 else 0, W_, HW, bs, rs, cs, base, _stream())
@@ -841,6 +867,12 @@ def avgpool_fwd_masked(x, valid, B, H, W, C, y):
     """y[b] = mean of x[b] over the rows h < valid[b] (and all of W): avgpool_fwd's bits for that slice alone."""
     assert valid.numel() >= B
     _call("scl_avgpool_fwd_masked", _p(x), _p(_klen(valid)), B, H, W, C, _p(y), _stream())
+
+
+def avgpool_bwd_masked(dy, valid, counts, B, H, W, C, dx):
+    """dx[b, h] = dy[b] / (valid[b] * W) for h < valid[b], exactly 0 beyond; counts: the same counts on the host, each in 1..H."""
+    assert valid.numel() >= B
+    _call("scl_avgpool_bwd_masked", _p(dy), _p(_klen(valid)), _host_counts(counts, B), B, H, W, C, _p(dx), _stream())
 
 
 def avgpool_bwd(dy, B, R, C, dx):

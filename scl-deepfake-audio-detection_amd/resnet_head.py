@@ -10,11 +10,14 @@ early layers come out 10-28 % off there, so it stays opt-in), every BatchNorm + 
 parameter and buffer CONTAINERS named like the reference's state dict (resnet.layer2.0.shortcut.0.weight, ...), so its checkpoints
 load; none of their torch forwards is ever called.
 
-Variable-length scoring batches (ResNetHead.forward(feats, frames), eval mode under torch.no_grad()): only the time axis H shrinks through the
+Variable-length batches (ResNetHead.forward(feats, frames)).  Scoring, eval mode under torch.no_grad(): only the time axis H shrinks through the
 network, so an utterance of T frames owns the first layer_rows(T) rows of every map.  In eval mode a BatchNorm is a per-element map and every
 convolution but conv5 reads BatchNorm outputs only: each BatchNorm + activation that feeds a convolution writes exact zeros (selected, not
 multiplied) at and beyond the utterance's own row count — what the convolution's zero border holds for the utterance alone — and the
-average runs over the utterance's own conv5 rows.
+average runs over the utterance's own conv5 rows.  Training, train mode with autograd on: the same masks, with every
+BatchNorm's batch statistics, running-statistics update and backward sums taken over the valid positions only (scl_bn_fwd_masked /
+scl_bn_bwd_masked) and the masked average differentiated; every convolution's output gradient is then zero at the padded rows, so the weight
+gradients sum valid positions only.  Basic-block networks only.
 
 Reference details kept: a block's shortcut convolution reads the block's BN+ReLU output (resnet.py:64-66); `_make_layer` builds a
 `downsample` module that is swallowed by *args and never registered (resnet.py:150-157) — no such keys here either; first_bn1 is
@@ -87,12 +90,14 @@ class PreActBlock(nn.Module):
         if stride != 1 or cin != planes:
             self.shortcut = _Shortcut(cin, planes, stride)
 
-    def run(self, x, dt, vin=None, vout=None):
-        """vin / vout: valid rows per utterance (int32 [B] on the GPU) of the block's input / output map, or None for a fixed-length batch."""
-        pooled = vin is None
-        a = hipnn.batch_norm(x, self.bn1, hipnn.ACT_RELU, grad_in_place=True, valid=vin)
+    def run(self, x, dt, vin=None, vout=None, pooled=None):
+        """vin / vout: valid rows per utterance of the block's input / output map as (int32 [B] on the GPU, the same counts on the host), or
+        None for a fixed-length batch.  pooled: whether the convolutions keep their staging maps per geometry (default: fixed-length only)."""
+        pooled = vin is None if pooled is None else pooled
+        (vi, ci), (vo, co) = vin or (None, None), vout or (None, None)
+        a = hipnn.batch_norm(x, self.bn1, hipnn.ACT_RELU, grad_in_place=True, valid=vi, counts=ci)
         skip = getattr(self.shortcut, "0").conv(a, dt, pooled=pooled) if hasattr(self, "shortcut") else x
-        h = hipnn.batch_norm(self.conv1.conv(a, dt, pooled=pooled), self.bn2, hipnn.ACT_RELU, grad_in_place=True, valid=vout)
+        h = hipnn.batch_norm(self.conv1.conv(a, dt, pooled=pooled), self.bn2, hipnn.ACT_RELU, grad_in_place=True, valid=vo, counts=co)
         return self.conv2.conv(h, dt, residual=skip, pooled=pooled)
 
 
@@ -111,13 +116,14 @@ class PreActBottleneck(nn.Module):
         if stride != 1 or cin != 4 * planes:
             self.shortcut = _Shortcut(cin, 4 * planes, stride)
 
-    def run(self, x, dt, vin=None, vout=None):
+    def run(self, x, dt, vin=None, vout=None, pooled=None):
         """vin / vout as PreActBlock.run's: bn2 sits behind the 1x1 conv1 (input rows), bn3 behind the strided conv2 (output rows)."""
-        pooled = vin is None
-        a = hipnn.batch_norm(x, self.bn1, hipnn.ACT_RELU, grad_in_place=True, valid=vin)
+        pooled = vin is None if pooled is None else pooled
+        (vi, ci), (vo, co) = vin or (None, None), vout or (None, None)
+        a = hipnn.batch_norm(x, self.bn1, hipnn.ACT_RELU, grad_in_place=True, valid=vi, counts=ci)
         skip = getattr(self.shortcut, "0").conv(a, dt, pooled=pooled) if hasattr(self, "shortcut") else x
-        h = hipnn.batch_norm(self.conv1.conv(a, dt, pooled=pooled), self.bn2, hipnn.ACT_RELU, grad_in_place=True, valid=vin)
-        h = hipnn.batch_norm(self.conv2.conv(h, dt, pooled=pooled), self.bn3, hipnn.ACT_RELU, grad_in_place=True, valid=vout)
+        h = hipnn.batch_norm(self.conv1.conv(a, dt, pooled=pooled), self.bn2, hipnn.ACT_RELU, grad_in_place=True, valid=vi, counts=ci)
+        h = hipnn.batch_norm(self.conv2.conv(h, dt, pooled=pooled), self.bn3, hipnn.ACT_RELU, grad_in_place=True, valid=vo, counts=co)
         return self.conv3.conv(h, dt, residual=skip, pooled=pooled)
 
 
@@ -147,21 +153,25 @@ class ResNet(nn.Module):
         self.bn5 = nn.BatchNorm2d(256)
         self.fc = nn.Linear(256, nclasses)          # container for fc.weight / fc.bias
 
-    def run(self, x, dt, rows=None):
+    def run(self, x, dt, rows=None, counts=None, pooled=None):
         """x [bz, T, 128, 1] -> (logits [bz, nclasses], emb [bz, 256]).
         rows: int32 [N_LEVELS, bz] on the GPU, layer_rows() of every utterance of a zero-padded variable-length batch (level 0, the frames, is
-        the caller's: x is masked already); None for a fixed-length batch."""
-        lv = (lambda i: None) if rows is None else (lambda i: rows[i])
-        pooled = rows is None
-        x = hipnn.batch_norm(self.conv1.conv(x, dt, pooled=pooled), self.bn1, hipnn.ACT_RELU, grad_in_place=True, valid=lv(1))
+        the caller's: x is masked already), and counts: the same table on the host; None for a fixed-length batch.
+        pooled: the convolutions' staging maps stay in the per-geometry pool — fixed-length batches and padded TRAINING batches (one padded
+        shape per run); a scoring batch, whose every padded length is a geometry of its own, leaves it off."""
+        lv = (lambda i: None) if rows is None else (lambda i: (rows[i], None if counts is None else counts[i]))
+        pooled = rows is None if pooled is None else pooled
+        v1 = lv(1) or (None, None)
+        x = hipnn.batch_norm(self.conv1.conv(x, dt, pooled=pooled), self.bn1, hipnn.ACT_RELU, grad_in_place=True, valid=v1[0], counts=v1[1])
         for s in (1, 2, 3, 4):
             for j, blk in enumerate(getattr(self, "layer%d" % s).children()):
-                x = blk.run(x, dt, lv(s if j == 0 else s + 1), lv(s + 1))      # a stage's first block takes the map of the stage before
-        x = hipnn.batch_norm(self.conv5.conv(x, dt, pooled=pooled), self.bn5, hipnn.ACT_RELU, grad_in_place=True, valid=lv(6))          # [bz, H', W', 256]
+                x = blk.run(x, dt, lv(s if j == 0 else s + 1), lv(s + 1), pooled)      # a stage's first block takes the map of the stage before
+        v6 = lv(6) or (None, None)
+        x = hipnn.batch_norm(self.conv5.conv(x, dt, pooled=pooled), self.bn5, hipnn.ACT_RELU, grad_in_place=True, valid=v6[0], counts=v6[1])          # [bz, H', W', 256]
         if rows is None:
             emb = hipnn.avg_pool_rows(x.reshape(x.shape[0], -1, x.shape[-1]))
         else:
-            emb = hipnn.avg_pool_rows_masked(x, rows[6])
+            emb = hipnn.avg_pool_rows_masked(x, rows[6], v6[1])
         return hipnn.linear(emb, self.fc.weight, self.fc.bias), emb
 
 
@@ -215,18 +225,30 @@ class ResNetHead(nn.Module):
         self.resnet = ResNet(**(cfg or DEFAULT_RESNET))
 
     def forward(self, feats, frames=None):
-        """frames: host-side frame counts (a list of ints, one per row of a zero-padded batch, each in min_frames()..T) — a scoring mode:
-        eval under torch.no_grad().  feats rows at or beyond an utterance's frames are not interpreted.  None: a fixed-length batch."""
-        rows = None
+        """frames: host-side frame counts (a list of ints, one per row of a zero-padded batch, each in min_frames()..T); feats rows at or
+        beyond an utterance's frames are not interpreted.  Two modes: scoring (eval under torch.no_grad(): every utterance gets what it
+        gets alone) and training (train mode with autograd on: every BatchNorm takes its batch statistics over the valid positions only,
+        hipnn.batch_norm, and the gradient of feats is exactly 0 beyond the frames); the mixed combinations are refused.
+        None: a fixed-length batch."""
+        rows = counts = None
+        train = False
         if frames is not None:
-            if self.training or torch.is_grad_enabled():
-                raise NotImplementedError("ResNetHead.forward(feats, frames) is a scoring mode: model.eval() under torch.no_grad()")
+            train = self.training and torch.is_grad_enabled()
+            if not train and (self.training or torch.is_grad_enabled()):
+                raise NotImplementedError("ResNetHead.forward(feats, frames) is a scoring mode: model.eval() under torch.no_grad() "
+                                          "(or a training mode: model.train() with autograd on)")
+            if train and STAGES[self.resnet.resnet_type][1]:
+                raise NotImplementedError("ResNetHead.forward(feats, frames): training on zero-padded batches is built for the basic-block "
+                                          "networks (resnet_type 18 / 28 / 34); the bottleneck types' 1024 / 2048-channel BatchNorms have no "
+                                          "train-mode kernel (scl_bn_fwd: C divides 256 or is 512), got resnet_type %r" % self.resnet.resnet_type)
             frames = [int(t) for t in frames]
             if len(frames) != feats.shape[0] or max(frames) > feats.shape[1]:
                 raise ValueError("frames: need one count in %d..%d per row of the %r batch, got %r"
                                  % (min_frames(self.resnet.resnet_type, self.resnet.num_nodes), feats.shape[1], tuple(feats.shape), frames))
-            host = torch.tensor(batch_rows(frames, self.resnet.resnet_type, self.resnet.num_nodes), dtype=torch.int32)
+            counts = batch_rows(frames, self.resnet.resnet_type, self.resnet.num_nodes)
+            host = torch.tensor(counts, dtype=torch.int32)
             rows = host.pin_memory().to(feats.device, non_blocking=True)
         x = hipnn.batch_norm(feats.unsqueeze(-1), self.first_bn, hipnn.ACT_SELU, grad_in_place=True,       # the [bz, 1, T, 128] map, channels last
-                             valid=None if rows is None else rows[0])
-        return self.resnet.run(x, _conv_dtype(), rows)
+                             valid=None if rows is None else rows[0], counts=None if rows is None else counts[0])
+        # a training batch has one padded shape (trim_length): its staging maps stay pooled, as the fixed-length step's
+        return self.resnet.run(x, _conv_dtype(), rows, counts if train else None, pooled=True if train else None)
