@@ -523,6 +523,12 @@ int scl_gat_score_fwd(const float* x, const float* W, const float* bias, const f
  * (dW | dbias | da[0] | da[1] | da[2]) for the caller to sum over the first dimension; dx f32 [B, N, D] */
 int scl_gat_score_bwd(const float* x, const float* W, const float* bias, const float* a, const float* ds, float* dP, float* part, float* dx,
                       int B, int N, int D, int Do, int n1, void* stream);
+/* scl_gat_score_fwd for a scoring batch of graphs of different sizes (the temporal node count of model/wav2vec2_aasist.py:541 follows the
+ * utterance's length; pair types :259-291): utterance b has nodes[b] in 1..Nmax nodes, the first n1[b] of the first type (n1 == NULL: the
+ * homogeneous layer).  nodes / n1: int32 [B] on the device.  x [B, Nmax, D] (rows >= nodes[b] are not read); s: utterance b's own
+ * [nodes[b]][nodes[b]] matrix, contiguous at the start of its Nmax * Nmax block.  The matrix-core forms only: (D, Do) in {(64, 64), (64, 32), (32, 32)}. */
+int scl_gat_score_fwd_var(const float* x, const float* W, const float* bias, const float* a, float* s, const int32_t* nodes, const int32_t* n1,
+                          int B, int Nmax, int D, int Do, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* AASIST RawNet2-style encoder: the six Residual_blocks (model/wav2vec2_aasist.py:377-433,     */
@@ -586,6 +592,19 @@ int scl_rs_bn_eval_stats(const float* gamma, const float* beta, const float* run
 /* to_dense == 0: dense [B * H' * W, Cs] -> bordered [G, Cd] (rows r_lo..r_hi, H' = r_hi - r_lo + 1; other channels and positions zero);
  * to_dense != 0: bordered [G, Cs] -> dense [B * H' * W, Cd] (the first Cd channels) */
 int scl_rs_copy(const float* src, float* dst, int Cs, int Cd, int to_dense, const SclRsGeom* geom, void* stream);
+/* Scoring batches of utterances of different widths (model/wav2vec2_aasist.py:377-433 Residual_block, :520-541 attention pooling, run as on
+ * each utterance alone): widths is int32 [B] on the device, utterance b owns the columns 1..min(widths[b], W) of its rows and everything
+ * beyond is padding — written as zeros by selection and never read into a valid result.  Forward only, eval mode.
+ * scl_rs_conv_w: scl_rs_conv with that mask, stat_mode 0, the forward shapes (cout >= cin).
+ * scl_rs_bn_act_w: scl_rs_bn_act with that mask.
+ * scl_rs_copy_w: dense [B * H' * src_w, Cs] (src_w <= W columns per row) -> bordered [G, Cd] with that mask.
+ * scl_rs_attn_pool_fwd_w: scl_rs_attn_pool_fwd over the utterance's own columns (the soft-max over the time axis and both sums); the rows
+ *   of eT [B, W, C] at and beyond the width are zeros. */
+int scl_rs_conv_w(const SclRsConv* c, const int32_t* widths, void* stream);
+int scl_rs_bn_act_w(const float* y, const float* stats, float* a, int C, int act, const SclRsGeom* geom, const int32_t* widths, void* stream);
+int scl_rs_copy_w(const float* src, float* dst, int Cs, int Cd, int src_w, const SclRsGeom* geom, const int32_t* widths, void* stream);
+int scl_rs_attn_pool_fwd_w(const float* x, const float* l, const float* pos, float* eS, float* eT, int C, const SclRsGeom* geom, const int32_t* widths,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* AASIST graph module: GraphAttentionLayer / HtrgGraphAttentionLayer / GraphPool / read-out    */
@@ -671,6 +690,17 @@ int scl_graph_final_bwd(const SclGraphFinal* f, int B, void* stream);
 #define SCL_GRAPH_MAX_REDUCE_JOBS 96
 typedef struct SclGraphReduceJob { const float* src; float* dst; int64_t stride; int32_t n, nparts; } SclGraphReduceJob;
 int scl_graph_reduce(const SclGraphReduceJob* jobs, int njobs, void* stream);
+/* The forward kernels for a scoring batch of graphs of different sizes (model/wav2vec2_aasist.py:62-155, 158-332, 336-374, 545-604 on each
+ * utterance's own nodes): every count table is int32 [B] on the device; the structs describe the padded batch (their N / n_in / K / KT are
+ * the largest counts and give the global strides); utterance b uses the first rows of every node matrix, its spectral rows directly behind
+ * its own temporal rows; rows beyond its counts are neither read nor written.  Eval mode (BatchNorm from stats, no dropout).
+ * post: layer i works on nodes_i[b] nodes (nodes_i == NULL: layers[i].N), S as scl_gat_score_fwd_var writes it.
+ * pre: unit 0 (temporal) takes t_in[b] rows and keeps t_keep[b]; unit 1 (spectral) keeps its fixed counts, reads behind unit 0's rows when
+ *   both units come from one layer (u[1].row0 != 0) and writes behind unit 0's kept rows.
+ * final: kt[b] temporal rows per branch. */
+int scl_graph_post_fwd_var(const SclGraphLayer* layers, int nlayers, const int32_t* nodes0, const int32_t* nodes1, int B, void* stream);
+int scl_graph_pre_fwd_var(const SclGraphPre* inst, int shared_pool, const int32_t* t_in, const int32_t* t_keep, int B, void* stream);
+int scl_graph_final_fwd_var(const SclGraphFinal* f, const int32_t* kt, int B, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* losses: supervised contrastive (model/loss_metrics.py:85-209) and NLL (linear_nll.py:167)   */

@@ -32,6 +32,13 @@ from model.wav2vec2_btse import wav2vec2_btse
 MODEL_REGISTRY = {"wav2vec2_linear_nll": wav2vec2_linear_nll, "wav2vec2_aasist": wav2vec2_aasist, "wav2vec2_resnet_nll": wav2vec2_resnet_nll,
                   "wav2vec2_btse": wav2vec2_btse}
 VARLEN_MODELS = ("wav2vec2_linear_nll", "wav2vec2_resnet_nll")      # --padding_type none / zero with --batch_size k: the plugins whose forward takes `lengths`
+# --padding_type none alone (scoring, never --padding_type zero --batch_size k training): plugin -> the environment switch that turns its
+# scoring mode with lengths on, read when main() runs
+VARLEN_SCORING_OPT_IN = {"wav2vec2_aasist": "SCL_AASIST_LENGTHS"}
+
+
+def _scores_varlen(name):
+    return name in VARLEN_MODELS or os.environ.get(VARLEN_SCORING_OPT_IN.get(name, ""), "0") == "1"
 
 
 class EarlyStop:
@@ -228,6 +235,7 @@ def _score_loop_varlen(dataset, model, device, batch_size, fn, workers):
     returns with rows for the whole window: the log-probs, or (log-probs, None, emb) (no emitter reads feats)."""
     from concurrent.futures import ThreadPoolExecutor
     from scl_amd.pack import VARLEN_MAX_SAMPLES, VARLEN_WINDOW, plan_varlen_batches
+    inner = getattr(dataset, "dataset", dataset)
     n = len(dataset)
     use_gpu = torch.device(device).type == "cuda"
     win = VARLEN_WINDOW * max(1, batch_size)
@@ -275,7 +283,7 @@ def _score_loop_varlen(dataset, model, device, batch_size, fn, workers):
         if pending is not None:
             emit(*pending)
     print("variable-length scoring: %d utterances, %d cut to %d samples"
-          % (n, getattr(getattr(dataset, "dataset", dataset), "n_cut", 0), VARLEN_MAX_SAMPLES))
+          % (n, getattr(inner, "n_cut", 0), getattr(inner, "max_samples", VARLEN_MAX_SAMPLES)))
 
 
 def produce_evaluation_file(dataset, model, device, save_path, batch_size=10):
@@ -403,9 +411,11 @@ def main(argv=None):
         sys.exit("main.py: model wav2vec2_btse needs the YAML key model.bio_tokenizer = '<module>:<callable>' (waveforms [bz, L] numpy, "
                  "sample_rate) -> equal-length token rows; the reference's biosegment package does not exist, so %s cannot run as shipped "
                  "(scl_amd/model_btse.py; bench.py --model wav2vec2_btse feeds synthetic tokens)" % args.config)
-    if args.padding_type == "none" and config["model"]["name"] not in VARLEN_MODELS:
+    if args.padding_type == "none" and not _scores_varlen(config["model"]["name"]):
+        switch = VARLEN_SCORING_OPT_IN.get(config["model"]["name"])
         sys.exit("main.py: --padding_type none needs a model that takes per-utterance lengths: wav2vec2_linear_nll only, or the scoring mode "
-                 "of wav2vec2_resnet_nll (%s has no padding mask in its back-end); use --padding_type zero or repeat" % config["model"]["name"])
+                 "of wav2vec2_resnet_nll (%s has no padding mask in its back-end); use --padding_type zero or repeat" % config["model"]["name"]
+                 + ("" if switch is None else ".  %s=1 turns on this plugin's scoring mode with lengths" % switch))
     model = MODEL_REGISTRY[config["model"]["name"]](config["model"], device, seed=args.seed, rank=rank)
     print("nb_params:", sum(p.numel() for p in model.parameters()))
 
@@ -441,6 +451,7 @@ def main(argv=None):
         eval_set = Dataset_for_eval(list_IDs=file_eval, base_dir=os.path.join(args.database_path + "/"), padding_type=args.padding_type)
         if args.padding_type == "none":      # shorter files are zero-padded to what the model takes (400 samples; 17,680 for the ResNet back-end)
             eval_set.min_samples = model.min_samples()
+            eval_set.max_samples = model.max_samples() if hasattr(model, "max_samples") else eval_set.max_samples      # longer files are cut (77,839 for the AASIST back-end)
         final_output = args.eval_output
         if world > 1:
             eval_set = Subset(eval_set, list(range(rank, len(eval_set), world)))

@@ -9,6 +9,14 @@ attention scores are the fused kernels of csrc/gat.hip, projections / att @ x / 
 element-wise glue (soft-max over <= 66 nodes, top-k, gathers).  nn.Linear / nn.BatchNorm* objects below are parameter and buffer
 containers under the reference's state-dict names; their torch forwards are never called.
 
+Variable-length batches (AasistHead.forward_frames(feats, frames)): scoring only, eval mode under torch.no_grad().  An utterance of T frames owns
+W = T // 3 columns of every map of the stack and W temporal nodes.  In eval mode every BatchNorm is a per-element map, so padding can reach an
+utterance only through a convolution's taps, the soft-max over the time axis and the graph module's node count: every convolution input is
+written as exact zeros (selected, not multiplied) at and beyond the utterance's width — what the convolution's zero border holds for the
+utterance alone — the attention pooling runs over the utterance's own columns, and the graph kernels take their node counts per utterance
+(node_counts; csrc/resstack.hip, gat.hip, graph.hip).  The masks live in the fused kernels, so the mode has their limits:
+min_frames() .. max_frames() frames per utterance.
+
 Reference quirks kept on purpose: Residual_block applies conv1 to its INPUT (the bn1+SELU result is discarded, :414-420; in training
 that BatchNorm still updates its running statistics); the temporal / spectral attention pools share one 1x1-conv score map.
 """
@@ -27,6 +35,48 @@ FUSED_GRAPH = os.environ.get("SCL_AASIST_FUSED_GRAPH", os.environ.get("SCL_AASIS
 
 UPSTREAM_AASIST = {"filts": [128, [1, 32], [32, 32], [32, 64], [64, 64]], "gat_dims": [64, 32],
                    "pool_ratios": [0.5, 0.5, 0.5, 0.5], "temperatures": [2.0, 2.0, 100.0, 100.0], "nclasses": 2}
+
+
+SPECTRAL_NODES = 128 // 3      # rows of the map behind the 3 x 3 max pool of the 128 LL features = spectral nodes (pos_S)
+POOL = 3                       # the max pool's window and stride along time
+
+
+def _keep(n, k):
+    """GraphPool's count of kept nodes (model/wav2vec2_aasist.py:352)."""
+    return max(int(n * k), 1)
+
+
+def node_counts(frames, cfg=None):
+    """Host-side node counts of utterances of `frames` LL frames each: W (map columns = temporal nodes), kT / kT2 (temporal nodes behind the
+    first / second GraphPool), N1 / N2 (nodes of the heterogeneous layers), per utterance, and the spectral side's fixed nS, kS, kS2.  The
+    kernels' count tables and the tests read this one function."""
+    pr = (cfg or UPSTREAM_AASIST)["pool_ratios"]
+    nS = SPECTRAL_NODES
+    kS = _keep(nS, pr[0])
+    kS2 = _keep(kS, pr[2])
+    W = [int(t) // POOL for t in frames]
+    kT = [_keep(w, pr[1]) for w in W]
+    kT2 = [_keep(k, pr[2]) for k in kT]
+    return dict(W=W, kT=kT, kT2=kT2, N1=[k + kS for k in kT], N2=[k + kS2 for k in kT2], nS=nS, kS=kS, kS2=kS2)
+
+
+def min_frames():
+    """The fewest frames forward_frames takes: the max pool needs one whole window."""
+    return POOL
+
+
+def max_nodes(cfg=None):
+    """The most temporal nodes per utterance the fused kernels take: graph.MAX_NODES in a homogeneous layer, kS + kT <= graph.MAX_HTRG_NODES in a
+    heterogeneous one, maps up to resstack.MAX_W wide."""
+    w = min(graph.MAX_NODES, resstack.MAX_W)
+    while w > 1 and node_counts([w * POOL], cfg)["N1"][0] > graph.MAX_HTRG_NODES:
+        w -= 1
+    return w
+
+
+def max_frames(cfg=None):
+    """The most frames per utterance forward_frames takes (a last partial pool window included)."""
+    return max_nodes(cfg) * POOL + POOL - 1
 
 
 def _xavier(*size):
@@ -137,6 +187,7 @@ class AasistHead(nn.Module):
     def __init__(self, cfg=None):
         super().__init__()
         cfg = cfg or UPSTREAM_AASIST
+        self.pool_cfg = {"pool_ratios": [float(v) for v in cfg["pool_ratios"]]}
         filts, gat, pr, temp = cfg["filts"], cfg["gat_dims"], cfg["pool_ratios"], cfg["temperatures"]
         self.first_bn = nn.BatchNorm2d(1)
         self.first_bn1 = nn.BatchNorm2d(64)
@@ -189,6 +240,40 @@ class AasistHead(nn.Module):
         if FUSED_GRAPH and graph.supported(self, e_S.shape[1], e_T.shape[1]):
             return graph.graph_module(e_S, e_T, self)          # the whole graph module as one autograd node (csrc/graph.hip)
         return AasistHead.graph_unfused(self, e_S, e_T)
+
+    def frames_supported(self):
+        """Whether this configuration's shapes run on the fused stack, attention block and graph module (forward_frames has no other path)."""
+        blocks = [blk[0] for blk in self.encoder]
+        return bool(FUSED_STACK and FUSED_GRAPH and resstack.supported(blocks, 1) and self.pos_S.shape[1] == SPECTRAL_NODES
+                    and resstack.attn_supported(self.first_bn1, self.attention, self.pos_S, blocks[-1].conv2.weight.shape[0])
+                    and graph.supported(self, SPECTRAL_NODES, max_nodes(self.pool_cfg)))
+
+    def forward_frames(self, feats, frames):
+        """Scoring mode (eval under torch.no_grad()): feats [B, T, 128] zero-padded, frames: host-side frame counts (ints, one per row, each in
+        min_frames()..min(T, max_frames())) -> (logits, last_hidden), every row what forward gives feats[b:b+1, :frames[b]] alone.  Rows of
+        feats at and beyond an utterance's frames are not interpreted; only the first 3 * (longest utterance's columns) rows are read."""
+        if self.training or torch.is_grad_enabled():
+            raise NotImplementedError("AasistHead.forward_frames is a scoring mode: model.eval() under torch.no_grad() (training with lengths "
+                                      "needs masked batch statistics inside the fused stack)")
+        if not AasistHead.frames_supported(self):
+            raise NotImplementedError("AasistHead.forward_frames runs on the fused stack and graph kernels only (csrc/resstack.hip, graph.hip): "
+                                      "this configuration's shapes are not theirs, or SCL_AASIST_FUSED=0 / SCL_AASIST_FUSED_GRAPH=0 is set")
+        frames = [int(t) for t in frames]
+        lo, hi = min_frames(), max_frames(self.pool_cfg)
+        if len(frames) != feats.shape[0] or not frames or min(frames) < lo or max(frames) > feats.shape[1]:
+            raise ValueError("frames: need one count in %d..%d per row of the %r batch, got %r" % (lo, feats.shape[1], tuple(feats.shape), frames))
+        if max(frames) > hi:
+            raise ValueError("AASIST back-end: an utterance of %d frames exceeds the %d frames forward(x, lengths) takes: the masks live in the "
+                             "fused kernels, whose graph module keeps at most %d temporal nodes (%d frames each) per utterance in LDS"
+                             % (max(frames), hi, max_nodes(self.pool_cfg), POOL))
+        counts = node_counts(frames, self.pool_cfg)
+        w_max = max(counts["W"])
+        # only the batch's longest utterance sizes the maps, whatever T the batch was padded to
+        x = hipnn.max_pool3(feats[:, :POOL * w_max].transpose(1, 2)).unsqueeze(-1)
+        x = hipnn.batch_norm(x, self.first_bn, hipnn.ACT_SELU)
+        blocks = [blk[0] for blk in self.encoder]
+        e_S, e_T = resstack.res_stack_pool_widths(x, counts["W"], blocks, self.first_bn1, self.attention, self.pos_S)
+        return graph.graph_module_counts(e_S, e_T, self, counts)
 
     def graph_unfused(self, e_S, e_T):
         """The graph module as a composition of per-operation autograd Functions (round 2): the fall-back for graph sizes the fused

@@ -218,15 +218,26 @@ __device__ __forceinline__ void gat_stage_x(float* xs, const float* __restrict__
     for (int e = threadIdx.x; e < (N + 16) * D; e += GAT_PAIRS) { const int r = e / D, d = e - r * D; xs[r * (D + 1) + d] = r < N ? xb[e] : 0.f; }
 }
 
-template <int D, int Do>
+// VAR: graphs of different sizes in one batch (scoring).  Utterance b has nodes[b] <= Nmax nodes, the first n1s[b] of the first type; x keeps
+// the padded batch's strides ([B, Nmax, D], rows >= nodes[b] are not read), s is written as the utterance's own [nodes[b]][nodes[b]]
+// matrix at the start of its Nmax * Nmax block.  Everything that differs per utterance is uniform in a workgroup.
+template <int D, int Do, bool VAR = false>
 __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_fwd_mfma_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                                          const float* __restrict__ bias, const float* __restrict__ a,
-                                                                         float* __restrict__ s, int N, int n1) {
+                                                                         float* __restrict__ s, int Nmax, int n1, const int* __restrict__ nodes = nullptr,
+                                                                         const int* __restrict__ n1s = nullptr) {
     constexpr int NS = D / 4, NOB = Do / 16, XP = D + 1;
     extern __shared__ float sm[];
     float* xs = sm;
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
-    gat_stage_x<D>(xs, x + (int64_t)b * N * D, N);
+    int N = Nmax;
+    if (VAR) {
+        N = nodes[b]; N = N < 1 ? 1 : (N > Nmax ? Nmax : N);
+        n1 = n1s ? n1s[b] : N; n1 = n1 < 0 ? 0 : (n1 > N ? N : n1);
+        const int ipb_ = (N + (int)gridDim.x - 1) / (int)gridDim.x;
+        if ((int)blockIdx.x * ipb_ >= N) return;      // a block wholly beyond the utterance's nodes: the whole workgroup leaves before any barrier
+    }
+    gat_stage_x<D>(xs, x + (int64_t)b * Nmax * D, N);
     float wr[NOB][NS], bo[NOB], av[3][NOB];
 #pragma unroll
     for (int ob = 0; ob < NOB; ++ob) {
@@ -263,7 +274,7 @@ __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_fwd_mfma_kernel(const 
         }
         if (li == 0) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { const int j = j0 + 4 * g + r; if (j < N) s[((int64_t)b * N + i) * N + j] = sc[r]; }
+            for (int r = 0; r < 4; ++r) { const int j = j0 + 4 * g + r; if (j < N) s[(int64_t)b * Nmax * Nmax + (int64_t)i * N + j] = sc[r]; }
         }
     }
 }
@@ -415,7 +426,7 @@ extern "C" int scl_gat_score_fwd(const float* x, const float* W, const float* bi
                 "gat_score_fwd: need D in {32, 64}, Do <= 64, N <= 128 (D=%d Do=%d N=%d)", D, Do, N);
     dim3 grid(scl_gat_score_nblocks(N), B), block(GAT_PAIRS);
     hipStream_t st = (hipStream_t)stream;
-#define GAT_FWD_MFMA(DD, OO) hipLaunchKernelGGL((gat_score_fwd_mfma_kernel<DD, OO>), grid, block, (gat_mfma_lds<DD, OO>(N, false)), st, x, W, bias, a, s, N, n1)
+#define GAT_FWD_MFMA(DD, OO) hipLaunchKernelGGL((gat_score_fwd_mfma_kernel<DD, OO>), grid, block, (gat_mfma_lds<DD, OO>(N, false)), st, x, W, bias, a, s, N, n1, (const int*)nullptr, (const int*)nullptr)
     if (D == 64 && Do == 64) { GAT_FWD_MFMA(64, 64); return scl_check_launch("scl_gat_score_fwd"); }
     if (D == 64 && Do == 32) { GAT_FWD_MFMA(64, 32); return scl_check_launch("scl_gat_score_fwd"); }
     if (D == 32 && Do == 32) { GAT_FWD_MFMA(32, 32); return scl_check_launch("scl_gat_score_fwd"); }
@@ -428,6 +439,21 @@ extern "C" int scl_gat_score_fwd(const float* x, const float* W, const float* bi
         hipLaunchKernelGGL((gat_score_fwd_kernel<32>), grid, block, lds, st, x, W, bias, a, s, N, Do, n1);
     }
     return scl_check_launch("scl_gat_score_fwd");
+}
+
+extern "C" int scl_gat_score_fwd_var(const float* x, const float* W, const float* bias, const float* a, float* s, const int32_t* nodes, const int32_t* n1,
+                                     int B, int Nmax, int D, int Do, void* stream) {
+    SCL_REQUIRE(x && W && bias && a && s && nodes && B > 0, "scl_gat_score_fwd_var: null pointer");
+    SCL_REQUIRE(((D == 64 && (Do == 64 || Do == 32)) || (D == 32 && Do == 32)) && Nmax >= 1 && Nmax <= GAT_MAXN,
+                "scl_gat_score_fwd_var: the matrix-core forms only: (D, Do) in {(64, 64), (64, 32), (32, 32)}, Nmax <= 128 (D=%d Do=%d Nmax=%d)", D, Do, Nmax);
+    dim3 grid(scl_gat_score_nblocks(Nmax), B), block(GAT_PAIRS);
+    hipStream_t st = (hipStream_t)stream;
+#define GAT_FWD_VAR(DD, OO) hipLaunchKernelGGL((gat_score_fwd_mfma_kernel<DD, OO, true>), grid, block, (gat_mfma_lds<DD, OO>(Nmax, false)), st, x, W, bias, a, s, Nmax, 0, nodes, n1)
+    if (D == 64 && Do == 64) GAT_FWD_VAR(64, 64);
+    else if (D == 64 && Do == 32) GAT_FWD_VAR(64, 32);
+    else GAT_FWD_VAR(32, 32);
+#undef GAT_FWD_VAR
+    return scl_check_launch("scl_gat_score_fwd_var");
 }
 
 // dP: f32 [B, N*N, D] scratch; part: f32 [B * nblocks(N)][Do*D + 4*Do] partial sums (dW | dbias | da11 | da22 | da12), to be

@@ -146,22 +146,28 @@ __global__ __launch_bounds__(GT) void graph_drop_kernel(const DropArgs a) {
 
 // ---- attention layer, second half ------------------------------------------------------------------------------------------------------
 typedef SclGraphLayer PostI;
-struct PostArgs { PostI L[2]; };
+struct PostArgs { PostI L[2]; const int* nodes[2]; };      // nodes: per-utterance node counts of the VAR forward (NULL: L.N)
 
+// VAR (scoring batches of graphs of different sizes): utterance b works on its first N = nodes[b] <= L.N rows of every node matrix and on
+// its own [N][N] score matrix; the global strides stay the padded batch's (Nmax = L.N) and rows beyond N are neither read nor written.
+// N is uniform in the workgroup, so every barrier below is reached by all of it.
+template <bool VAR>
 __global__ __launch_bounds__(GT) void graph_post_fwd_kernel(const PostArgs args) {
     const PostI& L = args.L[blockIdx.y];
-    const int b = blockIdx.x, tid = threadIdx.x, N = L.N, D = L.D, Do = L.Do;
+    const int b = blockIdx.x, tid = threadIdx.x, Nmax = L.N, D = L.D, Do = L.Do;
+    int N = Nmax;
+    if (VAR && args.nodes[blockIdx.y]) { N = args.nodes[blockIdx.y][b]; N = N < 1 ? 1 : (N > Nmax ? Nmax : N); }
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Bump bp{lds};
-    float* LA = bp.take(N * N);
-    float* LX = bp.take(N * (D + GP));
-    float* LG = bp.take(N * (D + GP));
-    float* LY = bp.take(N * (Do + GP));
+    float* LA = bp.take(Nmax * Nmax);
+    float* LX = bp.take(Nmax * (D + GP));
+    float* LG = bp.take(Nmax * (D + GP));
+    float* LY = bp.take(Nmax * (Do + GP));
     float* WL = bp.take(64 * (64 + GP));
     float* LV = bp.take(256);                       // small vectors: master, scores, ...
     double* mine = reinterpret_cast<double*>(bp.take(4 * 64 * 2 + 8));
-    g_load(LX, D + GP, L.xd + (size_t)b * N * D, N, D);
-    float* Sg = L.S + (size_t)b * N * N;
+    g_load(LX, D + GP, L.xd + (size_t)b * Nmax * D, N, D);
+    float* Sg = L.S + (size_t)b * Nmax * Nmax;
     for (int e = tid; e < N * N; e += GT) LA[e] = Sg[e];
     __syncthreads();
     softmax_rows(LA, N, N, L.inv_temp);
@@ -178,14 +184,14 @@ __global__ __launch_bounds__(GT) void graph_post_fwd_kernel(const PostArgs args)
     }
     stage_w(WL, L.Wa, Do, D);
     __syncthreads();
-    g_store(L.g + (size_t)b * N * D, LG, D + GP, N, D);
+    g_store(L.g + (size_t)b * Nmax * D, LG, D + GP, N, D);
     mm_nt(LY, Do + GP, LG, D + GP, WL, L.ba, N, D, Do, false);
     __syncthreads();
     stage_w(WL, L.Wb, Do, D);
     __syncthreads();
     mm_nt(LY, Do + GP, LX, D + GP, WL, L.bb, N, D, Do, true);
     __syncthreads();
-    g_store(L.y + (size_t)b * N * Do, LY, Do + GP, N, Do);
+    g_store(L.y + (size_t)b * Nmax * Do, LY, Do + GP, N, Do);
     bn_block_sums(mine, N, Do, [&](int n, int c, float& u, float& v) { u = LY[n * (Do + GP) + c]; v = u * u; });
     if (L.has_master) {
         float* LM = LV;            // master in [D]
@@ -199,7 +205,7 @@ __global__ __launch_bounds__(GT) void graph_post_fwd_kernel(const PostArgs args)
         __syncthreads();
         for (int e = tid; e < N * Do; e += GT) { const int n = e / Do, o = e - n * Do; LY[n * (Do + GP) + o] = g_tanh(LY[n * (Do + GP) + o]); }
         __syncthreads();
-        g_store(L.tM + (size_t)b * N * Do, LY, Do + GP, N, Do);
+        g_store(L.tM + (size_t)b * Nmax * Do, LY, Do + GP, N, Do);
         if (tid < N) {
             float s = 0.f;
             for (int o = 0; o < Do; ++o) s = fmaf(LY[tid * (Do + GP) + o], L.aM[o], s);
@@ -215,7 +221,7 @@ __global__ __launch_bounds__(GT) void graph_post_fwd_kernel(const PostArgs args)
             if (tid + 64 < N) LS[tid + 64] = e1 * inv;
         }
         __syncthreads();
-        if (tid < N) L.am[(size_t)b * N + tid] = LS[tid];
+        if (tid < N) L.am[(size_t)b * Nmax + tid] = LS[tid];
         float* LGM = LV + 192;     // [D]
         if (tid < D) {
             float s = 0.f;
@@ -386,16 +392,17 @@ __global__ __launch_bounds__(GT) void graph_post_bwd_kernel(const PostArgs args)
 // ---- BatchNorm + SELU, GraphPool, proj_type, input dropout: what sits between two attention layers -------------------------------------------
 typedef SclGraphPoolUnit PoolU;
 typedef SclGraphPre PreI;
-struct PreArgs { PreI I[2]; int shared_pool; };      // shared_pool: both instances read the SAME pooled nodes (layers ST11 / ST21 share pool_S / pool_T)
+struct PreArgs { PreI I[2]; int shared_pool; const int* tn_in; const int* tK; };      // shared_pool: both instances read the SAME pooled nodes (layers ST11 / ST21 share pool_S / pool_T)
 
 // GraphPool of one unit: LH [n_in][Dp + GP] holds h; writes scores, indices and the gated, gathered rows into LP [K][Dp + GP]
-__device__ __forceinline__ void pool_fwd(const PoolU& u, int b, int Dp, float* LH, float* LP, float* LS, int* LI, bool store) {
-    const int tid = threadIdx.x, n_in = u.n_in;
+// (n_in, K: this utterance's counts; n_max, K_max: the strides of sc / idx — the same but for a batch of graphs of different sizes)
+__device__ __forceinline__ void pool_fwd(const PoolU& u, int b, int Dp, float* LH, float* LP, float* LS, int* LI, bool store, int n_in, int K, int n_max, int K_max) {
+    const int tid = threadIdx.x;
     if (tid < n_in) {
         float s = u.pb[0];
         for (int d = 0; d < Dp; ++d) {
             float z = LH[tid * (Dp + GP) + d];
-            if (u.pool_p > 0.f) z *= dropout_scale(u.pool_seed, (uint64_t)(((size_t)b * n_in + tid) * Dp + d), u.pool_p);
+            if (u.pool_p > 0.f) z *= dropout_scale(u.pool_seed, (uint64_t)(((size_t)b * n_max + tid) * Dp + d), u.pool_p);
             s = fmaf(z, u.pw[d], s);
         }
         LS[tid] = 1.0f / (1.0f + __expf(-s));
@@ -405,52 +412,64 @@ __device__ __forceinline__ void pool_fwd(const PoolU& u, int b, int Dp, float* L
         const float s = LS[tid];
         int rank = 0;
         for (int m = 0; m < n_in; ++m) { const float t = LS[m]; rank += (t > s || (t == s && m < tid)) ? 1 : 0; }
-        if (rank < u.K) LI[rank] = tid;
-        if (store) u.sc[(size_t)b * n_in + tid] = s;
+        if (rank < K) LI[rank] = tid;
+        if (store) u.sc[(size_t)b * n_max + tid] = s;
     }
     __syncthreads();
-    if (store && tid < u.K) u.idx[(size_t)b * u.K + tid] = LI[tid];
-    for (int e = tid; e < u.K * Dp; e += GT) {
+    if (store && tid < K) u.idx[(size_t)b * K_max + tid] = LI[tid];
+    for (int e = tid; e < K * Dp; e += GT) {
         const int r = e / Dp, d = e - r * Dp, n = LI[r];
         LP[r * (Dp + GP) + d] = LH[n * (Dp + GP) + d] * LS[n];
     }
     __syncthreads();
 }
 
+// VAR: the first unit (the temporal nodes) has n_in = tn_in[b] rows of which it keeps K = tK[b]; the second unit (spectral nodes) keeps its
+// fixed counts, reads its rows directly behind the first unit's own rows when both come from one layer (u[1].row0 != 0) and writes its
+// pooled rows directly behind the first unit's K.  Strides are the padded batch's; rows beyond an utterance's counts are not touched.
+template <bool VAR>
 __global__ __launch_bounds__(GT) void graph_pre_fwd_kernel(const PreArgs args) {
     const PreI& I = args.I[blockIdx.y];
-    const int b = blockIdx.x, tid = threadIdx.x, Dp = I.Dp, N = I.N;
+    const int b = blockIdx.x, tid = threadIdx.x, Dp = I.Dp, Nmax = I.N;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Bump bp{lds};
     float* LH = bp.take(96 * (Dp + GP));
-    float* LP = bp.take(N * (Dp + GP));         // pooled rows of both units, concatenated
-    float* LXo = bp.take(N * (Dp + GP));
+    float* LP = bp.take(Nmax * (Dp + GP));         // pooled rows of both units, concatenated
+    float* LXo = bp.take(Nmax * (Dp + GP));
     float* WL = bp.take(64 * (64 + GP));
     float* LS = bp.take(128);
     int* LI = reinterpret_cast<int*>(bp.take(128));
     const bool store = I.store_common != 0;
+    int n0 = I.u[0].n_in, K0 = I.u[0].K;
+    if (VAR) {
+        n0 = args.tn_in[b]; n0 = n0 < 1 ? 1 : (n0 > I.u[0].n_in ? I.u[0].n_in : n0);
+        K0 = args.tK[b]; K0 = K0 < 1 ? 1 : (K0 > I.u[0].K ? I.u[0].K : K0); K0 = K0 > n0 ? n0 : K0;
+    }
+    const int N = K0 + I.u[1].K;
     for (int ui = 0; ui < 2; ++ui) {
         const PoolU& u = I.u[ui];
-        const float* ys = u.ysrc + ((size_t)b * u.src_n + u.row0) * Dp;
-        for (int e = tid; e < u.n_in * Dp; e += GT) {
+        const int n_in = ui == 0 ? n0 : u.n_in, K = ui == 0 ? K0 : u.K;
+        const int row0 = (VAR && ui == 1 && u.row0 != 0) ? n0 : u.row0, row_out = (VAR && ui == 1) ? K0 : u.row_out;
+        const float* ys = u.ysrc + ((size_t)b * u.src_n + row0) * Dp;
+        for (int e = tid; e < n_in * Dp; e += GT) {
             const int n = e / Dp, d = e - n * Dp;
             const float v = selu_f((ys[e] - u.stats[d]) * u.stats[2 * Dp + d] + u.stats[3 * Dp + d]);
             LH[n * (Dp + GP) + d] = v;
             if (store) u.h[(size_t)b * u.n_in * Dp + e] = v;
         }
         __syncthreads();
-        pool_fwd(u, b, Dp, LH, LP + u.row_out * (Dp + GP), LS, LI, store);
-        if (store) g_store(u.pooled + (size_t)b * u.K * Dp, LP + u.row_out * (Dp + GP), Dp + GP, u.K, Dp);
+        pool_fwd(u, b, Dp, LH, LP + row_out * (Dp + GP), LS, LI, store, n_in, K, u.n_in, u.K);
+        if (store) g_store(u.pooled + (size_t)b * u.K * Dp, LP + row_out * (Dp + GP), Dp + GP, K, Dp);
         stage_w(WL, u.Wt, Dp, Dp);
         __syncthreads();
-        mm_nt(LXo + u.row_out * (Dp + GP), Dp + GP, LP + u.row_out * (Dp + GP), Dp + GP, WL, u.bt, u.K, Dp, Dp, false);
+        mm_nt(LXo + row_out * (Dp + GP), Dp + GP, LP + row_out * (Dp + GP), Dp + GP, WL, u.bt, K, Dp, Dp, false);
         __syncthreads();
     }
-    float* xg = I.xd + (size_t)b * N * Dp;
+    float* xg = I.xd + (size_t)b * Nmax * Dp;
     for (int e = tid; e < N * Dp; e += GT) {
         const int n = e / Dp, d = e - n * Dp;
         float v = LXo[n * (Dp + GP) + d];
-        if (I.in_p > 0.f) v *= dropout_scale(I.in_seed, (uint64_t)((size_t)b * N * Dp + e), I.in_p);
+        if (I.in_p > 0.f) v *= dropout_scale(I.in_seed, (uint64_t)((size_t)b * Nmax * Dp + e), I.in_p);
         xg[e] = v;
     }
 }
@@ -582,18 +601,19 @@ typedef SclGraphFinalBranch FinalBr;
 typedef SclGraphFinal FinalArgs;
 
 // forward values of one utterance into LDS: T_b, S_b [2][K][D], m_b [2][D] after residual add and drop_way, aug kept for the backward
-__device__ __forceinline__ void final_branches(const FinalArgs& a, int b, float* LT, float* LSn, float* LMm, float* LAUG) {
-    const int tid = threadIdx.x, KT = a.KT, KS = a.KS, D = a.D, N2 = KT + KS;
+// (KT: this utterance's temporal rows; a.KT: the padded batch's, which the global strides follow)
+__device__ __forceinline__ void final_branches(const FinalArgs& a, int b, int KT, float* LT, float* LSn, float* LMm, float* LAUG) {
+    const int tid = threadIdx.x, KS = a.KS, D = a.D, N2 = KT + KS, KTm = a.KT, N2m = KTm + KS;
     for (int br = 0; br < 2; ++br) {
         const FinalBr& B_ = a.br[br];
-        const float* y = B_.y2 + (size_t)b * N2 * D;
+        const float* y = B_.y2 + (size_t)b * N2m * D;
         for (int e = tid; e < N2 * D; e += GT) {
             const int n = e / D, d = e - n * D;
             const float aug = selu_f((y[e] - B_.stats2[d]) * B_.stats2[2 * D + d] + B_.stats2[3 * D + d]);
             LAUG[br * N2 * D + e] = aug;
             if (n < KT) {
-                float v = B_.Tp[(size_t)b * KT * D + e] + aug;
-                if (a.way_p > 0.f) v *= dropout_scale(B_.way_seed[0], (uint64_t)((size_t)b * KT * D + e), a.way_p);
+                float v = B_.Tp[(size_t)b * KTm * D + e] + aug;
+                if (a.way_p > 0.f) v *= dropout_scale(B_.way_seed[0], (uint64_t)((size_t)b * KTm * D + e), a.way_p);
                 LT[br * KT * D + e] = v;
             } else {
                 const int e2 = e - KT * D;
@@ -611,13 +631,18 @@ __device__ __forceinline__ void final_branches(const FinalArgs& a, int b, float*
     __syncthreads();
 }
 
-__global__ __launch_bounds__(GT) void graph_final_fwd_kernel(const FinalArgs a) {
-    const int b = blockIdx.x, tid = threadIdx.x, KT = a.KT, KS = a.KS, D = a.D, N2 = KT + KS;
+// VAR: utterance b reads out its own kts[b] <= a.KT temporal rows (the spectral rows sit directly behind them in y2): |max|, mean and the
+// branch max run over those rows alone
+template <bool VAR>
+__global__ __launch_bounds__(GT) void graph_final_fwd_kernel(const FinalArgs a, const int* __restrict__ kts) {
+    const int b = blockIdx.x, tid = threadIdx.x, KS = a.KS, D = a.D, N2m = a.KT + KS;
+    int KT = a.KT;
+    if (VAR) { KT = kts[b]; KT = KT < 1 ? 1 : (KT > a.KT ? a.KT : KT); }
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Bump bp{lds};
-    float* LT = bp.take(2 * KT * D); float* LSn = bp.take(2 * KS * D); float* LMm = bp.take(2 * D); float* LAUG = bp.take(2 * N2 * D);
+    float* LT = bp.take(2 * a.KT * D); float* LSn = bp.take(2 * KS * D); float* LMm = bp.take(2 * D); float* LAUG = bp.take(2 * N2m * D);
     float* LH = bp.take(5 * D);
-    final_branches(a, b, LT, LSn, LMm, LAUG);
+    final_branches(a, b, KT, LT, LSn, LMm, LAUG);
     if (tid < D) {
         float mx = 0.f, sm = 0.f;
         for (int n = 0; n < KT; ++n) { const float v = fmaxf(LT[n * D + tid], LT[KT * D + n * D + tid]); mx = fmaxf(mx, fabsf(v)); sm += v; }
@@ -657,7 +682,7 @@ __global__ __launch_bounds__(GT) void graph_final_bwd_kernel(const FinalArgs a) 
     int* LIX = reinterpret_cast<int*>(bp.take(2 * D));
     float* LDZ = bp.take(N2 * (D + GP));
     double* mine = reinterpret_cast<double*>(bp.take(4 * 64 * 2 + 8));
-    final_branches(a, b, LT, LSn, LMm, LAUG);
+    final_branches(a, b, KT, LT, LSn, LMm, LAUG);
     float* slab = a.slab + (size_t)b * a.slab_bs;
     if (tid < a.NC) LDL[tid] = a.d_logits ? a.d_logits[(size_t)b * a.NC + tid] : 0.f;
     if (tid < D) {      // forward read-out again: values and the arg of the |max|
@@ -786,12 +811,27 @@ size_t layer_lds(const SclGraphLayer* L, int n, bool bwd) {
 extern "C" int scl_graph_post_fwd(const SclGraphLayer* layers, int nlayers, int B, void* stream) {
     SCL_REQUIRE(layers && (nlayers == 1 || nlayers == 2) && B > 0, "graph_post_fwd: 1 or 2 layers");
     PostArgs a;
+    a.nodes[0] = a.nodes[1] = nullptr;
     for (int i = 0; i < nlayers; ++i) { SCL_REQUIRE(layer_ok(layers[i]), "graph_post_fwd: layer %d: N <= 96 (64 with a master node), D / Do in {32, 64}", i); a.L[i] = layers[i]; }
-    return g_launch(graph_post_fwd_kernel, dim3(B, nlayers), layer_lds(layers, nlayers, false), (hipStream_t)stream, a, "graph_post_fwd");
+    return g_launch(graph_post_fwd_kernel<false>, dim3(B, nlayers), layer_lds(layers, nlayers, false), (hipStream_t)stream, a, "graph_post_fwd");
+}
+extern "C" int scl_graph_post_fwd_var(const SclGraphLayer* layers, int nlayers, const int32_t* nodes0, const int32_t* nodes1, int B, void* stream) {
+    SCL_REQUIRE(layers && (nlayers == 1 || nlayers == 2) && B > 0 && (nodes0 || nodes1), "scl_graph_post_fwd_var: 1 or 2 layers, a node-count table for at least one");
+    PostArgs a;
+    a.nodes[0] = nodes0; a.nodes[1] = nlayers == 2 ? nodes1 : nullptr;
+    for (int i = 0; i < nlayers; ++i) {
+        SCL_REQUIRE(layers[i].xd && layers[i].S && layers[i].g && layers[i].y && layers[i].Wa && layers[i].Wb && layers[i].ba && layers[i].bb && layers[i].bn.stats,
+                    "scl_graph_post_fwd_var: layer %d: null pointer", i);
+        SCL_REQUIRE(layer_ok(layers[i]), "scl_graph_post_fwd_var: layer %d: N <= 96 (64 with a master node), D / Do in {32, 64}", i);
+        SCL_REQUIRE(!layers[i].bn.training, "scl_graph_post_fwd_var: layer %d: a scoring-mode forward (BatchNorm in eval mode)", i);
+        a.L[i] = layers[i];
+    }
+    return g_launch(graph_post_fwd_kernel<true>, dim3(B, nlayers), layer_lds(layers, nlayers, false), (hipStream_t)stream, a, "scl_graph_post_fwd_var");
 }
 extern "C" int scl_graph_post_bwd(const SclGraphLayer* layers, int nlayers, int B, void* stream) {
     SCL_REQUIRE(layers && (nlayers == 1 || nlayers == 2) && B > 0, "graph_post_bwd: 1 or 2 layers");
     PostArgs a;
+    a.nodes[0] = a.nodes[1] = nullptr;
     for (int i = 0; i < nlayers; ++i) { SCL_REQUIRE(layer_ok(layers[i]), "graph_post_bwd: layer %d: N <= 96 (64 with a master node), D / Do in {32, 64}", i); a.L[i] = layers[i]; }
     return g_launch(graph_post_bwd_kernel, dim3(B, nlayers), layer_lds(layers, nlayers, true), (hipStream_t)stream, a, "graph_post_bwd");
 }
@@ -805,14 +845,23 @@ static bool pre_ok(const SclGraphPre* I) {
 }
 extern "C" int scl_graph_pre_fwd(const SclGraphPre* inst, int shared_pool, int B, void* stream) {
     SCL_REQUIRE(inst && B > 0 && pre_ok(inst), "graph_pre_fwd: two instances of equal shape, <= 96 nodes per unit, width 32 or 64");
-    PreArgs a; a.I[0] = inst[0]; a.I[1] = inst[1]; a.shared_pool = shared_pool;
+    PreArgs a; a.I[0] = inst[0]; a.I[1] = inst[1]; a.shared_pool = shared_pool; a.tn_in = nullptr; a.tK = nullptr;
     const size_t Dp = inst[0].Dp, N = inst[0].N;
     const size_t lds = (96 * (Dp + GP) + 2 * N * (Dp + GP) + 64 * (64 + GP) + 256 + 64) * 4;
-    return g_launch(graph_pre_fwd_kernel, dim3(B, 2), lds, (hipStream_t)stream, a, "graph_pre_fwd");
+    return g_launch(graph_pre_fwd_kernel<false>, dim3(B, 2), lds, (hipStream_t)stream, a, "graph_pre_fwd");
+}
+extern "C" int scl_graph_pre_fwd_var(const SclGraphPre* inst, int shared_pool, const int32_t* t_in, const int32_t* t_keep, int B, void* stream) {
+    SCL_REQUIRE(inst && t_in && t_keep && B > 0 && pre_ok(inst), "scl_graph_pre_fwd_var: two instances of equal shape, <= 96 nodes per unit, width 32 or 64, both count tables");
+    for (int i = 0; i < 2; ++i)
+        SCL_REQUIRE(inst[i].in_p == 0.f && inst[i].u[0].pool_p == 0.f && inst[i].u[1].pool_p == 0.f, "scl_graph_pre_fwd_var: a scoring-mode forward (no dropout), instance %d", i);
+    PreArgs a; a.I[0] = inst[0]; a.I[1] = inst[1]; a.shared_pool = shared_pool; a.tn_in = t_in; a.tK = t_keep;
+    const size_t Dp = inst[0].Dp, N = inst[0].N;
+    const size_t lds = (96 * (Dp + GP) + 2 * N * (Dp + GP) + 64 * (64 + GP) + 256 + 64) * 4;
+    return g_launch(graph_pre_fwd_kernel<true>, dim3(B, 2), lds, (hipStream_t)stream, a, "scl_graph_pre_fwd_var");
 }
 extern "C" int scl_graph_pre_bwd(const SclGraphPre* inst, int shared_pool, int B, void* stream) {
     SCL_REQUIRE(inst && B > 0 && pre_ok(inst), "graph_pre_bwd: two instances of equal shape, <= 96 nodes per unit, width 32 or 64");
-    PreArgs a; a.I[0] = inst[0]; a.I[1] = inst[1]; a.shared_pool = shared_pool;
+    PreArgs a; a.I[0] = inst[0]; a.I[1] = inst[1]; a.shared_pool = shared_pool; a.tn_in = nullptr; a.tK = nullptr;
     const size_t Dp = inst[0].Dp, N = inst[0].N;
     const size_t lds = (96 * (Dp + GP) + 3 * N * (Dp + GP) + 64 * (64 + GP) + 3 * 128 + 2 * (4 * 64 * 2 + 8) + 64) * 4;
     return g_launch(graph_pre_bwd_kernel, dim3(B, shared_pool ? 1 : 2), lds, (hipStream_t)stream, a, "graph_pre_bwd");
@@ -839,7 +888,18 @@ static size_t final_lds(const SclGraphFinal& f) {
 }
 extern "C" int scl_graph_final_fwd(const SclGraphFinal* f, int B, void* stream) {
     SCL_REQUIRE(f && B > 0 && f->D > 0 && 5 * f->D <= GT && f->NC > 0 && f->NC <= 8 && f->KT > 0 && f->KS > 0, "graph_final_fwd: 5 D <= 256, NC <= 8");
-    return g_launch(graph_final_fwd_kernel, dim3(B), final_lds(*f), (hipStream_t)stream, *f, "graph_final_fwd");
+    if (final_lds(*f) > 160 * 1024) { scl_set_error("graph_final_fwd: %zu bytes of LDS (graph too large: the fused graph module takes up to 80 nodes)", final_lds(*f)); return SCL_EINVAL; }
+    if (final_lds(*f) > 65536) (void)hipFuncSetAttribute((const void*)graph_final_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)final_lds(*f));
+    hipLaunchKernelGGL(graph_final_fwd_kernel<false>, dim3(B), dim3(GT), final_lds(*f), (hipStream_t)stream, *f, (const int*)nullptr);
+    return scl_check_launch("graph_final_fwd");
+}
+extern "C" int scl_graph_final_fwd_var(const SclGraphFinal* f, const int32_t* kt, int B, void* stream) {
+    SCL_REQUIRE(f && kt && B > 0 && f->D > 0 && 5 * f->D <= GT && f->NC > 0 && f->NC <= 8 && f->KT > 0 && f->KS > 0, "scl_graph_final_fwd_var: 5 D <= 256, NC <= 8, a row-count table");
+    SCL_REQUIRE(f->way_p == 0.f && f->drop_p == 0.f, "scl_graph_final_fwd_var: a scoring-mode forward (no dropout)");
+    SCL_REQUIRE(final_lds(*f) <= 160 * 1024, "scl_graph_final_fwd_var: %zu bytes of LDS", final_lds(*f));
+    if (final_lds(*f) > 65536) (void)hipFuncSetAttribute((const void*)graph_final_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)final_lds(*f));
+    hipLaunchKernelGGL(graph_final_fwd_kernel<true>, dim3(B), dim3(GT), final_lds(*f), (hipStream_t)stream, *f, kt);
+    return scl_check_launch("scl_graph_final_fwd_var");
 }
 extern "C" int scl_graph_final_bwd(const SclGraphFinal* f, int B, void* stream) {
     SCL_REQUIRE(f && B > 0 && 5 * f->D <= GT && f->NC > 0 && f->NC <= 8 && f->KT > 0 && f->KS > 0, "graph_final_bwd: 5 D <= 256, NC <= 8");

@@ -56,6 +56,28 @@ __device__ __forceinline__ bool rs_valid_rel(const RsGeom& q, unsigned rr0, unsi
     return r >= q.r_lo && r <= q.r_hi && c >= 1 && c <= q.W;
 }
 
+// Variable-width batches (scoring): utterance b owns the columns 1..wt[b] of its rows (wt: int32 [B] on the device, clamped to the
+// geometry's W); everything beyond is padding — selected to zero, never multiplied.
+__device__ __forceinline__ int rs_width(const RsGeom& q, const int* __restrict__ wt, unsigned b) { const int w = wt[b]; return w < q.W ? w : q.W; }
+__device__ __forceinline__ bool rs_valid_w(const RsGeom& q, const int* __restrict__ wt, unsigned g) {
+    if (g >= (unsigned)q.G) return false;
+    const unsigned row = g / (unsigned)q.Wp;
+    const int c = (int)(g - row * (unsigned)q.Wp);
+    const unsigned b = row / (unsigned)q.RPU;
+    const int r = (int)(row - b * (unsigned)q.RPU);
+    return r >= q.r_lo && r <= q.r_hi && c >= 1 && c <= rs_width(q, wt, b);
+}
+// rs_valid_rel for a position g0 + pos < G of a tile whose first row is row0 = b0 * RPU + rr0
+__device__ __forceinline__ bool rs_valid_rel_w(const RsGeom& q, const int* __restrict__ wt, unsigned b0, unsigned rr0, unsigned col0, unsigned pos) {
+    const unsigned x = col0 + pos;
+    const unsigned dq = (x * q.m_wp) >> 16;
+    const int c = (int)(x - dq * (unsigned)q.Wp);
+    const unsigned y = rr0 + dq;
+    const unsigned by = (y * q.m_rpu) >> 16;
+    const int r = (int)(y - by * (unsigned)q.RPU);
+    return r >= q.r_lo && r <= q.r_hi && c >= 1 && c <= rs_width(q, wt, b0 + by);
+}
+
 struct RsConvK {
     const float* in; const float* wpk; const float* bias; const float* addend; float* out;
     const float* act_a; const float* y1; const float* bnstats;     // stat_mode 2: out = conv * selu'(act_a); xhat = (y1 - mean) * rstd
@@ -69,9 +91,10 @@ struct RsConvK {
     int act_a_none;     // statistics mode 2 without the activation factor: out = conv (the gradient of a BatchNorm OUTPUT), xhat from y1
     float eps, momentum;
     double nvalid;
+    const int* wtab;    // VW instantiations: per-utterance widths (scl_rs_conv_w)
 };
 
-template <int CIN, int COUT, int NT, int SM>      // SM: statistics mode of the epilogue (0 none, 1 BatchNorm forward, 2 BatchNorm + SELU backward)
+template <int CIN, int COUT, int NT, int SM, bool VW = false>      // SM: statistics mode of the epilogue (0 none, 1 BatchNorm forward, 2 BatchNorm + SELU backward); VW: per-utterance widths
 __global__ __launch_bounds__(256, (CIN >= 64 ? 1 : 2)) void rs_conv_kernel(const RsConvK d) {
     constexpr int RS_MT = rs_mt(CIN);
     constexpr int NCB = COUT / 16;            // 16-channel output blocks: one per wave (64), two waves per block (32), four (16)
@@ -189,7 +212,7 @@ __global__ __launch_bounds__(256, (CIN >= 64 ? 1 : 2)) void rs_conv_kernel(const
                 const int pos = (tid + 256 * (p0 + u)) / N4;
                 const unsigned g = (unsigned)(g0 + pos);
                 if (g >= (unsigned)d.q.G) continue;
-                const bool ok = rs_valid_rel(d.q, rr0, col0, (unsigned)pos);
+                const bool ok = VW ? rs_valid_rel_w(d.q, d.wtab, row0 / (unsigned)d.q.RPU, rr0, col0, (unsigned)pos) : rs_valid_rel(d.q, rr0, col0, (unsigned)pos);
                 f32x4 v = *reinterpret_cast<const f32x4*>(lds + pos * OPITCH + 4 * ch4);
                 v += bias4;
                 v += ad[u];
@@ -276,6 +299,23 @@ __global__ __launch_bounds__(256) void rs_bn_act_kernel(const float* __restrict_
         *reinterpret_cast<f32x4*>(a + f * 4) = o;
     }
 }
+__global__ __launch_bounds__(256) void rs_bn_act_w_kernel(const float* __restrict__ y, const float* __restrict__ stats, float* __restrict__ a, int C, int act, RsGeom q,
+                                                          const int* __restrict__ wt) {
+    const int c4n = C >> 2;
+    const long long n4 = (long long)q.G * c4n;
+    for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < n4; f += (long long)gridDim.x * 256) {
+        const unsigned g = (unsigned)(f / c4n);
+        const int c = (int)(f - (long long)g * c4n) * 4;
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        if (rs_valid_w(q, wt, g)) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(y + f * 4), mean = *reinterpret_cast<const f32x4*>(stats + c),
+                        sc = *reinterpret_cast<const f32x4*>(stats + 2 * C + c), be = *reinterpret_cast<const f32x4*>(stats + 3 * C + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float z = (v[e] - mean[e]) * sc[e] + be[e]; o[e] = act ? selu_f(z) : z; }
+        }
+        *reinterpret_cast<f32x4*>(a + f * 4) = o;
+    }
+}
 // dy = sc * (dz - m1 - xhat * m2) on the valid positions (m1 = m2 = 0 in eval mode), 0 elsewhere; in place on dz
 __global__ __launch_bounds__(256) void rs_bn_bwd_apply_kernel(float* __restrict__ dz, const float* __restrict__ y, const float* __restrict__ stats,
                                                              const float* __restrict__ bstats, int C, int selu_in, RsGeom q) {
@@ -336,6 +376,24 @@ __global__ __launch_bounds__(256) void rs_copy_kernel(const float* __restrict__ 
             const int r = (int)(bh - b * H);
             dst[e] = src[(((b * q.RPU) + r + q.r_lo) * q.Wp + col + 1) * Cs + c];
         }
+    }
+}
+
+// dense [B * H * Ws, Cs] (Ws >= every width) -> bordered [G, Cd]: columns beyond the utterance's width are written as zeros and not read
+__global__ __launch_bounds__(256) void rs_copy_w_kernel(const float* __restrict__ src, float* __restrict__ dst, int Cs, int Cd, int H, int Ws, RsGeom q,
+                                                        const int* __restrict__ wt) {
+    const long long n = (long long)q.G * Cd;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const unsigned g = (unsigned)(e / Cd);
+        const int c = (int)(e - (long long)g * Cd);
+        float v = 0.f;
+        if (c < Cs && rs_valid_w(q, wt, g)) {
+            const unsigned row = g / (unsigned)q.Wp;
+            const unsigned b = row / (unsigned)q.RPU;
+            const int r = (int)(row - b * q.RPU), col = (int)(g - row * (unsigned)q.Wp);
+            if (col <= Ws) v = src[(((long long)b * H + (r - q.r_lo)) * Ws + (col - 1)) * Cs + c];
+        }
+        dst[e] = v;
     }
 }
 
@@ -547,6 +605,49 @@ __global__ __launch_bounds__(256) void rs_attn_pool_fwd_kernel(const float* __re
         }
     }
 }
+// The same for utterances of different widths: block b pools over its columns 1..wt[b] alone (the soft-max over the time axis and both sums);
+// the rows of eT at and beyond the width are written as zeros.  Columns beyond the width are not read.
+__global__ __launch_bounds__(256) void rs_attn_pool_fwd_w_kernel(const float* __restrict__ x, const float* __restrict__ l, const float* __restrict__ pos,
+                                                                 float* __restrict__ eS, float* __restrict__ eT, int C, int H, int W, RsGeom q,
+                                                                 const int* __restrict__ wt) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    f32x4* LX = reinterpret_cast<f32x4*>(lds);
+    f32x4* LL = LX + H * W;
+    const int b = blockIdx.x, c4 = blockIdx.y, tid = threadIdx.x;
+    int Wb = rs_width(q, wt, b);
+    Wb = Wb < 1 ? 1 : Wb;                    // uniform in the block
+    const size_t base = (size_t)b * q.RPU * q.Wp;
+    for (int e = tid; e < H * Wb; e += 256) {
+        const int h = e / Wb, w = e - h * Wb;
+        const size_t g = base + (size_t)(h + 1) * q.Wp + (w + 1);
+        LX[h * W + w] = *reinterpret_cast<const f32x4*>(x + g * C + 4 * c4);
+        LL[h * W + w] = *reinterpret_cast<const f32x4*>(l + g * C + 4 * c4);
+    }
+    __syncthreads();
+    for (int r = tid; r < H + W; r += 256) {
+        const bool row = r < H;
+        if (!row && r - H >= Wb) {
+            *reinterpret_cast<f32x4*>(eT + ((size_t)b * W + (r - H)) * C + 4 * c4) = f32x4{0.f, 0.f, 0.f, 0.f};
+            continue;
+        }
+        const int n = row ? Wb : H, i0 = row ? r * W : r - H, st = row ? 1 : W;
+        f32x4 mx = LL[i0];
+        for (int k = 1; k < n; ++k) { const f32x4 v = LL[i0 + k * st]; for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], v[e]); }
+        f32x4 den = {0.f, 0.f, 0.f, 0.f}, num = den;
+        for (int k = 0; k < n; ++k) {
+            const f32x4 v = LL[i0 + k * st], xv = LX[i0 + k * st];
+            for (int e = 0; e < 4; ++e) { const float p = __expf(v[e] - mx[e]); den[e] += p; num[e] = fmaf(p, xv[e], num[e]); }
+        }
+        f32x4 o;
+        for (int e = 0; e < 4; ++e) o[e] = num[e] / den[e];
+        if (row) {
+            if (pos) o += *reinterpret_cast<const f32x4*>(pos + (size_t)r * C + 4 * c4);
+            *reinterpret_cast<f32x4*>(eS + ((size_t)b * H + r) * C + 4 * c4) = o;
+        } else {
+            *reinterpret_cast<f32x4*>(eT + ((size_t)b * W + (r - H)) * C + 4 * c4) = o;
+        }
+    }
+}
 // backward: dx = deS[h] P1 + deT[w] P2;  dl = P1 (deS[h] x - <deS[h] x, P1>_w) + P2 (deT[w] x - <deT[w] x, P2>_h)     (bordered outputs, zero borders kept)
 // Four [H][W] slices per channel in LDS: a block takes TWO channels (42 x 66 x 2 x 4 arrays = 88 KiB).
 typedef __attribute__((ext_vector_type(2))) float rs_f32x2;
@@ -604,11 +705,11 @@ __global__ __launch_bounds__(256) void rs_attn_pool_bwd_kernel(const float* __re
     }
 }
 
-template <int CIN, int COUT, int NT, int SM>
+template <int CIN, int COUT, int NT, int SM, bool VW = false>
 int rs_conv_launch_sm(const RsConvK& k, int grid, size_t lds, hipStream_t s) {
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)rs_conv_kernel<CIN, COUT, NT, SM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SCL_LAUNCH((rs_conv_kernel<CIN, COUT, NT, SM>), dim3(grid), dim3(256), lds, s, k);
-    return scl_check_launch("rs_conv");
+    if (lds > 65536) (void)hipFuncSetAttribute((const void*)rs_conv_kernel<CIN, COUT, NT, SM, VW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    SCL_LAUNCH((rs_conv_kernel<CIN, COUT, NT, SM, VW>), dim3(grid), dim3(256), lds, s, k);
+    return scl_check_launch(VW ? "scl_rs_conv_w" : "rs_conv");
 }
 // which statistics modes an instantiation serves: 1 (BatchNorm forward) the forward shapes, 2 (BatchNorm backward) conv2's data gradient
 template <int CIN, int COUT, int NT>
@@ -622,6 +723,11 @@ int rs_conv_launch_t(const RsConvK& k, int grid, hipStream_t s) {
     if (lds_st > lds) lds = lds_st;
     if (lds > 160 * 1024) { scl_set_error("rs_conv: tile + halo of %zu bytes exceeds the LDS", lds); return SCL_EINVAL; }
     constexpr bool FWD = (NT == 6 && COUT >= CIN) || NT == 1, C2T = (NT == 6 || NT == 1) && CIN == COUT;
+    if (k.wtab) {      // variable widths: the forward shapes, no statistics (scoring)
+        if constexpr (COUT >= CIN) { if (k.stat_mode == 0) return rs_conv_launch_sm<CIN, COUT, NT, 0, true>(k, grid, lds, s); }
+        scl_set_error("scl_rs_conv_w: %d -> %d channels, %d taps with statistics mode %d is not instantiated (forward shapes, stat_mode 0)", CIN, COUT, NT, k.stat_mode);
+        return SCL_EINVAL;
+    }
     if (k.stat_mode == 0) return rs_conv_launch_sm<CIN, COUT, NT, 0>(k, grid, lds, s);
     if constexpr (FWD) { if (k.stat_mode == 1) return rs_conv_launch_sm<CIN, COUT, NT, 1>(k, grid, lds, s); }
     if constexpr (C2T) { if (k.stat_mode == 2) return rs_conv_launch_sm<CIN, COUT, NT, 2>(k, grid, lds, s); }
@@ -650,6 +756,12 @@ bool rs_fill_geom(const SclRsGeom& g, RsGeom* q) {
     q->m_wp = (65536u + q->Wp - 1) / q->Wp; q->m_rpu = (65536u + q->RPU - 1) / q->RPU;
     return true;
 }
+// the same conditions without an error text of their own: the variable-width entry points name themselves in their refusals
+bool rs_geom_ok(const SclRsGeom* g) {
+    return g && g->B > 0 && g->H > 0 && g->W > 0 && g->r_lo >= 0 && g->r_hi <= g->H + 1 && g->r_lo <= g->r_hi &&
+           (long long)g->B * (g->H + 2) * (g->W + 2) < (1LL << 31) / 64;
+}
+bool rs_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 bool rs_shifts(const int* shift, int ntaps, int* dst, int* smin, int* span) {
     if (ntaps != 1 && ntaps != 3 && ntaps != 6) { scl_set_error("rs: ntaps must be 1, 3 or 6"); return false; }
     int lo = shift[0], hi = shift[0];
@@ -677,9 +789,28 @@ extern "C" int scl_rs_pack_weights(const SclRsPackJob* jobs, int njobs, void* st
     return scl_check_launch("rs_pack_weights");
 }
 
+static int rs_conv_run(const SclRsConv* c, const int* widths, void* stream);
 extern "C" int scl_rs_conv(const SclRsConv* c, void* stream) {
     SCL_REQUIRE(c && c->in && c->wpk && c->out, "rs_conv: null pointers");
+    return rs_conv_run(c, nullptr, stream);
+}
+extern "C" int scl_rs_conv_w(const SclRsConv* c, const int32_t* widths, void* stream) {
+    SCL_REQUIRE(c && c->in && c->wpk && c->out && widths, "scl_rs_conv_w: null pointers");
+    SCL_REQUIRE(c->stat_mode == 0, "scl_rs_conv_w: a scoring-mode forward (stat_mode 0), got stat_mode %d", c->stat_mode);
+    SCL_REQUIRE(rs_geom_ok(&c->geom), "scl_rs_conv_w: bad geometry (B, H, W > 0, rows within 0..H + 1, fewer than 2^25 positions)");
+    SCL_REQUIRE(c->ntaps == 1 || c->ntaps == 3 || c->ntaps == 6, "scl_rs_conv_w: ntaps must be 1, 3 or 6, got %d", c->ntaps);
+    SCL_REQUIRE(c->geom.W <= RS_MAX_SPAN - 3, "scl_rs_conv_w: maps up to %d positions wide, got %d", RS_MAX_SPAN - 3, c->geom.W);
+    {
+        const int key = c->cin * 10000 + c->cout * 10 + c->ntaps;
+        SCL_REQUIRE(key == 160326 || key == 320326 || key == 320646 || key == 640646 || key == 160323 || key == 320643 || key == 640641,
+                    "scl_rs_conv_w: no instantiation for %d -> %d channels, %d taps (the forward shapes)", c->cin, c->cout, c->ntaps);
+    }
+    SCL_REQUIRE(rs_al16(c->in) && rs_al16(c->wpk) && rs_al16(c->out) && rs_al16(c->bias) && rs_al16(c->addend), "scl_rs_conv_w: maps, weights and bias 16-byte aligned");
+    return rs_conv_run(c, widths, stream);
+}
+static int rs_conv_run(const SclRsConv* c, const int* widths, void* stream) {
     RsConvK k;
+    k.wtab = widths;
     if (!rs_fill_geom(c->geom, &k.q)) return SCL_EINVAL;
     if (!rs_shifts(c->shift, c->ntaps, k.shift, &k.smin, &k.span)) return SCL_EINVAL;
     SCL_REQUIRE(c->stat_mode >= 0 && c->stat_mode <= 2, "rs_conv: stat_mode %d", c->stat_mode);
@@ -757,6 +888,17 @@ extern "C" int scl_rs_bn_act(const float* y, const float* stats, float* a, int C
     return scl_check_launch("rs_bn_act");
 }
 
+extern "C" int scl_rs_bn_act_w(const float* y, const float* stats, float* a, int C, int act, const SclRsGeom* geom, const int32_t* widths, void* stream) {
+    SCL_REQUIRE(y && stats && a && geom && widths && C > 0 && C % 4 == 0 && (act == 0 || act == 1), "scl_rs_bn_act_w: bad arguments");
+    SCL_REQUIRE(rs_geom_ok(geom), "scl_rs_bn_act_w: bad geometry (B, H, W > 0, rows within 0..H + 1, fewer than 2^25 positions)");
+    SCL_REQUIRE(rs_al16(y) && rs_al16(stats) && rs_al16(a), "scl_rs_bn_act_w: maps and statistics 16-byte aligned");
+    RsGeom q;
+    if (!rs_fill_geom(*geom, &q)) return SCL_EINVAL;
+    const long long n4 = (long long)q.G * (C / 4);
+    hipLaunchKernelGGL(rs_bn_act_w_kernel, dim3((unsigned)((n4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, y, stats, a, C, act, q, widths);
+    return scl_check_launch("scl_rs_bn_act_w");
+}
+
 extern "C" int scl_rs_bn_bwd_apply(float* dz, const float* y, const float* stats, const float* bstats, int C, int selu_in, const SclRsGeom* geom, void* stream) {
     SCL_REQUIRE(dz && y && stats && bstats && geom && C % 4 == 0, "rs_bn_bwd_apply: bad arguments");
     RsGeom q;
@@ -794,6 +936,32 @@ extern "C" int scl_rs_attn_pool_fwd(const float* x, const float* l, const float*
     hipLaunchKernelGGL(rs_attn_pool_fwd_kernel, dim3(geom->B, C / 4), dim3(256), lds, (hipStream_t)stream, x, l, pos, eS, eT, C, geom->H, geom->W, q);
     return scl_check_launch("rs_attn_pool_fwd");
 }
+extern "C" int scl_rs_copy_w(const float* src, float* dst, int Cs, int Cd, int src_w, const SclRsGeom* geom, const int32_t* widths, void* stream) {
+    SCL_REQUIRE(src && dst && geom && widths && Cs > 0 && Cd >= Cs, "scl_rs_copy_w: bad arguments");
+    SCL_REQUIRE(rs_geom_ok(geom), "scl_rs_copy_w: bad geometry (B, H, W > 0, rows within 0..H + 1, fewer than 2^25 positions)");
+    SCL_REQUIRE(src_w > 0 && src_w <= geom->W, "scl_rs_copy_w: source rows of %d columns for a map %d wide", src_w, geom->W);
+    RsGeom q;
+    if (!rs_fill_geom(*geom, &q)) return SCL_EINVAL;
+    const int H = geom->r_hi - geom->r_lo + 1;
+    const long long n = (long long)q.G * Cd;
+    hipLaunchKernelGGL(rs_copy_w_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, src, dst, Cs, Cd, H, src_w, q, widths);
+    return scl_check_launch("scl_rs_copy_w");
+}
+
+extern "C" int scl_rs_attn_pool_fwd_w(const float* x, const float* l, const float* pos, float* eS, float* eT, int C, const SclRsGeom* geom, const int32_t* widths,
+                                      void* stream) {
+    SCL_REQUIRE(x && l && eS && eT && geom && widths && C > 0 && C % 4 == 0, "scl_rs_attn_pool_fwd_w: bad arguments");
+    SCL_REQUIRE(rs_geom_ok(geom), "scl_rs_attn_pool_fwd_w: bad geometry (B, H, W > 0, rows within 0..H + 1, fewer than 2^25 positions)");
+    SCL_REQUIRE(rs_al16(x) && rs_al16(l) && rs_al16(eS) && rs_al16(eT) && rs_al16(pos), "scl_rs_attn_pool_fwd_w: maps and outputs 16-byte aligned");
+    RsGeom q;
+    if (!rs_fill_geom(*geom, &q)) return SCL_EINVAL;
+    const size_t lds = (size_t)2 * geom->H * geom->W * 16;
+    SCL_REQUIRE(lds <= 160 * 1024, "scl_rs_attn_pool_fwd_w: map of %d x %d positions exceeds the LDS", geom->H, geom->W);
+    if (lds > 65536) (void)hipFuncSetAttribute((const void*)rs_attn_pool_fwd_w_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(rs_attn_pool_fwd_w_kernel, dim3(geom->B, C / 4), dim3(256), lds, (hipStream_t)stream, x, l, pos, eS, eT, C, geom->H, geom->W, q, widths);
+    return scl_check_launch("scl_rs_attn_pool_fwd_w");
+}
+
 extern "C" int scl_rs_attn_pool_bwd(const float* x, const float* l, const float* deS, const float* deT, float* dx, float* dl, int C, const SclRsGeom* geom, void* stream) {
     SCL_REQUIRE(x && l && deS && deT && dx && dl && geom && C % 4 == 0, "rs_attn_pool_bwd: bad arguments");
     RsGeom q;

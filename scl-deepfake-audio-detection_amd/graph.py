@@ -30,6 +30,10 @@ def seed(value):
     _SEED[0] = int(value) & 0x7FFFFFFF
 
 
+MAX_NODES = 80           # nodes of a homogeneous layer (spectral or temporal) the one-workgroup-per-utterance kernels keep in LDS
+MAX_HTRG_NODES = 64      # nodes of a heterogeneous layer (pooled temporal + pooled spectral): the master-node vectors' room
+
+
 def supported(head, nS, nT):
     try:
         gS, gT = head.GAT_layer_S, head.GAT_layer_T
@@ -37,7 +41,7 @@ def supported(head, nS, nT):
         g0 = gS.att_proj.weight.shape[0]
         g1 = head.HtrgGAT_layer_ST11.att_proj.weight.shape[0]
         kS, kT = max(int(nS * head.pool_S.k), 1), max(int(nT * head.pool_T.k), 1)
-        return d0 == 64 and g0 == 64 and g1 in (32, 64) and nT <= 80 and nS <= 80 and kS + kT <= 64 and head.out_layer.weight.shape[0] <= 8 and 5 * g1 <= 256
+        return d0 == 64 and g0 == 64 and g1 in (32, 64) and nT <= MAX_NODES and nS <= MAX_NODES and kS + kT <= MAX_HTRG_NODES and head.out_layer.weight.shape[0] <= 8 and 5 * g1 <= 256
     except AttributeError:
         return False
 
@@ -53,8 +57,12 @@ def _S():
 
 
 class _Plan:
-    def __init__(self, head, B, nS, nT, dev):
-        self.key = (B, nS, nT)
+    def __init__(self, head, B, nS, nT, dev, counts=False):
+        """counts: the plan of a scoring batch of graphs of different sizes — nT is the padded batch's temporal node count, `cnt` holds the
+        per-utterance counts (int32 [5, B] on the device, fixed address: nT | kT | kT2 | kT + kS | kT2 + kS2, overwritten before every
+        replay); forward buffers only."""
+        self.key = (B, nS, nT) + (("counts",) if counts else ())
+        self.cnt = torch.ones(5, B, dtype=torch.int32, device=dev) if counts else None
         self.dev, self.busy = dev, False
         g0 = head.GAT_layer_S.att_proj.weight.shape[0]
         g1 = head.HtrgGAT_layer_ST11.att_proj.weight.shape[0]
@@ -63,24 +71,25 @@ class _Plan:
         self.kS2, self.kT2 = max(int(self.kS * head.pool_hS1.k), 1), max(int(self.kT * head.pool_hT1.k), 1)
         self.N1, self.N2 = self.kT + self.kS, self.kT2 + self.kS2
         f = lambda *s: torch.zeros(*s, device=dev)
+        fb = (lambda *s: None) if counts else f      # the backward's buffers
         self.layers = {}
         for name, N, D, Do, master in (("S", nS, 64, g0, False), ("T", nT, 64, g0, False), ("11", self.N1, g0, g1, True), ("21", self.N1, g0, g1, True),
                                        ("12", self.N2, g1, g1, True), ("22", self.N2, g1, g1, True)):
             nb = ops.gat_score_nblocks(N)
-            d = dict(N=N, D=D, Do=Do, master=master, xd=f(B, N, D), S=f(B, N, N), g=f(B, N, D), y=f(B, N, Do), dz=f(B, N, Do), dS=f(B, N, N),
-                     dxd_a=f(B, N, D), dxd_b=f(B, N, D), stats=f(4 * Do), bstats=f(2 * Do), acc=torch.zeros(16 * 2 * 64, dtype=torch.float64, device=dev),
-                     ticket=torch.zeros(1, dtype=torch.int32, device=dev), dP=torch.empty(B * N * N * D, device=dev),
-                     part=torch.empty(nb * B, Do * D + 4 * Do, device=dev), nb=nb, a3=f(3, Do))
+            d = dict(N=N, D=D, Do=Do, master=master, xd=f(B, N, D), S=f(B, N, N), g=f(B, N, D), y=f(B, N, Do), dz=fb(B, N, Do), dS=fb(B, N, N),
+                     dxd_a=fb(B, N, D), dxd_b=fb(B, N, D), stats=f(4 * Do), bstats=f(2 * Do), acc=torch.zeros(16 * 2 * 64, dtype=torch.float64, device=dev),
+                     ticket=torch.zeros(1, dtype=torch.int32, device=dev), dP=None if counts else torch.empty(B * N * N * D, device=dev),
+                     part=None if counts else torch.empty(nb * B, Do * D + 4 * Do, device=dev), nb=nb, a3=f(3, Do))
             if master:
-                d.update(am=f(B, N), gm=f(B, D), tM=f(B, N, Do), mout=f(B, Do), d_min=f(B, D))
+                d.update(am=f(B, N), gm=f(B, D), tM=f(B, N, Do), mout=f(B, Do), d_min=fb(B, D))
             self.layers[name] = d
         # pool units: (source layer, first row, rows in, rows kept)
         def unit(n_in, K, Dp):
             return dict(h=f(B, n_in, Dp), sc=f(B, n_in), idx=torch.zeros(B, K, dtype=torch.int32, device=dev), pooled=f(B, K, Dp))
         self.units = {"T": unit(nT, self.kT, g0), "S": unit(nS, self.kS, g0),
                       "T1": unit(self.kT, self.kT2, g1), "S1": unit(self.kS, self.kS2, g1), "T2": unit(self.kT, self.kT2, g1), "S2": unit(self.kS, self.kS2, g1)}
-        self.fin = [dict(dTp=f(B, self.kT2, g1), dSp=f(B, self.kS2, g1), dm1=f(B, g1), dm2=f(B, g1)) for _ in range(2)]
-        self.de = (f(B, nS, 64), f(B, nT, 64))
+        self.fin = [dict(dTp=fb(B, self.kT2, g1), dSp=fb(B, self.kS2, g1), dm1=fb(B, g1), dm2=fb(B, g1)) for _ in range(2)]
+        self.de = None if counts else (f(B, nS, 64), f(B, nT, 64))
         self.slab = None
         self.sig, self.fwd_calls, self.bwd_calls = None, None, None
 
@@ -99,7 +108,7 @@ def _bn(pl, lay, bnmod, nvalid, training):
     b.gamma, b.beta, b.run_mean, b.run_var, b.nbt = (bnmod.weight.data_ptr(), bnmod.bias.data_ptr(), bnmod.running_mean.data_ptr(),
                                                      bnmod.running_var.data_ptr(), bnmod.num_batches_tracked.data_ptr())
     b.stats, b.bstats = lay["stats"].data_ptr(), lay["bstats"].data_ptr()
-    b.dgamma, b.dbeta = _grad(bnmod.weight).data_ptr(), _grad(bnmod.bias).data_ptr()
+    b.dgamma, b.dbeta = (None, None) if pl.cnt is not None else (_grad(bnmod.weight).data_ptr(), _grad(bnmod.bias).data_ptr())
     b.nvalid, b.eps, b.momentum, b.training = float(nvalid), float(bnmod.eps), 0.1 if bnmod.momentum is None else float(bnmod.momentum), 1 if training else 0
     return b
 
@@ -126,7 +135,7 @@ def _layer_struct(pl, name, mod, B, training, slab, master_in=None, master_bs=0,
                               mod.proj_without_att.bias.data_ptr())
     s.N, s.D, s.Do, s.has_master, s.inv_temp = lay["N"], lay["D"], lay["Do"], 1 if lay["master"] else 0, 1.0 / float(mod.temp)
     s.bn = _bn(pl, lay, mod.bn, B * lay["N"], training)
-    s.dz, s.dS, s.dxd = lay["dz"].data_ptr(), lay["dS"].data_ptr(), lay["dxd_a"].data_ptr()
+    s.dz, s.dS, s.dxd = _ptr(lay["dz"]), _ptr(lay["dS"]), _ptr(lay["dxd_a"])
     s.slab, s.slab_bs = pl.slab.data_ptr(), pl.slab.shape[1]
     s.o_Wa, s.o_ba, s.o_Wb, s.o_bb = (slab.add(mod.proj_with_att.weight), slab.add(mod.proj_with_att.bias), slab.add(mod.proj_without_att.weight),
                                       slab.add(mod.proj_without_att.bias))
@@ -135,7 +144,7 @@ def _layer_struct(pl, name, mod, B, training, slab, master_in=None, master_bs=0,
         s.WM, s.bM, s.aM = mod.att_projM.weight.data_ptr(), mod.att_projM.bias.data_ptr(), mod.att_weightM.data_ptr()
         s.WaM, s.baM, s.WbM, s.bbM = (mod.proj_with_attM.weight.data_ptr(), mod.proj_with_attM.bias.data_ptr(), mod.proj_without_attM.weight.data_ptr(),
                                       mod.proj_without_attM.bias.data_ptr())
-        s.am, s.gm, s.tM, s.mout, s.d_min = lay["am"].data_ptr(), lay["gm"].data_ptr(), lay["tM"].data_ptr(), lay["mout"].data_ptr(), lay["d_min"].data_ptr()
+        s.am, s.gm, s.tM, s.mout, s.d_min = lay["am"].data_ptr(), lay["gm"].data_ptr(), lay["tM"].data_ptr(), lay["mout"].data_ptr(), _ptr(lay["d_min"])
         s.d_mout, s.d_mout2 = _ptr(d_mout), _ptr(d_mout2)
         s.o_WM, s.o_bM, s.o_aM = slab.add(mod.att_projM.weight), slab.add(mod.att_projM.bias), slab.add(mod.att_weightM)
         s.o_WaM, s.o_baM, s.o_WbM, s.o_bbM = (slab.add(mod.proj_with_attM.weight), slab.add(mod.proj_with_attM.bias), slab.add(mod.proj_without_attM.weight),
@@ -164,7 +173,16 @@ def _score_fwd(pl, name, mod, B):
     n1 = lay["N"] if not lay["master"] else (pl.kT if name in ("11", "21") else pl.kT2)
     a3 = _a3(lay, mod)
     lay["a3_used"], lay["n1"] = a3, n1
-    ops.gat_score_fwd(lay["xd"], mod.att_proj.weight, mod.att_proj.bias, a3, lay["S"], B, lay["N"], lay["D"], lay["Do"], n1)
+    row = None if pl.cnt is None else _CNT_ROWS[name]
+    if row is None:
+        ops.gat_score_fwd(lay["xd"], mod.att_proj.weight, mod.att_proj.bias, a3, lay["S"], B, lay["N"], lay["D"], lay["Do"], n1)
+    else:      # the utterance's own node count and, in a heterogeneous layer, its own count of temporal nodes
+        ops.gat_score_fwd_var(lay["xd"], mod.att_proj.weight, mod.att_proj.bias, a3, lay["S"], pl.cnt[row[0]], None if row[1] is None else pl.cnt[row[1]],
+                              B, lay["N"], lay["D"], lay["Do"])
+
+
+# rows of _Plan.cnt per layer: (node count, count of first-type nodes); the spectral layer has one size
+_CNT_ROWS = {"S": None, "T": (0, None), "11": (3, 1), "21": (3, 1), "12": (4, 2), "22": (4, 2)}
 
 
 def _score_bwd(pl, name, mod, B):
@@ -185,7 +203,7 @@ def _unit(pl, uname, src_lay, src_bn, row0, pool, Wt_mod, row_out, slab, seeds, 
     u.h, u.sc, u.idx, u.pooled = un["h"].data_ptr(), un["sc"].data_ptr(), un["idx"].data_ptr(), un["pooled"].data_ptr()
     u.Wt, u.bt = Wt_mod.weight.data_ptr(), Wt_mod.bias.data_ptr()
     u.row_out = row_out
-    u.d_res, u.dz = _ptr(d_res), src_lay["dz"].data_ptr()
+    u.d_res, u.dz = _ptr(d_res), _ptr(src_lay["dz"])
     u.o_pw, u.o_pb, u.o_Wt, u.o_bt = slab.add(pool.proj.weight), slab.add(pool.proj.bias), slab.add(Wt_mod.weight), slab.add(Wt_mod.bias)
     u.bn = src_bn
     return u
@@ -227,7 +245,7 @@ def _structs(pl, head, B, training, seeds):
                     I.same_bn, I.store_common = 1, 1
                 I.u[0], I.u[1] = uT, uS
                 lay = pl.layers[nm]
-                I.xd, I.dxd_a, I.dxd_b = lay["xd"].data_ptr(), lay["dxd_a"].data_ptr(), lay["dxd_b"].data_ptr()
+                I.xd, I.dxd_a, I.dxd_b = lay["xd"].data_ptr(), _ptr(lay["dxd_a"]), _ptr(lay["dxd_b"])
                 I.in_seed, I.in_p = seeds["in_" + nm], p_in(mod)
                 I.Dp, I.N = lay["D"], lay["N"]
                 I.slab, I.slab_bs = pl.slab.data_ptr(), pl.slab.shape[1]
@@ -242,7 +260,7 @@ def _structs(pl, head, B, training, seeds):
             for k, site in enumerate(("T", "S", "M")):
                 br.way_seed[k] = seeds["way_%s%d" % (site, i)]
             f = pl.fin[i]
-            br.dz2, br.dTp, br.dSp, br.dm1, br.dm2 = l2["dz"].data_ptr(), f["dTp"].data_ptr(), f["dSp"].data_ptr(), f["dm1"].data_ptr(), f["dm2"].data_ptr()
+            br.dz2, br.dTp, br.dSp, br.dm1, br.dm2 = _ptr(l2["dz"]), _ptr(f["dTp"]), _ptr(f["dSp"]), _ptr(f["dm1"]), _ptr(f["dm2"])
             br.bn = Ls[n2].bn
         fin.Wout, fin.bout = H.out_layer.weight.data_ptr(), H.out_layer.bias.data_ptr()
         fin.slab, fin.slab_bs = pl.slab.data_ptr(), pl.slab.shape[1]
@@ -264,9 +282,21 @@ def _eval_stats(pl, mods):
                   lay["Do"], lay["stats"].data_ptr(), _S())
 
 
-def _post(st, names, B, fwd):
+def _post(st, names, B, fwd, pl=None):
     arr = (L.SclGraphLayer * 2)(st["L"][names[0]], st["L"][names[1]])
+    if pl is not None and pl.cnt is not None:
+        tabs = [None if _CNT_ROWS[n] is None else pl.cnt[_CNT_ROWS[n][0]].data_ptr() for n in names]
+        ops._call("scl_graph_post_fwd_var", arr, 2, tabs[0], tabs[1], B, _S(), keep=arr)
+        return
     ops._call("scl_graph_post_fwd" if fwd else "scl_graph_post_bwd", arr, 2, B, _S(), keep=arr)
+
+
+def _pre_fwd(pl, st, tag, shared, B):
+    if pl.cnt is not None:      # temporal unit: rows in / rows kept per utterance
+        r_in, r_keep = (0, 1) if tag == "1" else (1, 2)
+        ops._call("scl_graph_pre_fwd_var", st["pre"][tag], shared, pl.cnt[r_in].data_ptr(), pl.cnt[r_keep].data_ptr(), B, _S(), keep=st["pre"][tag])
+    else:
+        ops._call("scl_graph_pre_fwd", st["pre"][tag], shared, B, _S(), keep=st["pre"][tag])
 
 
 _SEED_NAMES = ["in_S", "in_T", "in_11", "in_21", "in_12", "in_22", "pool_T", "pool_S", "pool_T1", "pool_S1", "pool_T2", "pool_S2", "drop"] + \
@@ -337,18 +367,21 @@ def _forward(pl, head, e_S, e_T, training):
     pl.p_in0 = p_in
     _score_fwd(pl, "S", mods["S"], B)
     _score_fwd(pl, "T", mods["T"], B)
-    _post(st, ("S", "T"), B, True)
-    ops._call("scl_graph_pre_fwd", st["pre"]["1"], 1, B, _S(), keep=st["pre"]["1"])
+    _post(st, ("S", "T"), B, True, pl)
+    _pre_fwd(pl, st, "1", 1, B)
     _score_fwd(pl, "11", mods["11"], B)
     _score_fwd(pl, "21", mods["21"], B)
-    _post(st, ("11", "21"), B, True)
-    ops._call("scl_graph_pre_fwd", st["pre"]["2"], 0, B, _S(), keep=st["pre"]["2"])
+    _post(st, ("11", "21"), B, True, pl)
+    _pre_fwd(pl, st, "2", 0, B)
     _score_fwd(pl, "12", mods["12"], B)
     _score_fwd(pl, "22", mods["22"], B)
-    _post(st, ("12", "22"), B, True)
+    _post(st, ("12", "22"), B, True, pl)
     fin = st["fin"]
     fin.logits, fin.hidden = fin_out[0].data_ptr(), fin_out[1].data_ptr()
-    ops._call("scl_graph_final_fwd", ctypes.byref(fin), B, _S(), keep=fin)
+    if pl.cnt is not None:
+        ops._call("scl_graph_final_fwd_var", ctypes.byref(fin), pl.cnt[2].data_ptr(), B, _S(), keep=fin)
+    else:
+        ops._call("scl_graph_final_fwd", ctypes.byref(fin), B, _S(), keep=fin)
     pl.live = _storages(e_S, e_T, fin_out)
     if record:
         pl.fwd_calls = ops.stop_recording()
@@ -443,6 +476,24 @@ class _GraphFn(torch.autograd.Function):
 
 _NAMES = ("GAT_layer_S", "GAT_layer_T", "HtrgGAT_layer_ST11", "HtrgGAT_layer_ST12", "HtrgGAT_layer_ST21", "HtrgGAT_layer_ST22", "pool_S", "pool_T",
           "pool_hS1", "pool_hT1", "pool_hS2", "pool_hT2", "out_layer")
+
+
+_POOL_C = PlanPool()      # plans of scoring batches of graphs of different sizes: forward buffers only, at most PlanPool.MAX_POOL alive
+
+
+def graph_module_counts(e_S, e_T, head, counts):
+    """Scoring (eval mode under torch.no_grad()): graph_module for utterances with different temporal node counts in one padded batch.
+    e_T [B, nT, 64]: utterance b's nodes are its first counts["W"][b] rows (the rest is not read); counts: aasist_head.node_counts of the
+    batch.  Every utterance gets what graph_module gives it alone."""
+    if head.GAT_layer_S.training or torch.is_grad_enabled():
+        raise NotImplementedError("graph_module_counts is a scoring mode: eval mode under torch.no_grad()")
+    B, nS, nT, dev = e_S.shape[0], e_S.shape[1], e_T.shape[1], e_S.device
+    if len(counts["W"]) != B or max(counts["W"]) > nT or min(counts["W"]) < 1 or not supported(head, nS, nT):
+        raise ValueError("graph_module_counts: need one temporal node count in 1..%d per utterance of a graph the fused module takes, got %r" % (nT, counts["W"]))
+    pl = _POOL_C.acquire((B, nS, nT, "counts"), dev, False, lambda: _Plan(head, B, nS, nT, dev, counts=True))
+    table = torch.tensor([counts["W"], counts["kT"], counts["kT2"], counts["N1"], counts["N2"]], dtype=torch.int32)
+    pl.cnt.copy_(table.pin_memory(), non_blocking=True)
+    return _forward(pl, head, e_S.contiguous().float(), e_T.contiguous().float(), False)
 
 
 def graph_module(e_S, e_T, head):

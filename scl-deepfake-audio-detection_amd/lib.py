@@ -216,6 +216,7 @@ def _protos():
         "scl_gat_score_nblocks": ([_i32], _i32),
         "scl_gat_score_fwd": ([_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
         "scl_gat_score_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
+        "scl_gat_score_fwd_var": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
         "scl_dropout_rows": ([_vp, _vp, _i64, _i32, _i32, _i32, _u32, _f32, _vp], _i32),
         # resstack.hip
         "scl_rs_conv": ([P(SclRsConv), _vp], _i32),
@@ -229,6 +230,10 @@ def _protos():
         "scl_rs_attn_pool_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, P(SclRsGeom), _vp], _i32),
         "scl_rs_bn_eval_stats": ([_vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp], _i32),
         "scl_rs_copy": ([_vp, _vp, _i32, _i32, _i32, P(SclRsGeom), _vp], _i32),
+        "scl_rs_conv_w": ([P(SclRsConv), _vp, _vp], _i32),
+        "scl_rs_bn_act_w": ([_vp, _vp, _vp, _i32, _i32, P(SclRsGeom), _vp, _vp], _i32),
+        "scl_rs_copy_w": ([_vp, _vp, _i32, _i32, _i32, P(SclRsGeom), _vp, _vp], _i32),
+        "scl_rs_attn_pool_fwd_w": ([_vp, _vp, _vp, _vp, _vp, _i32, P(SclRsGeom), _vp, _vp], _i32),
         # graph.hip
         "scl_graph_post_fwd": ([_vp, _i32, _i32, _vp], _i32),
         "scl_graph_post_bwd": ([_vp, _i32, _i32, _vp], _i32),
@@ -239,6 +244,9 @@ def _protos():
         "scl_graph_final_fwd": ([_vp, _i32, _vp], _i32),
         "scl_graph_final_bwd": ([_vp, _i32, _vp], _i32),
         "scl_graph_reduce": ([_vp, _i32, _vp], _i32),
+        "scl_graph_post_fwd_var": ([_vp, _i32, _vp, _vp, _i32, _vp], _i32),
+        "scl_graph_pre_fwd_var": ([_vp, _i32, _vp, _vp, _i32, _vp], _i32),
+        "scl_graph_final_fwd_var": ([_vp, _vp, _i32, _vp], _i32),
         # loss.hip
         "scl_supcon_nchunks": ([_i64], _i32),
         "scl_supcon_ws_floats": ([_i32, _i64], _i64),

@@ -2,6 +2,9 @@
 
     Model(args: dict with an `aasist` section, device, is_train=True)
     forward(x [bz, L]) -> (logits [bz, 2], feats [bz, T, 128], last_hidden [bz, 160])   (logits only when not is_train)
+    forward(x, lengths=[n_0, ...])   SCL_AASIST_LENGTHS=1 (read at call time; without it the call is refused as before): scoring mode (eval, no
+                                     grad): row b holds n_b samples (min_samples() .. max_samples()) followed by padding and gets the result it
+                                     gets alone at its own length; feats rows beyond an utterance's frames are 0
     loss(output, feats, emb, labels, config, info=None) -> dict of 0-d tensors
 
 Encoder + LL + losses: HIP kernels; graph back-end: `aasist_head.AasistHead` on flat-buffer parameter views, replayed as
@@ -10,6 +13,9 @@ hipGraphs in training (scl_amd/model_front.py).
 The reference's train-mode forward returns a 2-tuple while main.py:63 unpacks three values: this plugin
 returns the triple main.py and Model.loss need — feats is the LL output, exactly what the linear plugin hands to SupCon.
 """
+import os
+
+from . import aasist_head
 from .aasist_head import UPSTREAM_AASIST, AasistHead
 from .model_front import FrontHeadModel
 from .model_linear import dropout_stream_seed, loss_custom
@@ -24,9 +30,32 @@ class Model(FrontHeadModel):
         graph.seed(dropout_stream_seed(seed, rank) ^ 0x3C6EF372)
 
     def _build_head(self, args):
-        return AasistHead(args.get("aasist") or UPSTREAM_AASIST)
+        head = AasistHead(args.get("aasist") or UPSTREAM_AASIST)
+        self.__dict__["pool_cfg"] = head.pool_cfg
+        return head
 
-    _head_forward = staticmethod(AasistHead.forward)
+    @staticmethod
+    def _head_forward(mod, feats, frames=None):
+        return AasistHead.forward(mod, feats) if frames is None else AasistHead.forward_frames(mod, feats, frames)
+
+    LENGTHS_SWITCH = "SCL_AASIST_LENGTHS"
+
+    @property
+    def head_takes_frames(self):
+        """forward(x, lengths) is opt-in for this plugin: SCL_AASIST_LENGTHS=1, read at call time."""
+        return os.environ.get(self.LENGTHS_SWITCH, "0") == "1"
+
+    def head_min_frames(self):
+        return aasist_head.min_frames()
+
+    def head_max_frames(self):
+        return aasist_head.max_frames(self.pool_cfg)
+
+    def forward(self, x, lengths=None):
+        if lengths is not None and self.head_takes_frames and not AasistHead.frames_supported(self):
+            raise NotImplementedError("wav2vec2_aasist: forward(x, lengths) runs on the fused stack and graph kernels only: this configuration's "
+                                      "shapes are not theirs, or SCL_AASIST_FUSED=0 is set")
+        return super().forward(x, lengths)
 
     # aasist.py:33-52: the SSL model simply follows the parent's train / eval mode (FrontHeadModel._ssl_train default)
 

@@ -8,7 +8,8 @@ graph.py, resnet_head.py, btse_head.py) whose parameters are views into the same
 data-parallel gradient buckets cover them too.  SCL_HEAD_GRAPH=1 replays a back-end as two captured hipGraphs per feature shape (off by
 default: the HIP back-ends are a few dozen launches).
 Variable-length scoring batches (forward(x, lengths), eval mode under torch.no_grad()) for a back-end that declares `head_takes_frames`
-and whose `_head_forward(mod, feats, frames)` masks the padding itself (resnet_head.py): the encoder runs with its padding mask on either
+and whose `_head_forward(mod, feats, frames)` masks the padding itself (resnet_head.py; aasist_head.py behind SCL_AASIST_LENGTHS=1, whose
+fused kernels also bound an utterance's frames from above: head_max_frames / max_samples): the encoder runs with its padding mask on either
 scoring precision and either row layout, feats rows beyond an utterance's frames are zeroed, and the back-end gets the host-side frame counts.
 Variable-length TRAINING batches (train mode, autograd on) for a back-end that declares `head_trains_frames` besides: the autograd boundary
 carries the row layout, the encoder trains under its padding mask or on packed rows (SCL_VARLEN_PACK=1; the back-end stays padded), and the
@@ -87,6 +88,19 @@ class FrontHeadModel(FlatModel):
     def min_samples(self):
         """The shortest row forward(x, lengths) takes: main.py --padding_type none zero-pads shorter files to it."""
         return self.cfg.samples_for(self.head_min_frames())
+
+    def head_max_frames(self):
+        """The most frames per utterance the back-end takes with lengths, or None: no limit of its own (a head_takes_frames plugin overrides it)."""
+        return None
+
+    def max_samples(self):
+        """The longest row forward(x, lengths) takes: main.py --padding_type none cuts longer files to it.  pack.VARLEN_MAX_SAMPLES unless the
+        back-end has a limit of its own: then the most samples that still give head_max_frames() frames."""
+        from .pack import VARLEN_MAX_SAMPLES
+        hi = self.head_max_frames()
+        if hi is None:
+            return VARLEN_MAX_SAMPLES
+        return min(VARLEN_MAX_SAMPLES, self.cfg.samples_for(hi + 1) - 1)
 
     def __init__(self, args, device, is_train=True, w2v_cfg=None, seed=0, rank=0):
         super().__init__(args, device, is_train, w2v_cfg)
@@ -242,10 +256,12 @@ class FrontHeadModel(FlatModel):
     VARLEN_REFUSAL = ("variable-length batches (forward(x, lengths), main.py --padding_type none, --padding_type zero --batch_size k) "
                       "are implemented for the wav2vec2_linear_nll and wav2vec2_resnet_nll plugins: this back-end has no padding mask; "
                       "use fixed-length clips (--padding_type zero / repeat at --batch_size 1) or one utterance per call")
+    LENGTHS_SWITCH = None      # a plugin whose scoring mode with lengths is opt-in names its environment switch here
 
     def forward(self, x, lengths=None):
         if lengths is not None and not self.head_takes_frames:
-            raise NotImplementedError("%s: %s" % (type(self).__module__.split(".")[-1], self.VARLEN_REFUSAL))
+            hint = "" if self.LENGTHS_SWITCH is None else ".  %s=1 turns on this plugin's scoring mode with lengths (eval mode under torch.no_grad())" % self.LENGTHS_SWITCH
+            raise NotImplementedError("%s: %s%s" % (type(self).__module__.split(".")[-1], self.VARLEN_REFUSAL, hint))
         if x.dim() == 3:
             x = x[:, :, 0]
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
@@ -259,6 +275,10 @@ class FrontHeadModel(FlatModel):
                                              " and a training mode on model.train() with autograd on" if self.head_trains_frames else
                                              " (training on zero-padded batches: wav2vec2_linear_nll and wav2vec2_resnet_nll)"))
             # the packed layout: encoder.VARLEN_PACK serves the bf16 encoder path (training, bf16 scoring), encoder.SCORE_PACK fp32 scoring
+            if self.head_max_frames() is not None and max(int(n) for n in lengths) > self.max_samples():
+                raise ValueError("%s: forward(x, lengths) takes at most %d samples (%d frames) per utterance — the back-end's fused kernels keep "
+                                 "an utterance's temporal nodes in LDS — got %d" % (type(self).__module__.split(".")[-1], self.max_samples(),
+                                                                                   self.head_max_frames(), max(int(n) for n in lengths)))
             counts, layout = ENC.row_layout(self.cfg, lengths, *x.shape, min_samples=self.min_samples(), refuse_short=True,
                                             score_f32=not train and SCORE_FP32, device=self.device)
         if torch.is_grad_enabled():

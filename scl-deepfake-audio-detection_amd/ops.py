@@ -783,6 +783,13 @@ def gat_score_fwd(x, W, bias, a, s, B, N, D, Do, n1):
     _call("scl_gat_score_fwd", _p(x), _p(W), _p(bias), _p(a), _p(s), B, N, D, Do, n1, _stream())
 
 
+def gat_score_fwd_var(x, W, bias, a, s, nodes, n1, B, Nmax, D, Do):
+    """gat_score_fwd for graphs of different sizes: nodes / n1 int32 [B] on the GPU (n1 None: the homogeneous layer); s holds utterance b's own
+    [nodes[b]][nodes[b]] matrix at the start of its Nmax * Nmax block."""
+    assert nodes.dtype == torch.int32 and nodes.numel() >= B and (n1 is None or (n1.dtype == torch.int32 and n1.numel() >= B))
+    _call("scl_gat_score_fwd_var", _p(x), _p(W), _p(bias), _p(a), _p(s), _p(nodes), None if n1 is None else _p(n1), B, Nmax, D, Do, _stream())
+
+
 def gat_score_bwd(x, W, bias, a, ds, dP, part, dx, B, N, D, Do, n1):
     _call("scl_gat_score_bwd", _p(x), _p(W), _p(bias), _p(a), _p(ds), _p(dP), _p(part), _p(dx), B, N, D, Do, n1, _stream())
 

@@ -507,8 +507,9 @@ class EvalDataset(Dataset):
         self.base_dir = os.path.join(base_dir, subdir) if subdir else base_dir
         self.cut = 64600
         self.padding_type = padding_type      # "zero" / "repeat": cut or pad to self.cut; "none": the waveform at its own length
-        self.n_cut = 0                        # "none": files longer than VARLEN_MAX_SAMPLES that were cut
+        self.n_cut = 0                        # "none": files longer than max_samples that were cut
         self.min_samples = VARLEN_MIN_SAMPLES     # "none": shorter files are zero-padded to it (main.py sets the model's own minimum)
+        self.max_samples = VARLEN_MAX_SAMPLES     # "none": longer files are cut to it (main.py sets the model's own maximum)
         self._cut_lock = threading.Lock()
 
     def __len__(self):
@@ -519,8 +520,8 @@ class EvalDataset(Dataset):
         x = load_audio(os.path.join(self.base_dir, utt_id), 16000)
         if self.padding_type == "none":
             x = np.asarray(x, dtype=np.float32)
-            if x.shape[0] > VARLEN_MAX_SAMPLES:
-                x = x[:VARLEN_MAX_SAMPLES]
+            if x.shape[0] > self.max_samples:
+                x = x[:self.max_samples]
                 with self._cut_lock:
                     self.n_cut += 1
             elif x.shape[0] < self.min_samples:

@@ -55,8 +55,11 @@ def _grad(p):
 class _Plan:
     """Buffers of one (B, H, W, channel plan); a plan is busy from a grad-mode forward until its backward."""
 
-    def __init__(self, B, H, W, chans, dev):
-        self.key = (B, H, W, tuple(chans))
+    def __init__(self, B, H, W, chans, dev, widths=False):
+        """widths: the plan of a variable-width scoring batch — forward buffers only, and `wt`, the per-utterance widths (int32 [B] on the
+        device, fixed address: overwritten before every replay)."""
+        self.key = (B, H, W, tuple(chans)) + (("widths",) if widths else ())
+        self.wt = torch.ones(B, dtype=torch.int32, device=dev) if widths else None
         self.B, self.H, self.W, self.Wp = B, H, W, W + 2
         self.G = B * (H + 2) * self.Wp
         self.slack = self.Wp + 2 + 256 + 6          # positions on either side of [0, G): halo of the first / last (256-position) tile
@@ -74,13 +77,14 @@ class _Plan:
         self.bstats = torch.zeros(2 * max(cps), device=dev)
         self.acc = torch.zeros(16 * 2 * max(cps), dtype=torch.float64, device=dev)      # SCL_RS_NSLOT rows; left zeroed by every finishing block
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.dx = [z(c) for c in cps]
-        self.dz = z(max(cps))
-        self.dtmp = z(max(cps))
+        if not widths:
+            self.dx = [z(c) for c in cps]
+            self.dz = z(max(cps))
+            self.dtmp = z(max(cps))
         self.wpk = None
         self.sig, self.fwd_calls, self.bwd_calls, self.bwd_need = None, None, None, None
         nsl = L.load().scl_rs_wgrad_nslabs
-        self.part = torch.empty(max(max(nsl(ci, co) * 6 * ci * co for ci, co in zip(cps[:-1], cps[1:])), max(nsl(c, c) * 6 * c * c for c in cps[1:])), device=dev)
+        self.part = None if widths else torch.empty(max(max(nsl(ci, co) * 6 * ci * co for ci, co in zip(cps[:-1], cps[1:])), max(nsl(c, c) * 6 * c * c for c in cps[1:])), device=dev)
         self.gx = L.SclRsGeom(B, H, W, 1, H, 0)        # block inputs / outputs: rows 1..H
         self.gy = L.SclRsGeom(B, H, W, 0, H, 0)        # conv1 outputs (H + 1 rows): rows 0..H
         Wp = self.Wp
@@ -97,7 +101,8 @@ class _Plan:
         if getattr(self, "at", None) is None:
             z = lambda: torch.zeros((self.G + 2 * self.slack) * 64, device=self.dev)
             f = lambda n: torch.zeros(n, device=self.dev)
-            self.at = dict(xa=z(), a1=[z(), z()], b1=[z(), z()], wl=z(), dxa=z(), dwl=z(), db1=[z(), z()], st_fb=f(256), st_a=[f(256), f(256)],
+            zb = (lambda: None) if self.wt is not None else z      # the backward's maps: not for a scoring plan
+            self.at = dict(xa=z(), a1=[z(), z()], b1=[z(), z()], wl=z(), dxa=zb(), dwl=zb(), db1=[zb(), zb()], st_fb=f(256), st_a=[f(256), f(256)],
                            bst_a=[f(128), f(128)], bst_fb=f(128), wpk=torch.empty(8 * 64 * 64, device=self.dev),
                            job=(L.SclGraphReduceJob * 1)())
         return self.at
@@ -134,7 +139,17 @@ def _conv(pl, inp, wpk, out, cin, cout, shifts, geom, *, bias=None, addend=None,
         d.shift[i] = s
     d.cin, d.cout, d.ntaps, d.stat_mode, d.training = cin, cout, len(shifts), stat_mode, 1 if training else 0
     d.eps, d.momentum, d.epi_act = eps, momentum, epi_act
-    ops._call("scl_rs_conv", ctypes.byref(d), _stream(), keep=d)
+    if pl.wt is not None:
+        ops._call("scl_rs_conv_w", ctypes.byref(d), pl.wt.data_ptr(), _stream(), keep=d)
+    else:
+        ops._call("scl_rs_conv", ctypes.byref(d), _stream(), keep=d)
+
+
+def _bn_act(pl, y, stats, a, C, act, geom):
+    if pl.wt is not None:
+        ops._call("scl_rs_bn_act_w", y, stats, a, C, act, ctypes.byref(geom), pl.wt.data_ptr(), _stream())
+    else:
+        ops._call("scl_rs_bn_act", y, stats, a, C, act, ctypes.byref(geom), _stream())
 
 
 def _pack_all(pl, blocks):
@@ -151,6 +166,8 @@ def _pack_all(pl, blocks):
         if blk.downsample:
             spec.append((i, "ds", blk.conv_downsample.weight, 3, ci_p, co, 0))
             spec.append((i, "dsT", blk.conv_downsample.weight, 3, co, ci_p, 1))
+    if pl.wt is not None:
+        spec = [e for e in spec if not e[6]]      # a scoring plan has no backward: no data-gradient images
     sizes = [nt * cinp * coutp for (_, _, _, nt, cinp, coutp, _) in spec]
     if pl.wpk is None or pl.wpk.numel() < sum(sizes):
         pl.wpk = torch.empty(sum(sizes), device=pl.dev)
@@ -187,6 +204,8 @@ def _forward(pl, x0, blocks, training, attn=None):
     sig = _signature(blocks, training) + ((id(attn[0]), attn[2].data_ptr(), _grad(attn[2]).data_ptr(), _grad(attn[1][0].weight).data_ptr()) if attn is not None else ())
     if pl.sig == sig and pl.fwd_calls is not None:
         pl.in_entry[1][0] = x0.data_ptr()
+        if pl.wt is not None:
+            pl.in_entry[1][4] = x0.shape[2]      # the source rows' own pitch: the batch's widest utterance
         if attn is None:
             pl.out_entry[1][1] = out.data_ptr()
         else:
@@ -200,7 +219,10 @@ def _forward(pl, x0, blocks, training, attn=None):
         ops.start_recording()
     wv = _pack_all(pl, blocks)
     pl.wv = wv
-    pl.in_entry = ops._call("scl_rs_copy", x0.data_ptr(), pl.p(pl.x[0], pl.cps[0]), x0.shape[-1], pl.cps[0], 0, ctypes.byref(pl.gx), S())
+    if pl.wt is not None:
+        pl.in_entry = ops._call("scl_rs_copy_w", x0.data_ptr(), pl.p(pl.x[0], pl.cps[0]), x0.shape[-1], pl.cps[0], x0.shape[2], ctypes.byref(pl.gx), pl.wt.data_ptr(), S())
+    else:
+        pl.in_entry = ops._call("scl_rs_copy", x0.data_ptr(), pl.p(pl.x[0], pl.cps[0]), x0.shape[-1], pl.cps[0], 0, ctypes.byref(pl.gx), S())
     n_y, n_x = float(B * (H + 1) * W), float(B * H * W)
     for i, blk in enumerate(blocks):
         ci, co = pl.cps[i], pl.cps[i + 1]
@@ -213,7 +235,7 @@ def _forward(pl, x0, blocks, training, attn=None):
             _conv(pl, xin, wv[(i, "c1")], y1, ci, co, pl.s1, pl.gy, bias=blk.conv1.bias)
             ops._call("scl_rs_bn_eval_stats", bn2.weight.data_ptr(), bn2.bias.data_ptr(), bn2.running_mean.data_ptr(), bn2.running_var.data_ptr(),
                       float(bn2.eps), co, pl.stats[i].data_ptr(), S())
-        ops._call("scl_rs_bn_act", y1, pl.stats[i].data_ptr(), a, co, 1, ctypes.byref(pl.gy), S())
+        _bn_act(pl, y1, pl.stats[i].data_ptr(), a, co, 1, pl.gy)
         if blk.downsample:
             tmp = pl.p(pl.tmp, co)
             _conv(pl, xin, wv[(i, "ds")], tmp, ci, co, pl.sd, pl.gx, bias=blk.conv_downsample.bias)
@@ -274,7 +296,7 @@ def _attn_forward(pl, attn, training, out):
     if not training:
         ops._call("scl_rs_bn_eval_stats", fb1.weight.data_ptr(), fb1.bias.data_ptr(), fb1.running_mean.data_ptr(), fb1.running_var.data_ptr(), float(fb1.eps), 64,
                   at["st_fb"].data_ptr(), S())
-    ops._call("scl_rs_bn_act", x6, at["st_fb"].data_ptr(), P(at["xa"]), 64, 1, ctypes.byref(pl.gx), S())
+    _bn_act(pl, x6, at["st_fb"].data_ptr(), P(at["xa"]), 64, 1, pl.gx)
     for p in range(2):
         o = 4 * 64 * p
         if training:
@@ -285,10 +307,14 @@ def _attn_forward(pl, attn, training, out):
             _conv(pl, P(at["xa"]), wv[("w1", p)], P(at["a1"][p]), 64, 64, [0], pl.gx, bias=a0.bias.data_ptr() + o, epi_act=1)
             ops._call("scl_rs_bn_eval_stats", bnA.weight.data_ptr() + o, bnA.bias.data_ptr() + o, bnA.running_mean.data_ptr() + o, bnA.running_var.data_ptr() + o,
                       float(bnA.eps), 64, at["st_a"][p].data_ptr(), S())
-        ops._call("scl_rs_bn_act", P(at["a1"][p]), at["st_a"][p].data_ptr(), P(at["b1"][p]), 64, 0, ctypes.byref(pl.gx), S())
+        _bn_act(pl, P(at["a1"][p]), at["st_a"][p].data_ptr(), P(at["b1"][p]), 64, 0, pl.gx)
     _conv(pl, P(at["b1"][0]), wv[("w3", 0)], P(at["wl"]), 64, 64, [0], pl.gx, bias=a3.bias)
     _conv(pl, P(at["b1"][1]), wv[("w3", 1)], P(at["wl"]), 64, 64, [0], pl.gx, addend=P(at["wl"]))
-    pl.pool_entry = ops._call("scl_rs_attn_pool_fwd", P(at["xa"]), P(at["wl"]), pos_S.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), 64, ctypes.byref(pl.gx), S())
+    if pl.wt is not None:
+        pl.pool_entry = ops._call("scl_rs_attn_pool_fwd_w", P(at["xa"]), P(at["wl"]), pos_S.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), 64, ctypes.byref(pl.gx),
+                                  pl.wt.data_ptr(), S())
+    else:
+        pl.pool_entry = ops._call("scl_rs_attn_pool_fwd", P(at["xa"]), P(at["wl"]), pos_S.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), 64, ctypes.byref(pl.gx), S())
 
 
 def _attn_backward(pl, attn, training, deS, deT):
@@ -439,6 +465,34 @@ def res_stack_pool(x0, blocks, first_bn1, attention, pos_S):
     params = [p for b in blocks for p in b.parameters()] + list(first_bn1.parameters()) + list(attention.parameters()) + [pos_S]
     hold = torch.is_grad_enabled() and (x0.requires_grad or any(p.requires_grad for p in params))
     return _StackPoolFn.apply(x0, blocks, attn, training, hold, *params)
+
+
+_POOL_W = PlanPool()      # plans of variable-width scoring batches: forward buffers only, at most PlanPool.MAX_POOL alive (the oldest goes)
+WIDTH_STEP = 8            # their map width is the batch's widest utterance rounded up to this (the masks make it free): <= 10 geometries per batch size
+
+
+def plan_width(w_max):
+    """The map width a variable-width batch whose widest utterance has w_max columns runs at."""
+    return min(-(-int(w_max) // WIDTH_STEP) * WIDTH_STEP, MAX_W)
+
+
+def res_stack_pool_widths(x0, widths, blocks, first_bn1, attention, pos_S):
+    """Scoring (eval mode under torch.no_grad()): res_stack_pool for utterances of different widths in one zero-padded batch.
+    x0 [B, H, Ws, 1] (Ws = the widest utterance; columns at and beyond an utterance's width are not interpreted), widths: ints in 1..Ws
+    -> (e_S [B, H, 64], e_T [B, plan_width(Ws), 64] with zero rows at and beyond an utterance's width).  Every utterance gets what
+    res_stack_pool gives it alone at its own width."""
+    blocks = list(blocks)
+    widths = [int(w) for w in widths]
+    B, H, Ws, _ = x0.shape
+    if blocks[0].training or torch.is_grad_enabled():
+        raise NotImplementedError("res_stack_pool_widths is a scoring mode: eval mode under torch.no_grad()")
+    if len(widths) != B or min(widths) < 1 or max(widths) > Ws or Ws > MAX_W:
+        raise ValueError("res_stack_pool_widths: need one width in 1..%d per row of the %r batch (maps up to %d wide), got %r" % (Ws, tuple(x0.shape), MAX_W, widths))
+    W = plan_width(Ws)
+    chans = [blocks[0].conv1.weight.shape[1]] + [b.conv1.weight.shape[0] for b in blocks]
+    pl = _POOL_W.acquire((B, H, W, tuple(chans), "widths"), x0.device, False, lambda: _Plan(B, H, W, chans, x0.device, widths=True))
+    pl.wt.copy_(torch.tensor(widths, dtype=torch.int32).pin_memory(), non_blocking=True)
+    return _forward(pl, x0.contiguous().float(), blocks, False, (first_bn1, attention, pos_S))
 
 
 def res_stack(x0, blocks):
