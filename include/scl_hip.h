@@ -844,6 +844,15 @@ int scl_btse_bio_supported(int bio_dim, int n_heads, int pf_dim, int n_layers, i
 int64_t scl_btse_bio_ws_floats(int n_layers, int L);
 int scl_btse_bio_fwd(const SclBtseBio* p, void* stream);
 int scl_btse_bio_bwd(const SclBtseBio* p, void* stream);
+/* The same descriptor and kernel bodies for a batch of WHOLE utterances of different token counts (BtseHead.forward(..., frames=...)):
+ * utterance b's score is read at its OWN last token lens[b] - 1 (clamped to 0..L; zeros for 0), which is what it gets alone at its own
+ * token count — masked keys take the fill value -1e4 and their soft-max weight underflows to exactly 0.  A deliberate difference from
+ * the reference, whose last-padded-position read-out gives every utterance shorter than the longest of a batch an exactly zero score.
+ * scl_btse_bio_bwd_own: the score's gradient enters at row lens[b] - 1 and the backward runs on the padded tail too: rows at and beyond
+ * lens[b] add exactly zero to every sum (same order and row ranges as scl_btse_bio_bwd), token ids beyond lens[b] are not read by the
+ * embedding gradient, and every scratch entry is written before it is read.  lens[b] == L everywhere: bit-identical to the entries above. */
+int scl_btse_bio_fwd_own(const SclBtseBio* p, void* stream);
+int scl_btse_bio_bwd_own(const SclBtseBio* p, void* stream);
 /* model.py:329-335, the join in front of fc2.  is_add == 0: b[r] = [emb[r] (C) | s[r] (bio_out)] — emb is copied, the s columns are
  * expected in place already (scl_btse_bio_fwd writes them), bwd: demb = db[:, :C], ds = db[:, C:].  is_add != 0: b = fc1(emb) + s
  * (fc1: [bio_out][C]); bwd also writes dW1 / db1.  All f32, B <= 4096. */

@@ -35,10 +35,13 @@ VARLEN_MODELS = ("wav2vec2_linear_nll", "wav2vec2_resnet_nll")      # --padding_
 # --padding_type none alone (scoring, never --padding_type zero --batch_size k training): plugin -> the environment switch that turns its
 # scoring mode with lengths on, read when main() runs
 VARLEN_SCORING_OPT_IN = {"wav2vec2_aasist": "SCL_AASIST_LENGTHS"}
+# --padding_type none with no switch, and likewise never routed into --padding_type zero --batch_size k training: the plugin's own
+# forward(x, lengths=...) in train mode is its training interface (the tokeniser runs per utterance)
+VARLEN_SCORING_MODELS = ("wav2vec2_btse",)
 
 
 def _scores_varlen(name):
-    return name in VARLEN_MODELS or os.environ.get(VARLEN_SCORING_OPT_IN.get(name, ""), "0") == "1"
+    return name in VARLEN_MODELS or name in VARLEN_SCORING_MODELS or os.environ.get(VARLEN_SCORING_OPT_IN.get(name, ""), "0") == "1"
 
 
 class EarlyStop:

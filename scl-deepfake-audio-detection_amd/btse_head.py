@@ -10,6 +10,16 @@ autograd node whose forward and hand-written backward are C-ABI calls only:
   * the frame-level MLP on the exact-fp32 MFMA GEMM (bias + LeakyReLU + counter-hash dropout in the epilogue, as the linear plugin's head),
   * the whole bio transformer in one launch per direction, one workgroup per utterance (csrc/btse.hip),
   * the join + fc2 + log_softmax tail (csrc/btse.hip, csrc/elementwise.hip).
+
+Variable-length batches (BtseHead.forward(..., frames=[...]): whole utterances of different frame AND token counts in one zero-padded
+batch, scoring and training).  Row b gets what the head computes for that utterance alone at its own frames and tokens: the mean over time
+runs over its frames[b] frames (meanpool_*_varlen; the MLP GEMMs still run over all B * T rows, and the backward's zeros beyond frames[b]
+keep the padding out of every weight, bias and data gradient), and the bio score is read at its OWN last token bio_lengths[b] - 1
+(scl_btse_bio_*_own).  That read-out is a deliberate difference from the reference, which reads the last PADDED position times its mask
+(model.py:234-236) and so gives every row shorter than the longest an exactly zero score and gradient: right for its fixed-length
+batches — and unchanged here without `frames` — wrong for a batch of whole utterances.  Masked keys take the fill value -1e4, their
+soft-max weight underflows to exactly 0, so the valid positions do not see the padding: on the CPU oracle the own-last-token score equals
+the utterance alone to 3.9e-16 relative in fp64 (2.4e-7 in fp32; tests/test_btse_varlen_cpu.py).
 """
 import ctypes
 import math
@@ -118,7 +128,12 @@ class BtseHead(nn.Module):
         _raise_if_bad_tokens(mod, mod.btse_args["n_bios"], wait=True)
 
     @staticmethod
-    def forward(mod, feats, bio=None, bio_lengths=None):
+    def forward(mod, feats, bio=None, bio_lengths=None, frames=None):
+        """frames: None (a fixed-length batch: mean over all T frames, the reference's read-out at the last padded token position) or the
+        host-side frame counts of a zero-padded batch of whole utterances, one int in 1..T per row: mean over the row's own frames, d feats
+        exactly 0 beyond them, and the bio score read at the row's own last token bio_lengths[b] - 1.  In that mode bio_lengths on the host
+        must lie in 1..tokens (ValueError); device-resident counts are clamped by the kernel, and a count of 0 gives a zero score and a zero
+        gradient row.  Train-mode MLP dropout masks are indexed by element of the padded [B, T, 128] in both modes."""
         if bio is None:
             bio, bio_lengths = mod.__dict__["_bio"]
         a = mod.btse_args
@@ -128,13 +143,14 @@ class BtseHead(nn.Module):
         if a["is_add"]:
             params += [mod.fc1.weight, mod.fc1.bias]
         params += [mod.fc2.weight, mod.fc2.bias]
-        return _BtseFn.apply(mod, feats, bio, bio_lengths, *params)
+        return _BtseFn.apply(mod, feats, bio, bio_lengths, frames, *params)
 
 
-def _plan(mod, B, T, Lt, dev):
-    """Static buffers + the kernel descriptor of a (batch, frames, tokens) combination."""
+def _plan(mod, B, T, Lt, dev, own=False):
+    """Static buffers + the kernel descriptor of a (batch, frames, tokens) combination; own: a variable-length batch (its device-side
+    frame counts live in the plan)."""
     plans = mod.__dict__.setdefault("_btse_plans", {})
-    key = (B, T, Lt, torch.cuda.current_stream(dev).cuda_stream)
+    key = (B, T, Lt, torch.cuda.current_stream(dev).cuda_stream, bool(own))
     pl = plans.get(key)
     if pl is not None:
         return pl
@@ -175,6 +191,8 @@ def _plan(mod, B, T, Lt, dev):
     d.d_out, d.dout_ld, d.slab, d.slab_ld, d.ws_stride = pl["ds"].data_ptr(), bo, pl["slab"].data_ptr(), NP, wsf
     d.n_layers, d.n_bios, d.bio_out, d.L, d.B = NL, a["n_bios"], bo, Lt, B
     d.bio_dim, d.n_heads, d.pf_dim, d.window = a["bio_dim"], a["n_heads"], a["pf_dim"], WINDOW
+    if own:
+        pl["frames"] = torch.ones(B, dtype=torch.int32, device=dev)
     pl["desc"] = d
     pl["ptrs"] = [p.data_ptr() for p in bio_p]
     plans[key] = pl
@@ -211,7 +229,7 @@ def _raise_if_bad_tokens(mod, n_bios, wait=False):
 
 class _BtseFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mod, feats, bio, bio_lengths, *params):
+    def forward(ctx, mod, feats, bio, bio_lengths, frames, *params):
         a = mod.btse_args
         dev = feats.device
         B, T, C = feats.shape
@@ -223,7 +241,15 @@ class _BtseFn(torch.autograd.Function):
             raise IndexError("wav2vec2_btse: bio token out of range [0, %d)" % a["n_bios"])          # nn.Embedding's error (model.py:228)
         _raise_if_bad_tokens(mod, a["n_bios"])          # a device-side check queued by an EARLIER forward, if it has completed
         Lt = bio.shape[1]
-        pl = _plan(mod, B, T, Lt, dev)
+        own = frames is not None
+        if own:
+            frames = [int(t) for t in (frames.tolist() if torch.is_tensor(frames) else frames)]
+            if len(frames) != B or min(frames) < 1 or max(frames) > T:
+                raise ValueError("wav2vec2_btse: frames: need one count in 1..%d per row of the %r batch, got %r" % (T, tuple(feats.shape), frames))
+            if not bio_lengths.is_cuda and bio_lengths.numel() and (int(bio_lengths.min()) < 1 or int(bio_lengths.max()) > Lt):
+                raise ValueError("wav2vec2_btse: with frames, the score is read at every utterance's own last token: bio_lengths must lie "
+                                 "in 1..%d, got %r" % (Lt, bio_lengths.tolist()))
+        pl = _plan(mod, B, T, Lt, dev, own)
         if pl["ptrs"] != [p.data_ptr() for p in BtseHead.bio_params(mod)]:
             raise RuntimeError("wav2vec2_btse: parameter storage moved after the kernel descriptor was built")
         M = B * T
@@ -243,13 +269,18 @@ class _BtseFn(torch.autograd.Function):
             ops.gemm(Op(prev, HID), Op(w[2 * j].detach(), HID), pl["h"][j], M, HID, HID, bias=w[2 * j + 1].detach(), act=ACT_LEAKY, c2=pl["pre"][j],
                      drop_p=drop, drop_seed=seeds[j], x3=False)       # x3=False: the EXACT f32 kernel, as model_linear's head (not the SCL_F32X3 default)
             prev = pl["h"][j]
-        ops.meanpool_fwd(prev, pl["emb"], B, T, HID)                              # linear.py:62
-        ops.btse_bio_fwd(pl["desc"])                                              # model.py:328
+        if own:      # the mean over the utterance's own frames, the score at its own last token
+            pl["frames"].copy_(torch.tensor(frames, dtype=torch.int32), non_blocking=True)
+            ops.meanpool_fwd_varlen(prev, pl["emb"], pl["frames"], B, T, HID)
+            ops.btse_bio_fwd_own(pl["desc"])
+        else:
+            ops.meanpool_fwd(prev, pl["emb"], B, T, HID)                          # linear.py:62
+            ops.btse_bio_fwd(pl["desc"])                                          # model.py:328
         is_add = a["is_add"]
         fc1w, fc1b = (params[-4].detach(), params[-3].detach()) if is_add else (None, None)
         ops.btse_join_fwd(pl["emb"], pl["s"] if is_add else None, fc1w, fc1b, pl["bvec"], B, HID, a["bio_out"], is_add)
         ops.utt_head_fwd(pl["bvec"], params[-2].detach(), params[-1].detach(), pl["logp"], B, pl["KB"], a["nb_classes"])   # model.py:336-338
-        ctx.mod, ctx.pl, ctx.x, ctx.seeds, ctx.drop, ctx.params = mod, pl, x, seeds, drop, params
+        ctx.mod, ctx.pl, ctx.x, ctx.seeds, ctx.drop, ctx.params, ctx.own = mod, pl, x, seeds, drop, params, own
         ctx.gen = pl["gen"] = pl.get("gen", 0) + 1
         return pl["logp"].clone(), pl["bvec"].clone()
 
@@ -271,11 +302,14 @@ class _BtseFn(torch.autograd.Function):
                          pl["tail_ws"], B, KB, NC)
         dfc1w, dfc1b = (f32(bo, HID), f32(bo)) if is_add else (None, None)
         ops.btse_join_bwd(pl["db"], pl["emb"], params[-4].detach() if is_add else None, pl["demb"], pl["ds"], dfc1w, dfc1b, B, HID, bo, is_add)
-        ops.btse_bio_bwd(pl["desc"])
+        (ops.btse_bio_bwd_own if ctx.own else ops.btse_bio_bwd)(pl["desc"])
         ops.reduce_slabs(pl["slab"], pl["gbio"], pl["NP"], B, pl["NP"])          # utterance rows summed in index order
         gbio = [g.clone().view(p.shape) for g, p in zip(torch.split(pl["gbio"], pl["sizes"]), BtseHead.bio_params(mod))]
         # the frame-level MLP, in reverse (as scl_amd/model_linear.py::_backward_kernels, f32 operands)
-        ops.meanpool_bwd(pl["demb"], pl["pre"][2], pl["dpre"][2], B, T, HID, ACT_LEAKY, drop, seeds[2])
+        if ctx.own:      # scaled by 1 / frames[b], zeros beyond: the GEMMs below run over all B * T rows and see only the valid ones
+            ops.meanpool_bwd_varlen(pl["demb"], pl["pre"][2], pl["dpre"][2], pl["frames"], B, T, HID, ACT_LEAKY, drop, seeds[2])
+        else:
+            ops.meanpool_bwd(pl["demb"], pl["pre"][2], pl["dpre"][2], B, T, HID, ACT_LEAKY, drop, seeds[2])
         gw = [None] * 6
         d_feats = f32(B, T, HID)
         sk = max(1, min(32, M // 128))
@@ -297,4 +331,4 @@ class _BtseFn(torch.autograd.Function):
             else:
                 ops.gemm(Op(dpre, HID), wj, d_feats, M, HID, HID, b_t=True, x3=False)      # backend.py:41-43: no activation between LL and the MLP
         grads = gw + gbio + ([dfc1w, dfc1b] if is_add else []) + [dfc2w, dfc2b]
-        return (None, d_feats, None, None) + tuple(grads)
+        return (None, d_feats, None, None, None) + tuple(grads)

@@ -28,6 +28,10 @@
 // The activations the backward needs go to a per-utterance scratch row in HBM (L2-resident: 392 L floats per layer).
 // model.py:236 reads the LAST padded position times its mask: an utterance shorter than L scores exactly zero and contributes no
 // gradient — the backward writes a zero row for it and returns.
+// The _own entries (scl_btse_bio_fwd_own / _bwd_own: the same kernel bodies behind a template flag) serve a batch of WHOLE utterances of
+// different token counts: the read-out is the utterance's own last token len - 1, its gradient enters there, and the backward runs on a
+// padded tail — the attention passes recompute the forward's mask, so every row at or beyond len carries an exactly zero data gradient
+// and adds exactly zero to every reduction over the rows; only len == 0 writes a zero row and returns.
 #include "common.h"
 
 namespace {
@@ -143,6 +147,8 @@ __device__ __forceinline__ float dot8_lds(const float* __restrict__ a, const flo
 // scratch row already, so the split adds no traffic.
 
 // rows kernel `l` (0 .. n_layers): [embedding | the post-attention half of layer l - 1] -> x;  [Q, K, V of layer l | the read-out]
+// OWN: the read-out at the utterance's own last token (row len - 1, zeros for len == 0) instead of the last padded position
+template <bool OWN>
 __global__ __launch_bounds__(NTR) void btse_rows_fwd_kernel(const SclBtseBio p, const int l) {
     const int b = blockIdx.x, t = threadIdx.x, L = p.L;
     const int len = min(max(p.lens[b], 0), L);            // commons.sequence_mask: arange(L) < length
@@ -215,15 +221,16 @@ __global__ __launch_bounds__(NTR) void btse_rows_fwd_kernel(const SclBtseBio p, 
         }
         }
     }
-    if (l < p.n_layers || (int)blockIdx.y != (L - 1) / NTR) return;       // the read-out is the work of the block that owns row L - 1
-    __syncthreads();                                                                  // row L - 1 was written by a thread of this block
-    const bool mlast = L - 1 < len;                                                   // model.py:234-236
+    const int last = OWN ? max(len - 1, 0) : L - 1;
+    if (l < p.n_layers || (int)blockIdx.y != last / NTR) return;          // the read-out is the work of the block that owns row `last`
+    __syncthreads();                                                                  // row `last` was written by a thread of this block
+    const bool mlast = OWN ? len > 0 : L - 1 < len;                                   // model.py:234-236
     for (int o = t; o < p.bio_out; o += NTR) {
         float y = 0.f;
         if (mlast) {
             y = p.bs[o];
 #pragma unroll 8
-            for (int k = 0; k < BD; ++k) y = fmaf(cur[(L - 1) * BD + k], p.Ws[o * BD + k], y);
+            for (int k = 0; k < BD; ++k) y = fmaf(cur[last * BD + k], p.Ws[o * BD + k], y);
         }
         p.out[(int64_t)b * p.out_ld + o] = y;
     }
@@ -358,13 +365,16 @@ __device__ __forceinline__ void ln_param_grads(const float* __restrict__ dy, con
 //   attention (3): workgroup per (utterance, head), thread per QUERY row -> dq, delta, the band of dS / P the relative embeddings need;
 //   attention (5): workgroup per (utterance, head), thread per KEY row   -> dk, dv;
 // and a last rows kernel for (4) + (6) of layer 0 and the embedding gradient.  2 n_layers attention + n_layers + 1 row launches.
+// OWN: the score's gradient enters at row len - 1 and all L rows run (those at and beyond len with an exactly zero data gradient: every sum
+// over the rows keeps its order and its row ranges, and gets +-0 from them).
+template <bool OWN>
 __global__ __launch_bounds__(NT) void btse_rows_bwd_kernel(const SclBtseBio p, const int l6, const int l012) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float red[2 * NG * BD], epart[2][3][NR * BK];
     const int b = blockIdx.x, t = threadIdx.x, L = p.L;
     const int len = min(max(p.lens[b], 0), L);
     float* slab = p.slab + (int64_t)b * p.slab_ld;
-    if (len < L) {      // the read-out position is padding: zero score, zero gradient (model.py:234-236)
+    if (OWN ? len == 0 : len < L) {      // the read-out position is padding: zero score, zero gradient (model.py:234-236)
         if (l6 < 0)
             for (int64_t idx = t; idx < p.slab_ld; idx += NT) slab[idx] = 0.f;
         return;
@@ -374,16 +384,18 @@ __global__ __launch_bounds__(NT) void btse_rows_bwd_kernel(const SclBtseBio p, c
     float* G = ws + ((int64_t)p.n_layers * O_LAYER + BD) * L;
     float* gdx = G + G_DX * L;
     const float* gda = G + G_DA * L;
-    if (l6 < 0) {   // scoring conv at the last position
+    const int last = OWN ? len - 1 : L - 1;
+    if (l6 < 0) {   // scoring conv at the read-out position
         const float* dsc = p.d_out + (int64_t)b * p.dout_ld;
-        const float* xfin = ws + (int64_t)p.n_layers * O_LAYER * L + (L - 1) * BD;
+        const float* xfin = ws + (int64_t)p.n_layers * O_LAYER * L + last * BD;
         for (int o = t; o < p.bio_out; o += NT) slab[p.go_bs + o] = dsc[o];
         for (int idx = t; idx < p.bio_out * BD; idx += NT) slab[p.go_Ws + idx] = dsc[idx >> 5] * xfin[idx & 31];
-        for (int idx = t; idx < (L - 1) * BD; idx += NT) gdx[idx] = 0.f;
+        for (int idx = t; idx < L * BD; idx += NT)
+            if ((idx >> 5) != last) gdx[idx] = 0.f;
         if (t < BD) {
             float a = 0.f;
             for (int o = 0; o < p.bio_out; ++o) a = fmaf(dsc[o], p.Ws[o * BD + t], a);
-            gdx[(L - 1) * BD + t] = a;
+            gdx[last * BD + t] = a;
         }
         __syncthreads();
     } else {
@@ -483,19 +495,22 @@ __global__ __launch_bounds__(NT) void btse_rows_bwd_kernel(const SclBtseBio p, c
     for (int idx = t; idx < p.n_bios * BD; idx += NT) {      // embedding rows (model.py:228)
         const int tk = idx >> 5, cc = idx & 31;
         float a = 0.f;
-        for (int r = 0; r < L; ++r)
+        for (int r = 0; r < (OWN ? len : L); ++r)      // OWN: the ids beyond the utterance's tokens are not read
             if (min(max(tok[r], 0), p.n_bios - 1) == tk) a += gdx[r * BD + cc];
         slab[p.go_emb + idx] = a * EMB_SCALE;
     }
 }
 
 // (3) attention backward, pass 1 of layer l: head blockIdx.y of utterance blockIdx.x, four lanes per QUERY row (keys j = s mod 4, as the forward)
-//     -> dq, delta, the band of dS / P
+//     -> dq, delta, the band of dS / P.  OWN: the forward's mask (query and key below len, FILL elsewhere) is recomputed; a masked
+//     entry passes no gradient to q or k (masked_fill), and its probability is exactly 0 for a valid query
+template <bool OWN>
 __global__ __launch_bounds__(NTA) void btse_attn_bwd_q_kernel(const SclBtseBio p, const int l) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float Eks[NR * BK], Evs[NR * BK];
     const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x, L = p.L;
-    if (min(max(p.lens[b], 0), L) < L) return;
+    const int len = min(max(p.lens[b], 0), L);
+    if (OWN ? len == 0 : len < L) return;
     float* ws = p.ws + (int64_t)b * p.ws_stride;
     float* base = ws + (int64_t)l * O_LAYER * L;
     const float* const* W = p.lw[l];
@@ -512,6 +527,7 @@ __global__ __launch_bounds__(NTA) void btse_attn_bwd_q_kernel(const SclBtseBio p
     __syncthreads();
     const int i = blockIdx.z * RPB + (t >> 2), ks = t & 3;
     const int ir = min(i, L - 1);
+    const bool mi = ir < len;
     float qs[BK], da[BK], dq[BK];
 #pragma unroll
     for (int d = 0; d < BK; ++d) { qs[d] = base[O_Q * L + ir * BD + h * BK + d] * QSCALE; da[d] = gda[ir * BD + h * BK + d]; dq[d] = 0.f; }
@@ -520,7 +536,8 @@ __global__ __launch_bounds__(NTA) void btse_attn_bwd_q_kernel(const SclBtseBio p
 #pragma unroll 2
     for (int j = ks; j < L; j += KS) {
         const int dj = j - ir;
-        const float pij = __expf(score(qs, Kh + j * BK, Eks, dj) - lse);
+        const bool on = !OWN || (mi && j < len);
+        const float pij = __expf((on ? score(qs, Kh + j * BK, Eks, dj) : FILL) - lse);
         delta = fmaf(pij, score(da, Vh + j * BK, Evs, dj), delta);
     }
     delta = quad_sum(delta);
@@ -538,8 +555,9 @@ __global__ __launch_bounds__(NTA) void btse_attn_bwd_q_kernel(const SclBtseBio p
     for (int j = ks; j < L; j += KS) {
         const int dj = j - ir;
         const float* kr = Kh + j * BK;
-        const float pij = __expf(score(qs, kr, Eks, dj) - lse);
-        const float dS = pij * (score(da, Vh + j * BK, Evs, dj) - delta);
+        const bool on = !OWN || (mi && j < len);
+        const float pij = __expf((on ? score(qs, kr, Eks, dj) : FILL) - lse);
+        const float dS = on ? pij * (score(da, Vh + j * BK, Evs, dj) - delta) : 0.f;
 #pragma unroll
         for (int d = 0; d < BK; ++d) dq[d] = fmaf(dS, kr[d], dq[d]);
         if ((unsigned)(dj + BW) <= 2u * BW) {
@@ -559,11 +577,14 @@ __global__ __launch_bounds__(NTA) void btse_attn_bwd_q_kernel(const SclBtseBio p
 }
 
 // (5) attention backward, pass 2: four lanes per KEY row (queries i = s mod 4) -> dk, dv (the head's Q * scale, dA, log-sum-exp and delta rows in LDS)
+//     OWN: masked as pass 1 — a key at or beyond len gets dk = 0 (no valid query sees it) and dv = 0 (the padded queries' dA rows are 0)
+template <bool OWN>
 __global__ __launch_bounds__(NTA) void btse_attn_bwd_kv_kernel(const SclBtseBio p, const int l) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float Eks[NR * BK], Evs[NR * BK];
     const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x, L = p.L;
-    if (min(max(p.lens[b], 0), L) < L) return;
+    const int len = min(max(p.lens[b], 0), L);
+    if (OWN ? len == 0 : len < L) return;
     float* ws = p.ws + (int64_t)b * p.ws_stride;
     float* base = ws + (int64_t)l * O_LAYER * L;
     const float* const* W = p.lw[l];
@@ -595,8 +616,9 @@ __global__ __launch_bounds__(NTA) void btse_attn_bwd_kv_kernel(const SclBtseBio 
         const bool band = (unsigned)(dj + BW) <= 2u * BW;
         const float sij = dot8(qr, kj) + (band ? dot8_lds(qr, Eks + (dj + BW) * BK) : 0.f);      // q_i . (k_j + emb_rel_k[j - i + 4])
         const float g = dot8(ar, vj) + (band ? dot8_lds(ar, Evs + (dj + BW) * BK) : 0.f);         // dA_i . (v_j + emb_rel_v[j - i + 4])
-        const float pij = __expf(sij - lseS[i]);
-        const float dS = pij * (g - delS[i]);
+        const bool on = !OWN || (i < len && jr < len);
+        const float pij = __expf((on ? sij : FILL) - lseS[i]);
+        const float dS = on ? pij * (g - delS[i]) : 0.f;
 #pragma unroll
         for (int d = 0; d < BK; ++d) { dk[d] = fmaf(dS, qr[d], dk[d]); dv[d] = fmaf(pij, ar[d], dv[d]); }
     }
@@ -677,31 +699,39 @@ extern "C" int scl_btse_bio_supported(int bio_dim, int n_heads, int pf_dim, int 
 }
 extern "C" int64_t scl_btse_bio_ws_floats(int n_layers, int L) { return ((int64_t)n_layers * O_LAYER + BD + G_TOTAL) * L; }
 
-extern "C" int scl_btse_bio_fwd(const SclBtseBio* p, void* stream) {
-    const int rc = bio_check(p, "btse_bio_fwd", false);
+namespace {
+template <bool OWN>
+int bio_fwd(const SclBtseBio* p, void* stream, const char* what) {
+    const int rc = bio_check(p, what + 4, false);
     if (rc != SCL_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = (size_t)2 * p->L * BK * sizeof(float);      // one head's K and V slices
     for (int l = 0; l <= p->n_layers; ++l) {
-        hipLaunchKernelGGL(btse_rows_fwd_kernel, dim3(p->B, (p->L + NTR - 1) / NTR), dim3(NTR), 0, s, *p, l);
+        hipLaunchKernelGGL(btse_rows_fwd_kernel<OWN>, dim3(p->B, (p->L + NTR - 1) / NTR), dim3(NTR), 0, s, *p, l);
         if (l < p->n_layers) hipLaunchKernelGGL(btse_attn_fwd_kernel, dim3(p->B, BH, (p->L + RPB - 1) / RPB), dim3(NTA), lds, s, *p, l);
     }
-    return scl_check_launch("scl_btse_bio_fwd");
+    return scl_check_launch(what);
 }
-extern "C" int scl_btse_bio_bwd(const SclBtseBio* p, void* stream) {
-    const int rc = bio_check(p, "btse_bio_bwd", true);
+template <bool OWN>
+int bio_bwd(const SclBtseBio* p, void* stream, const char* what) {
+    const int rc = bio_check(p, what + 4, true);
     if (rc != SCL_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t stage = (size_t)RC * (BD + BF) * sizeof(float);                 // the widest weight-gradient staging chunk
     const size_t lds_q = (size_t)2 * p->L * BK * sizeof(float), lds_kv = (size_t)(2 * p->L * BK + 2 * p->L) * sizeof(float);
     for (int l = p->n_layers - 1; l >= 0; --l) {
-        hipLaunchKernelGGL(btse_rows_bwd_kernel, dim3(p->B), dim3(NT), stage, s, *p, l + 1 < p->n_layers ? l + 1 : -1, l);
-        hipLaunchKernelGGL(btse_attn_bwd_q_kernel, dim3(p->B, BH, (p->L + RPB - 1) / RPB), dim3(NTA), lds_q, s, *p, l);
-        hipLaunchKernelGGL(btse_attn_bwd_kv_kernel, dim3(p->B, BH, (p->L + RPB - 1) / RPB), dim3(NTA), lds_kv, s, *p, l);
+        hipLaunchKernelGGL(btse_rows_bwd_kernel<OWN>, dim3(p->B), dim3(NT), stage, s, *p, l + 1 < p->n_layers ? l + 1 : -1, l);
+        hipLaunchKernelGGL(btse_attn_bwd_q_kernel<OWN>, dim3(p->B, BH, (p->L + RPB - 1) / RPB), dim3(NTA), lds_q, s, *p, l);
+        hipLaunchKernelGGL(btse_attn_bwd_kv_kernel<OWN>, dim3(p->B, BH, (p->L + RPB - 1) / RPB), dim3(NTA), lds_kv, s, *p, l);
     }
-    hipLaunchKernelGGL(btse_rows_bwd_kernel, dim3(p->B), dim3(NT), stage, s, *p, 0, -1);
-    return scl_check_launch("scl_btse_bio_bwd");
+    hipLaunchKernelGGL(btse_rows_bwd_kernel<OWN>, dim3(p->B), dim3(NT), stage, s, *p, 0, -1);
+    return scl_check_launch(what);
 }
+}  // namespace
+extern "C" int scl_btse_bio_fwd(const SclBtseBio* p, void* stream) { return bio_fwd<false>(p, stream, "scl_btse_bio_fwd"); }
+extern "C" int scl_btse_bio_bwd(const SclBtseBio* p, void* stream) { return bio_bwd<false>(p, stream, "scl_btse_bio_bwd"); }
+extern "C" int scl_btse_bio_fwd_own(const SclBtseBio* p, void* stream) { return bio_fwd<true>(p, stream, "scl_btse_bio_fwd_own"); }
+extern "C" int scl_btse_bio_bwd_own(const SclBtseBio* p, void* stream) { return bio_bwd<true>(p, stream, "scl_btse_bio_bwd_own"); }
 extern "C" int scl_btse_join_fwd(const float* emb, const float* s, const float* W1, const float* b1, float* b, int B, int C, int bio_out, int is_add,
                                  void* stream) {
     SCL_REQUIRE(emb && b && B > 0 && B <= 4096 && C > 0 && bio_out > 0, "btse_join_fwd: bad args");

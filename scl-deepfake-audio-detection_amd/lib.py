@@ -293,6 +293,8 @@ def _protos():
         "scl_btse_bio_ws_floats": ([_i32, _i32], _i64),
         "scl_btse_bio_fwd": ([P(SclBtseBio), _vp], _i32),
         "scl_btse_bio_bwd": ([P(SclBtseBio), _vp], _i32),
+        "scl_btse_bio_fwd_own": ([P(SclBtseBio), _vp], _i32),
+        "scl_btse_bio_bwd_own": ([P(SclBtseBio), _vp], _i32),
         "scl_btse_join_fwd": ([_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
         "scl_btse_join_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
     }

@@ -1,7 +1,7 @@
 """`wav2vec2_btse` model plugin — host-side mirror of model/wav2vec2_btse/model.py::Model (BASELINE.json configs[4]).
 
     Model(args: the YAML `model:` block of conf-5-btse-trans64.yaml, device, is_train=True)
-    forward(x [bz, L], bio=None, bio_lengths=None, y=None) -> (log_probs [bz, 2], ssl_feat [bz, T, 128], b [bz, 128 + bio_out])
+    forward(x [bz, L], bio=None, bio_lengths=None, y=None, lengths=None) -> (log_probs [bz, 2], ssl_feat [bz, T, 128], b [bz, 128 + bio_out])
                                                               (log_probs only when not is_train)          (model.py:321-343)
     loss(output, feats, emb, labels, config, info=None) -> dict of 0-d tensors
 
@@ -21,6 +21,17 @@ Two things the reference does not hold, and what this plugin does about them:
 The MLP's own logits (m_utt_level) are computed and dropped by the reference (model.py:324): here they are not computed, and the two
 tensors sit behind the trainable range so that AdamW leaves them untouched exactly as torch.optim.AdamW skips a parameter without .grad.
 The SSL encoder always runs in train mode (backend.py:29,39: the back-end's own `is_train` stays True whatever the outer flag says).
+
+Variable-length batches: forward(x, lengths=[n_b]) takes whole utterances of different lengths, zero-padded to [bz, L] — scoring (eval mode
+under torch.no_grad(), either scoring precision) and training (train mode with autograd on).  Row b's outputs and its share of every
+gradient are what the plugin computes for that utterance alone at its own length with its own tokens: the encoder runs under its padding
+mask (or on packed rows), the mean over time of the frame-level MLP runs over its T_b frames, rows of feats and d(feats) beyond T_b are zero,
+and the bio score is read at its OWN last token k_b - 1 — not, as model.py:234-236 has it for fixed-length batches and as this plugin keeps
+it without `lengths`, at the last padded position, which would leave every row shorter than the longest with a zero bio score
+(btse_head.py).  Tokens: bio [bz, Lt] padded with any valid id and bio_lengths = the own counts k_b (1..Lt on the host); without explicit
+tokens the tokeniser is called once per utterance on x[b:b+1, :n_b] and the rows are padded with token 0 to the longest.  Limits: 400
+samples at least (one frame), 1..512 tokens per utterance (the fused bio kernel).  main.py routes --eval --padding_type none here;
+main.py training with --padding_type zero --batch_size k is not routed (forward(x, lengths=...) in train mode is the training interface).
 """
 import importlib
 
@@ -32,8 +43,19 @@ from .model_front import FrontHeadModel
 from .model_linear import dropout_stream_seed, loss_custom
 
 
+def pad_token_rows(rows):
+    """Ragged token rows (one sequence per utterance) -> (bio [bz, longest] int32 with token 0 as filler, the own counts [bz] int32)."""
+    lens = [len(r) for r in rows]
+    bio = np.zeros((len(rows), max(lens + [1])), dtype=np.int32)
+    for b, r in enumerate(rows):
+        bio[b, :lens[b]] = np.asarray(r, dtype=np.int32)
+    return torch.from_numpy(bio), torch.tensor(lens, dtype=torch.int32)
+
+
 class Model(FrontHeadModel):
     front_prefix = "backend."
+    head_takes_frames = True       # BtseHead masks the mean over time and reads the bio score at the utterance's own last token
+    head_trains_frames = True      # ... with a masked backward
 
     def __init__(self, args, device, is_train=True, w2v_cfg=None, seed=0, rank=0):
         super().__init__(args, device, is_train=is_train, w2v_cfg=w2v_cfg, seed=seed, rank=rank)
@@ -51,7 +73,9 @@ class Model(FrontHeadModel):
         self.btse_args = head.btse_args
         return head
 
-    _head_forward = staticmethod(BtseHead.forward)
+    @staticmethod
+    def _head_forward(mod, feats, frames=None):
+        return BtseHead.forward(mod, feats, frames=frames)
 
     def _ssl_train(self):
         return True      # backend.py:29,39 -> xlsr.py:30-31: self.model.train() on every call
@@ -66,14 +90,25 @@ class Model(FrontHeadModel):
         lens = torch.tensor([len(t) for t in toks], dtype=torch.int32)
         return torch.from_numpy(np.asarray(toks, dtype=np.int32)), lens          # ragged lists fail here, as torch.IntTensor(bio) does
 
+    def get_bio_own(self, X_pad, lengths, fs):
+        """The tokens of a variable-length batch: the tokeniser runs once per utterance on its own samples x[b:b+1, :n_b]; the rows may
+        differ in length and are padded with token 0, bio_lengths are the own counts."""
+        lengths = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        if len(lengths) != X_pad.shape[0] or any(n < 1 or n > X_pad.shape[1] for n in lengths):
+            raise ValueError("lengths: need one sample count in 1..%d per row of the %r batch, got %r" % (X_pad.shape[1], tuple(X_pad.shape), lengths))
+        rows = []
+        for b, n in enumerate(lengths):
+            toks, _ = self.get_Bio(X_pad[b:b + 1, :n], fs)
+            rows.append(toks[0].tolist())
+        return pad_token_rows(rows)
+
     def forward(self, x, bio=None, bio_lengths=None, y=None, lengths=None):
-        if lengths is not None:
-            raise NotImplementedError("model_btse: " + self.VARLEN_REFUSAL)
         if bio is None:
-            bio, bio_lengths = self.get_Bio(x if x.dim() == 2 else x[:, :, 0], 16000)
+            xs = x if x.dim() == 2 else x[:, :, 0]
+            bio, bio_lengths = self.get_Bio(xs, 16000) if lengths is None else self.get_bio_own(xs, lengths, 16000)
         self.__dict__["_bio"] = (bio, bio_lengths)
         try:
-            return super().forward(x)
+            return super().forward(x, lengths)
         finally:
             self.__dict__["_bio"] = None
 

@@ -8,7 +8,7 @@ graph.py, resnet_head.py, btse_head.py) whose parameters are views into the same
 data-parallel gradient buckets cover them too.  SCL_HEAD_GRAPH=1 replays a back-end as two captured hipGraphs per feature shape (off by
 default: the HIP back-ends are a few dozen launches).
 Variable-length scoring batches (forward(x, lengths), eval mode under torch.no_grad()) for a back-end that declares `head_takes_frames`
-and whose `_head_forward(mod, feats, frames)` masks the padding itself (resnet_head.py; aasist_head.py behind SCL_AASIST_LENGTHS=1, whose
+and whose `_head_forward(mod, feats, frames)` masks the padding itself (resnet_head.py; btse_head.py; aasist_head.py behind SCL_AASIST_LENGTHS=1, whose
 fused kernels also bound an utterance's frames from above: head_max_frames / max_samples): the encoder runs with its padding mask on either
 scoring precision and either row layout, feats rows beyond an utterance's frames are zeroed, and the back-end gets the host-side frame counts.
 Variable-length TRAINING batches (train mode, autograd on) for a back-end that declares `head_trains_frames` besides: the autograd boundary

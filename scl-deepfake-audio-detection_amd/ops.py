@@ -952,6 +952,15 @@ def btse_bio_bwd(desc):
     return _call("scl_btse_bio_bwd", ctypes.byref(desc), _stream(), keep=desc)
 
 
+def btse_bio_fwd_own(desc):
+    """btse_bio_fwd with the read-out at every utterance's own last token (lens[b] - 1) instead of the last padded position."""
+    return _call("scl_btse_bio_fwd_own", ctypes.byref(desc), _stream(), keep=desc)
+
+
+def btse_bio_bwd_own(desc):
+    return _call("scl_btse_bio_bwd_own", ctypes.byref(desc), _stream(), keep=desc)
+
+
 def btse_join_fwd(emb, s, W1, b1, b, B, C, bio_out, is_add):
     _call("scl_btse_join_fwd", _p(emb), _p(s), _p(W1), _p(b1), _p(b), B, C, bio_out, int(is_add), _stream())
 
