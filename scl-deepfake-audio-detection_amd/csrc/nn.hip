@@ -107,18 +107,36 @@ __device__ __forceinline__ void slab_reduce4(long long e0, long long e1, int C, 
     }
 }
 
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int N, int C, double* __restrict__ part, int slab_rows) {
-    const int slab = blockIdx.x;
-    const long long e0 = (long long)slab * slab_rows * C, e1 = min((long long)(slab + 1) * slab_rows, (long long)N) * C;
-    if (C >= 4) {
-        slab_reduce4(e0, e1, C, part, slab, [&](long long e, int, float4& u, float4& v) {
-            u = *reinterpret_cast<const float4*>(x + e);
-            v = make_float4(u.x * u.x, u.y * u.y, u.z * u.z, u.w * u.w);
-        });
-        return;
+// The two pairs of terms the statistics kernels sum, each written once for the fixed-length and the masked kernels, 16 bytes wide
+// (slab_reduce4) and scalar (slab_reduce).  Forward: (x, x * x).
+struct BnFwdTerms {
+    const float* __restrict__ x;
+    __device__ __forceinline__ void operator()(long long e, int, float4& u, float4& v) const {
+        u = *reinterpret_cast<const float4*>(x + e);
+        v = make_float4(u.x * u.x, u.y * u.y, u.z * u.z, u.w * u.w);
     }
-    slab_reduce(e0, e1, C, part, slab, [&](long long e, int, float& u, float& v) { const float a = x[e]; u = a; v = a * a; });
-}
+    __device__ __forceinline__ void operator()(long long e, int, float& u, float& v) const { const float a = x[e]; u = a; v = a * a; }
+};
+// Backward: (dz, dz * xhat) with dz = dy * act'(y); y is not read without an activation
+struct BnBwdTerms {
+    const float* __restrict__ dy; const float* __restrict__ y; const float* __restrict__ x;
+    const float* __restrict__ mean; const float* __restrict__ rstd;
+    int act;
+    __device__ __forceinline__ void operator()(long long e, int c, float4& u, float4& v) const {
+        float4 dz = *reinterpret_cast<const float4*>(dy + e);
+        if (act) {
+            const float4 yv = *reinterpret_cast<const float4*>(y + e);
+            dz.x *= nn_act_grad_from_y(act, yv.x); dz.y *= nn_act_grad_from_y(act, yv.y); dz.z *= nn_act_grad_from_y(act, yv.z); dz.w *= nn_act_grad_from_y(act, yv.w);
+        }
+        const float4 xv = *reinterpret_cast<const float4*>(x + e), mv = *reinterpret_cast<const float4*>(mean + c), rv = *reinterpret_cast<const float4*>(rstd + c);
+        u = dz;
+        v = make_float4(dz.x * (xv.x - mv.x) * rv.x, dz.y * (xv.y - mv.y) * rv.y, dz.z * (xv.z - mv.z) * rv.z, dz.w * (xv.w - mv.w) * rv.w);
+    }
+    __device__ __forceinline__ void operator()(long long e, int c, float& u, float& v) const {
+        const float dz = dy[e] * (act ? nn_act_grad_from_y(act, y[e]) : 1.f);
+        u = dz; v = dz * (x[e] - mean[c]) * rstd[c];
+    }
+};
 
 // mean / rstd from the slab partials (training) or from the running statistics (eval); training also updates the running
 // statistics with momentum (unbiased variance, as torch) and num_batches_tracked
@@ -193,19 +211,28 @@ __device__ __forceinline__ void masked_slab(const int* __restrict__ valid, int H
     e1 = min((long long)(blockIdx.x + 1) * slab_rows, rows) * C;
     slot = b * gridDim.x + blockIdx.x;
 }
-__global__ __launch_bounds__(256) void bn_stats_masked_kernel(const float* __restrict__ x, const int* __restrict__ valid, int H, int W, int C,
-                                                              double* __restrict__ part, int slab_rows) {
-    long long base, e0, e1; int slot;
-    masked_slab(valid, H, W, C, slab_rows, base, e0, e1, slot);
-    const float* __restrict__ xb = x + base;
-    if (C >= 4) {
-        slab_reduce4(e0, e1, C, part, slot, [&](long long e, int, float4& u, float4& v) {
-            u = *reinterpret_cast<const float4*>(xb + e);
-            v = make_float4(u.x * u.x, u.y * u.y, u.z * u.z, u.w * u.w);
-        });
-        return;
+// A statistics block's slab: MASKED from masked_slab, else slab blockIdx.x of the flat map of N rows (base 0, the last slab ragged)
+template <bool MASKED>
+__device__ __forceinline__ void bn_slab(const int* __restrict__ valid, int N, int H, int W, int C, int slab_rows, long long& base, long long& e0,
+                                        long long& e1, int& slot) {
+    if constexpr (MASKED) {
+        masked_slab(valid, H, W, C, slab_rows, base, e0, e1, slot);
+    } else {
+        base = 0; slot = blockIdx.x;
+        e0 = (long long)slot * slab_rows * C; e1 = min((long long)(slot + 1) * slab_rows, (long long)N) * C;
     }
-    slab_reduce(e0, e1, C, part, slot, [&](long long e, int, float& u, float& v) { const float a = xb[e]; u = a; v = a * a; });
+}
+template <class F>
+__device__ __forceinline__ void slab_sums(long long e0, long long e1, int C, double* part, int slot, F f) {
+    if (C >= 4) slab_reduce4(e0, e1, C, part, slot, f); else slab_reduce(e0, e1, C, part, slot, f);
+}
+// per slab and channel (sum x, sum x * x).  The fixed-length launch passes N, the masked one valid, H, W.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, const int* __restrict__ valid, int N, int H, int W, int C,
+                                                       double* __restrict__ part, int slab_rows) {
+    long long base, e0, e1; int slot;
+    bn_slab<MASKED>(valid, N, H, W, C, slab_rows, base, e0, e1, slot);
+    slab_sums(e0, e1, C, part, slot, BnFwdTerms{x + base});
 }
 // bn_finish_kernel in training mode with N = N_v counted here from `valid`
 __global__ __launch_bounds__(1024) void bn_finish_masked_kernel(const double* __restrict__ part, int nslab, const int* __restrict__ valid, int B, int H, int W,
@@ -291,32 +318,20 @@ __global__ __launch_bounds__(256) void bn_apply_masked_kernel(const float* __res
     }
 }
 
-// backward, pass 1: per slab and channel (sum dz, sum dz * xhat) with dz = dy * act'(y)
+// backward, pass 1: per slab and channel (sum dz, sum dz * xhat) on bn_stats_kernel's partition - the masked form's slabs end at the
+// utterance's last valid row, so dy, y and x of the padding are not loaded
+template <bool MASKED>
 __global__ __launch_bounds__(256) void bn_bwd_stats_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x,
-                                                           const float* __restrict__ mean, const float* __restrict__ rstd, int N, int C, int act,
+                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                           const int* __restrict__ valid, int N, int H, int W, int C, int act,
                                                            double* __restrict__ part, int slab_rows) {
-    const int slab = blockIdx.x;
-    const long long e0 = (long long)slab * slab_rows * C, e1 = min((long long)(slab + 1) * slab_rows, (long long)N) * C;
-    if (C >= 4) {
-        slab_reduce4(e0, e1, C, part, slab, [&](long long e, int c, float4& u, float4& v) {
-            float4 dz = *reinterpret_cast<const float4*>(dy + e);
-            if (act) {
-                const float4 yv = *reinterpret_cast<const float4*>(y + e);
-                dz.x *= nn_act_grad_from_y(act, yv.x); dz.y *= nn_act_grad_from_y(act, yv.y); dz.z *= nn_act_grad_from_y(act, yv.z); dz.w *= nn_act_grad_from_y(act, yv.w);
-            }
-            const float4 xv = *reinterpret_cast<const float4*>(x + e), mv = *reinterpret_cast<const float4*>(mean + c), rv = *reinterpret_cast<const float4*>(rstd + c);
-            u = dz;
-            v = make_float4(dz.x * (xv.x - mv.x) * rv.x, dz.y * (xv.y - mv.y) * rv.y, dz.z * (xv.z - mv.z) * rv.z, dz.w * (xv.w - mv.w) * rv.w);
-        });
-        return;
-    }
-    slab_reduce(e0, e1, C, part, slab, [&](long long e, int c, float& u, float& v) {
-        const float dz = dy[e] * (act ? nn_act_grad_from_y(act, y[e]) : 1.f);
-        u = dz; v = dz * (x[e] - mean[c]) * rstd[c];
-    });
+    long long base, e0, e1; int slot;
+    bn_slab<MASKED>(valid, N, H, W, C, slab_rows, base, e0, e1, slot);
+    slab_sums(e0, e1, C, part, slot, BnBwdTerms{dy + base, y ? y + base : nullptr, x + base, mean, rstd, act});
 }
-__global__ __launch_bounds__(1024) void bn_bwd_finish_kernel(const double* __restrict__ part, int nslab, int C, float* __restrict__ dgamma,
-                                                            float* __restrict__ dbeta, float* __restrict__ sums, int accumulate) {
+// dgamma / dbeta (stored or added) and the two sums the apply kernels subtract, from the slab partials: bn_finish_body's 64 x 16 walk
+__device__ __forceinline__ void bn_bwd_finish_body(const double* __restrict__ part, int nslab, int C, float* __restrict__ dgamma,
+                                                   float* __restrict__ dbeta, float* __restrict__ sums, int accumulate) {
     __shared__ double red[2][16][64];
     const int cl = threadIdx.x & 63, lane4 = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + cl;
@@ -332,7 +347,23 @@ __global__ __launch_bounds__(1024) void bn_bwd_finish_kernel(const double* __res
     if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)q : (float)q;
     sums[c] = (float)s; sums[C + c] = (float)q;
 }
+__global__ __launch_bounds__(1024) void bn_bwd_finish_kernel(const double* __restrict__ part, int nslab, int C, float* __restrict__ dgamma,
+                                                            float* __restrict__ dbeta, float* __restrict__ sums, int accumulate) {
+    bn_bwd_finish_body(part, nslab, C, dgamma, dbeta, sums, accumulate);
+}
+// the same, plus 1 / N_v (counted from `valid` as in the forward) in sums[2 * C] for the masked apply kernel
+__global__ __launch_bounds__(1024) void bn_bwd_finish_masked_kernel(const double* __restrict__ part, int nslab, const int* __restrict__ valid, int B, int H,
+                                                                   int W, int C, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                   float* __restrict__ sums, int accumulate) {
+    const long long N = valid_positions(valid, B, H, W);
+    bn_bwd_finish_body(part, nslab, C, dgamma, dbeta, sums, accumulate);
+    if (blockIdx.x == 0 && threadIdx.x == 0) sums[2 * C] = 1.0f / (float)N;
+}
+
 // pass 2: dx = gamma * rstd * (dz - [training] (sum dz + xhat * sum dz*xhat) / N)
+// Unlike pass 1, this formula is still written in both apply kernels.  The compiler contracts it differently in the two: here dz is rounded
+// and then takes the fused subtraction, fma(-1/N, s, dz); the masked kernel has no eval mode and fuses the other product, fma(dy, act', -s/N).
+// They differ in the last place, so one expression for both changes the bits of one of them (tools/backend_body_probe.py --digest shows it).
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                            const float* __restrict__ sums, long long n, int N, int C, int act, int training,
@@ -373,56 +404,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     }
 }
 
-// The backward over the valid rows only.  Pass 1: bn_bwd_stats_kernel's sums on the partition of bn_stats_masked_kernel - a slab ends at the
-// utterance's last valid row, so dy, y and x of the padding are not loaded.
-__global__ __launch_bounds__(256) void bn_bwd_stats_masked_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x,
-                                                                  const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                  const int* __restrict__ valid, int H, int W, int C, int act,
-                                                                  double* __restrict__ part, int slab_rows) {
-    long long base, e0, e1; int slot;
-    masked_slab(valid, H, W, C, slab_rows, base, e0, e1, slot);
-    const float* __restrict__ dyb = dy + base;
-    const float* __restrict__ yb = y ? y + base : nullptr;
-    const float* __restrict__ xb = x + base;
-    if (C >= 4) {
-        slab_reduce4(e0, e1, C, part, slot, [&](long long e, int c, float4& u, float4& v) {
-            float4 dz = *reinterpret_cast<const float4*>(dyb + e);
-            if (act) {
-                const float4 yv = *reinterpret_cast<const float4*>(yb + e);
-                dz.x *= nn_act_grad_from_y(act, yv.x); dz.y *= nn_act_grad_from_y(act, yv.y); dz.z *= nn_act_grad_from_y(act, yv.z); dz.w *= nn_act_grad_from_y(act, yv.w);
-            }
-            const float4 xv = *reinterpret_cast<const float4*>(xb + e), mv = *reinterpret_cast<const float4*>(mean + c), rv = *reinterpret_cast<const float4*>(rstd + c);
-            u = dz;
-            v = make_float4(dz.x * (xv.x - mv.x) * rv.x, dz.y * (xv.y - mv.y) * rv.y, dz.z * (xv.z - mv.z) * rv.z, dz.w * (xv.w - mv.w) * rv.w);
-        });
-        return;
-    }
-    slab_reduce(e0, e1, C, part, slot, [&](long long e, int c, float& u, float& v) {
-        const float dz = dyb[e] * (act ? nn_act_grad_from_y(act, yb[e]) : 1.f);
-        u = dz; v = dz * (xb[e] - mean[c]) * rstd[c];
-    });
-}
-// bn_bwd_finish_kernel, plus 1 / N_v (counted from `valid` as in the forward) in sums[2 * C] for the apply kernel
-__global__ __launch_bounds__(1024) void bn_bwd_finish_masked_kernel(const double* __restrict__ part, int nslab, const int* __restrict__ valid, int B, int H,
-                                                                   int W, int C, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                   float* __restrict__ sums, int accumulate) {
-    __shared__ double red[2][16][64];
-    const long long N = valid_positions(valid, B, H, W);
-    const int cl = threadIdx.x & 63, lane4 = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    double s = 0.0, q = 0.0;
-    if (c < C)
-        for (int k = lane4; k < nslab; k += 16) { s += part[((long long)k * 2) * C + c]; q += part[((long long)k * 2 + 1) * C + c]; }
-    red[0][lane4][cl] = s; red[1][lane4][cl] = q;
-    __syncthreads();
-    if (lane4 != 0 || c >= C) return;
-    s = 0.0; q = 0.0;
-    for (int k = 0; k < 16; ++k) { s += red[0][k][cl]; q += red[1][k][cl]; }
-    if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)s : (float)s;
-    if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)q : (float)q;
-    sums[c] = (float)s; sums[C + c] = (float)q;
-    if (c == 0) sums[2 * C] = 1.0f / (float)N;
-}
 // pass 2: bn_bwd_apply_kernel's training expression on the rows h < valid[b], exactly 0 beyond - selected by ROW, never by y == 0 (SELU's
 // derivative at y == 0 is scale * alpha, not 0); dy, y and x of the padding are not read.  The launch shape of bn_apply_masked_kernel.
 __global__ __launch_bounds__(256) void bn_bwd_apply_masked_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x,
@@ -527,26 +508,25 @@ __global__ __launch_bounds__(256) void maxpool3_bwd_kernel(const float* __restri
 }
 
 // y[b][c] = mean_r x[b][r][c]   /   dx[b][r][c] = dy[b][c] / R
-__global__ __launch_bounds__(256) void avgpool_fwd_kernel(const float* __restrict__ x, int R, int C, float* __restrict__ y) {
-    const int b = blockIdx.x;
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float s = 0.f;
-        for (int r = 0; r < R; ++r) s += x[((long long)b * R + r) * C + c];
-        y[(long long)b * C + c] = s / (float)R;
-    }
-}
-// y[b][c] = mean over the rows r < valid[b] * W of x[b] ([B][H*W][C], utterance b owns its first valid[b] * W rows): avgpool_fwd_kernel's
-// summation order and division for the utterance's slice alone, so the bits are those of that slice pooled on its own.  Rows beyond are not read.
-__global__ __launch_bounds__(256) void avgpool_fwd_masked_kernel(const float* __restrict__ x, const int* __restrict__ valid, int H, int W, int C,
-                                                                 float* __restrict__ y) {
-    const int b = blockIdx.x;
-    const int R = valid_rows(valid, b, H) * W;
-    const float* __restrict__ xb = x + (long long)b * H * W * C;
+// one utterance: yb[c] = mean of the first R rows of xb, summed in row order.  EMPTY_OK: an utterance without rows averages to 0
+template <bool EMPTY_OK>
+__device__ __forceinline__ void avgpool_fwd_body(const float* __restrict__ xb, int R, int C, float* __restrict__ yb) {
     for (int c = threadIdx.x; c < C; c += 256) {
         float s = 0.f;
         for (int r = 0; r < R; ++r) s += xb[(long long)r * C + c];
-        y[(long long)b * C + c] = R > 0 ? s / (float)R : 0.f;
+        yb[c] = !EMPTY_OK || R > 0 ? s / (float)R : 0.f;
     }
+}
+__global__ __launch_bounds__(256) void avgpool_fwd_kernel(const float* __restrict__ x, int R, int C, float* __restrict__ y) {
+    const int b = blockIdx.x;
+    avgpool_fwd_body<false>(x + (long long)b * R * C, R, C, y + (long long)b * C);
+}
+// y[b][c] = mean over the rows r < valid[b] * W of x[b] ([B][H*W][C], utterance b owns its first valid[b] * W rows): the same body on the
+// utterance's slice alone, so the bits are those of that slice pooled on its own.  Rows beyond are not read.
+__global__ __launch_bounds__(256) void avgpool_fwd_masked_kernel(const float* __restrict__ x, const int* __restrict__ valid, int H, int W, int C,
+                                                                 float* __restrict__ y) {
+    const int b = blockIdx.x;
+    avgpool_fwd_body<true>(x + (long long)b * H * W * C, valid_rows(valid, b, H) * W, C, y + (long long)b * C);
 }
 __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float* __restrict__ dy, int R, int C, long long n, float* __restrict__ dx) {
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
@@ -586,6 +566,35 @@ bool bn_channels_ok(int C) { return C >= 1 && (C == 512 || (C <= 256 && 256 % C 
 // takes, up to the 2048 channels of the bottleneck networks' last stage
 bool bn_eval_channels_ok(int C) { return C >= 1 && C <= 2048 && (C & (C - 1)) == 0; }
 
+// the launch shape of the masked apply kernels: blockIdx.y the utterance, the unmasked launch's block budget shared among them
+dim3 masked_grid(long long per, int B, int C) {
+    int gx = grid_for(per >> ((C & 3) == 0 ? 2 : 0));
+    const int cap = (8192 + B - 1) / B;
+    return dim3(gx > cap ? cap : gx, B);
+}
+bool any_valid_row(const int32_t* valid_host, int B) {
+    for (int b = 0; b < B; ++b)
+        if (valid_host[b] > 0) return true;
+    return false;
+}
+// What scl_bn_eval_masked / scl_bn_fwd_masked / scl_bn_bwd_masked (`who`) ask of their shapes and pointers.  Batch statistics (`part`
+// given) narrow the channel counts and index the B * H * W rows of the batch; al16 is the OR of the addresses the 16-byte path touches.
+int bn_masked_args_ok(const char* who, int B, int H, int W, int C, int act, const void* part, uintptr_t al16, const char* al16_names) {
+    const bool stats = part != nullptr;
+    if (stats) {
+        SCL_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && bn_channels_ok(C), "%s: need 1 <= B <= 65535, H, W >= 1, C dividing 256 or 512", who);
+        SCL_REQUIRE((long long)H * W * C < (1ll << 31) && (long long)B * H * W < (1ll << 31),
+                    "%s: H * W * C of one utterance and the B * H * W rows of the batch must stay below 2^31", who);
+    } else {
+        SCL_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && bn_eval_channels_ok(C), "%s: need 1 <= B <= 65535, H, W >= 1, C a power of two <= 2048", who);
+        SCL_REQUIRE((long long)H * W * C < (1ll << 31), "%s: H * W * C of one utterance must stay below 2^31", who);
+    }
+    SCL_REQUIRE(act >= 0 && act <= 2, "%s: act", who);
+    SCL_REQUIRE((C & 3) != 0 || (al16 & 15) == 0, "%s: C %% 4 == 0 takes 16-byte aligned %s", who, al16_names);
+    SCL_REQUIRE(!stats || ((uintptr_t)part & 7) == 0, "%s: part holds doubles (8-byte aligned)", who);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int scl_bn_nslabs(int N) { const int r = bn_slab_rows(N); return (N + r - 1) / r; }
@@ -600,7 +609,7 @@ extern "C" int scl_bn_fwd(const float* x, int N, int C, const float* gamma, cons
     SCL_REQUIRE(act >= 0 && act <= 2, "bn_fwd: act");
     hipStream_t s = (hipStream_t)stream;
     const int nslab = scl_bn_nslabs(N);
-    if (training) hipLaunchKernelGGL(bn_stats_kernel, dim3(nslab), dim3(256), 0, s, x, N, C, (double*)part, bn_slab_rows(N));
+    if (training) hipLaunchKernelGGL(bn_stats_kernel<false>, dim3(nslab), dim3(256), 0, s, x, (const int*)nullptr, N, 0, 0, C, (double*)part, bn_slab_rows(N));
     hipLaunchKernelGGL(bn_finish_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, (const double*)part, nslab, N, C, eps, momentum, training, running_mean, running_var,
                        num_batches_tracked, mean, rstd);
     const RowMap map = {m_W > 0 ? m_W : 1, m_HW > 0 ? m_HW : 1, m_bs, m_rs, m_cs, m_base};
@@ -613,35 +622,16 @@ extern "C" int scl_bn_eval_masked(const float* x, int B, int H, int W, int C, co
                                   const float* running_var, float eps, int act, const int32_t* valid, float* mean, float* rstd, float* y,
                                   void* stream) {
     SCL_REQUIRE(x && running_mean && running_var && valid && mean && rstd && y, "bn_eval_masked: null argument (running statistics: eval mode only)");
-    SCL_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && bn_eval_channels_ok(C), "bn_eval_masked: need 1 <= B <= 65535, H, W >= 1, C a power of two <= 2048");
-    SCL_REQUIRE((long long)H * W * C < (1ll << 31), "bn_eval_masked: H * W * C of one utterance must stay below 2^31");
-    SCL_REQUIRE(act >= 0 && act <= 2, "bn_eval_masked: act");
-    SCL_REQUIRE((C & 3) != 0 || ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0),
-                "bn_eval_masked: C % 4 == 0 takes 16-byte aligned x, y, mean, rstd, gamma, beta");
+    if (int rc = bn_masked_args_ok("bn_eval_masked", B, H, W, C, act, nullptr,
+                                   (uintptr_t)x | (uintptr_t)y | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)beta,
+                                   "x, y, mean, rstd, gamma, beta")) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(bn_finish_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, (const double*)nullptr, 0, 1, C, eps, 0.f, 0, const_cast<float*>(running_mean),
                        const_cast<float*>(running_var), (long long*)nullptr, mean, rstd);
     const long long per = (long long)H * W * C;
-    int gx = grid_for(per >> ((C & 3) == 0 ? 2 : 0));
-    const int cap = (8192 + B - 1) / B;          // the unmasked launch's block budget, shared among the utterances
-    if (gx > cap) gx = cap;
-    hipLaunchKernelGGL(bn_apply_masked_kernel, dim3(gx, B), dim3(256), 0, s, x, mean, rstd, gamma, beta, valid, per, W * C, H, C, act, y);
+    hipLaunchKernelGGL(bn_apply_masked_kernel, masked_grid(per, B, C), dim3(256), 0, s, x, mean, rstd, gamma, beta, valid, per, W * C, H, C, act, y);
     return scl_check_launch("scl_bn_eval_masked");
 }
-
-namespace {
-// the launch shape of the masked apply kernels: blockIdx.y the utterance, the unmasked launch's block budget shared among them
-dim3 masked_grid(long long per, int B, int C) {
-    int gx = grid_for(per >> ((C & 3) == 0 ? 2 : 0));
-    const int cap = (8192 + B - 1) / B;
-    return dim3(gx > cap ? cap : gx, B);
-}
-bool any_valid_row(const int32_t* valid_host, int B) {
-    for (int b = 0; b < B; ++b)
-        if (valid_host[b] > 0) return true;
-    return false;
-}
-}  // namespace
 
 extern "C" int scl_bn_masked_nslabs(int B, int H, int W) {
     if (B < 1 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31)) return 0;
@@ -653,17 +643,13 @@ extern "C" int scl_bn_fwd_masked(const float* x, int B, int H, int W, int C, con
                                  float* running_var, long long* num_batches_tracked, float momentum, float eps, int act, const int32_t* valid,
                                  const int32_t* valid_host, float* part, float* mean, float* rstd, float* y, void* stream) {
     SCL_REQUIRE(x && valid && valid_host && part && mean && rstd && y, "bn_fwd_masked: null argument");
-    SCL_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && bn_channels_ok(C), "bn_fwd_masked: need 1 <= B <= 65535, H, W >= 1, C dividing 256 or 512");
-    SCL_REQUIRE((long long)H * W * C < (1ll << 31) && (long long)B * H * W < (1ll << 31),
-                "bn_fwd_masked: H * W * C of one utterance and the B * H * W rows of the batch must stay below 2^31");
-    SCL_REQUIRE(act >= 0 && act <= 2, "bn_fwd_masked: act");
-    SCL_REQUIRE((C & 3) != 0 || ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0),
-                "bn_fwd_masked: C % 4 == 0 takes 16-byte aligned x, y, mean, rstd, gamma, beta");
-    SCL_REQUIRE(((uintptr_t)part & 7) == 0, "bn_fwd_masked: part holds doubles (8-byte aligned)");
+    if (int rc = bn_masked_args_ok("bn_fwd_masked", B, H, W, C, act, part,
+                                   (uintptr_t)x | (uintptr_t)y | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)beta,
+                                   "x, y, mean, rstd, gamma, beta")) return rc;
     SCL_REQUIRE(any_valid_row(valid_host, B), "bn_fwd_masked: no valid position (every valid[b] is 0): batch statistics over nothing");
     hipStream_t s = (hipStream_t)stream;
     const int slab_rows = bn_slab_rows(B * H * W), nslab = scl_bn_masked_nslabs(B, H, W);
-    hipLaunchKernelGGL(bn_stats_masked_kernel, dim3(nslab / B, B), dim3(256), 0, s, x, valid, H, W, C, (double*)part, slab_rows);
+    hipLaunchKernelGGL(bn_stats_kernel<true>, dim3(nslab / B, B), dim3(256), 0, s, x, valid, 0, H, W, C, (double*)part, slab_rows);
     hipLaunchKernelGGL(bn_finish_masked_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, (const double*)part, nslab, valid, B, H, W, C, eps, momentum,
                        running_mean, running_var, num_batches_tracked, mean, rstd);
     const long long per = (long long)H * W * C;
@@ -675,18 +661,14 @@ extern "C" int scl_bn_bwd_masked(const float* dy, const float* y, const float* x
                                  int H, int W, int C, int act, const int32_t* valid, const int32_t* valid_host, float* part, float* sums,
                                  float* dgamma, float* dbeta, float* dx, int accumulate, void* stream) {
     SCL_REQUIRE(dy && x && mean && rstd && valid && valid_host && part && sums && dx, "bn_bwd_masked: null argument");
-    SCL_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && bn_channels_ok(C), "bn_bwd_masked: need 1 <= B <= 65535, H, W >= 1, C dividing 256 or 512");
-    SCL_REQUIRE((long long)H * W * C < (1ll << 31) && (long long)B * H * W < (1ll << 31),
-                "bn_bwd_masked: H * W * C of one utterance and the B * H * W rows of the batch must stay below 2^31");
-    SCL_REQUIRE(act >= 0 && act <= 2, "bn_bwd_masked: act");
+    if (int rc = bn_masked_args_ok("bn_bwd_masked", B, H, W, C, act, part,
+                                   (uintptr_t)dy | (uintptr_t)y | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma,
+                                   "dy, y, x, dx, mean, rstd, gamma")) return rc;
     SCL_REQUIRE(act == 0 || y, "bn_bwd_masked: the activation gradient needs the forward output y");
-    SCL_REQUIRE((C & 3) != 0 || ((((uintptr_t)dy | (uintptr_t)y | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma) & 15) == 0),
-                "bn_bwd_masked: C % 4 == 0 takes 16-byte aligned dy, y, x, dx, mean, rstd, gamma");
-    SCL_REQUIRE(((uintptr_t)part & 7) == 0, "bn_bwd_masked: part holds doubles (8-byte aligned)");
     SCL_REQUIRE(any_valid_row(valid_host, B), "bn_bwd_masked: no valid position (every valid[b] is 0)");
     hipStream_t s = (hipStream_t)stream;
     const int slab_rows = bn_slab_rows(B * H * W), nslab = scl_bn_masked_nslabs(B, H, W);
-    hipLaunchKernelGGL(bn_bwd_stats_masked_kernel, dim3(nslab / B, B), dim3(256), 0, s, dy, y, x, mean, rstd, valid, H, W, C, act, (double*)part, slab_rows);
+    hipLaunchKernelGGL(bn_bwd_stats_kernel<true>, dim3(nslab / B, B), dim3(256), 0, s, dy, y, x, mean, rstd, valid, 0, H, W, C, act, (double*)part, slab_rows);
     hipLaunchKernelGGL(bn_bwd_finish_masked_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, (const double*)part, nslab, valid, B, H, W, C, dgamma, dbeta, sums,
                        accumulate);
     const long long per = (long long)H * W * C;
@@ -701,7 +683,8 @@ extern "C" int scl_bn_bwd(const float* dy, const float* y, const float* x, const
     SCL_REQUIRE(act == 0 || y, "bn_bwd: the activation gradient needs the forward output y");
     hipStream_t s = (hipStream_t)stream;
     const int nslab = scl_bn_nslabs(N);
-    hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(nslab), dim3(256), 0, s, dy, y, x, mean, rstd, N, C, act, (double*)part, bn_slab_rows(N));
+    hipLaunchKernelGGL(bn_bwd_stats_kernel<false>, dim3(nslab), dim3(256), 0, s, dy, y, x, mean, rstd, (const int*)nullptr, N, 0, 0, C, act, (double*)part,
+                       bn_slab_rows(N));
     hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, (const double*)part, nslab, C, dgamma, dbeta, sums, accumulate);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for((long long)N * C)), dim3(256), 0, s, dy, y, x, mean, rstd, gamma, sums, (long long)N * C, N, C,
                        act, training, dx);

@@ -37,45 +37,31 @@ constexpr int RS_MAX_SPAN = 96; // largest halo (W + 3 positions) the register p
 
 struct RsGeom { int G, Wp, RPU, W, r_lo, r_hi; unsigned m_wp, m_rpu; };      // m_*: ceil(65536 / x), exact quotients for dividends < 65536 / x
 
-__device__ __forceinline__ bool rs_valid(const RsGeom& q, unsigned g) {
+// Variable-width batches (the VW forms, scoring): utterance b owns the columns 1..wt[b] of its rows (wt: int32 [B] on the device, clamped
+// to the geometry's W); everything beyond is padding — selected to zero, never multiplied.
+__device__ __forceinline__ int rs_width(const RsGeom& q, const int* __restrict__ wt, unsigned b) { const int w = wt[b]; return w < q.W ? w : q.W; }
+
+// is position g an interior position of its utterance (VW: within the utterance's own width)?
+template <bool VW>
+__device__ __forceinline__ bool rs_valid(const RsGeom& q, const int* __restrict__ wt, unsigned g) {
     if (g >= (unsigned)q.G) return false;
     const unsigned row = g / (unsigned)q.Wp;
     const int c = (int)(g - row * (unsigned)q.Wp);
     const int r = (int)(row % (unsigned)q.RPU);
-    return r >= q.r_lo && r <= q.r_hi && c >= 1 && c <= q.W;
+    return r >= q.r_lo && r <= q.r_hi && c >= 1 && c <= (VW ? rs_width(q, wt, row / (unsigned)q.RPU) : q.W);
 }
 
-// The same test for position g0 + pos of a tile whose first position sits at (row0 % RPU, col0): two 16-bit magic divisions of small
-// numbers instead of two 32-bit integer divisions per position (they were most of the epilogue's instructions).
-__device__ __forceinline__ bool rs_valid_rel(const RsGeom& q, unsigned rr0, unsigned col0, unsigned pos) {
+// The same test for position g0 + pos < G of a tile whose first position sits at (row0 = b0 * RPU + rr0, col0): two 16-bit magic divisions
+// of small numbers instead of two 32-bit integer divisions per position (they were most of the epilogue's instructions).
+template <bool VW>
+__device__ __forceinline__ bool rs_valid_rel(const RsGeom& q, const int* __restrict__ wt, unsigned b0, unsigned rr0, unsigned col0, unsigned pos) {
     const unsigned x = col0 + pos;                        // < Wp + 256
     const unsigned dq = (x * q.m_wp) >> 16;               // x / Wp
     const int c = (int)(x - dq * (unsigned)q.Wp);
     const unsigned y = rr0 + dq;                          // < RPU + 256 / Wp + 1
-    const int r = (int)(y - ((y * q.m_rpu) >> 16) * (unsigned)q.RPU);
-    return r >= q.r_lo && r <= q.r_hi && c >= 1 && c <= q.W;
-}
-
-// Variable-width batches (scoring): utterance b owns the columns 1..wt[b] of its rows (wt: int32 [B] on the device, clamped to the
-// geometry's W); everything beyond is padding — selected to zero, never multiplied.
-__device__ __forceinline__ int rs_width(const RsGeom& q, const int* __restrict__ wt, unsigned b) { const int w = wt[b]; return w < q.W ? w : q.W; }
-__device__ __forceinline__ bool rs_valid_w(const RsGeom& q, const int* __restrict__ wt, unsigned g) {
-    if (g >= (unsigned)q.G) return false;
-    const unsigned row = g / (unsigned)q.Wp;
-    const int c = (int)(g - row * (unsigned)q.Wp);
-    const unsigned b = row / (unsigned)q.RPU;
-    const int r = (int)(row - b * (unsigned)q.RPU);
-    return r >= q.r_lo && r <= q.r_hi && c >= 1 && c <= rs_width(q, wt, b);
-}
-// rs_valid_rel for a position g0 + pos < G of a tile whose first row is row0 = b0 * RPU + rr0
-__device__ __forceinline__ bool rs_valid_rel_w(const RsGeom& q, const int* __restrict__ wt, unsigned b0, unsigned rr0, unsigned col0, unsigned pos) {
-    const unsigned x = col0 + pos;
-    const unsigned dq = (x * q.m_wp) >> 16;
-    const int c = (int)(x - dq * (unsigned)q.Wp);
-    const unsigned y = rr0 + dq;
-    const unsigned by = (y * q.m_rpu) >> 16;
+    const unsigned by = (y * q.m_rpu) >> 16;              // y / RPU
     const int r = (int)(y - by * (unsigned)q.RPU);
-    return r >= q.r_lo && r <= q.r_hi && c >= 1 && c <= rs_width(q, wt, b0 + by);
+    return r >= q.r_lo && r <= q.r_hi && c >= 1 && c <= (VW ? rs_width(q, wt, b0 + by) : q.W);
 }
 
 struct RsConvK {
@@ -212,7 +198,7 @@ __global__ __launch_bounds__(256, (CIN >= 64 ? 1 : 2)) void rs_conv_kernel(const
                 const int pos = (tid + 256 * (p0 + u)) / N4;
                 const unsigned g = (unsigned)(g0 + pos);
                 if (g >= (unsigned)d.q.G) continue;
-                const bool ok = VW ? rs_valid_rel_w(d.q, d.wtab, row0 / (unsigned)d.q.RPU, rr0, col0, (unsigned)pos) : rs_valid_rel(d.q, rr0, col0, (unsigned)pos);
+                const bool ok = rs_valid_rel<VW>(d.q, d.wtab, row0 / (unsigned)d.q.RPU, rr0, col0, (unsigned)pos);
                 f32x4 v = *reinterpret_cast<const f32x4*>(lds + pos * OPITCH + 4 * ch4);
                 v += bias4;
                 v += ad[u];
@@ -283,31 +269,16 @@ __global__ __launch_bounds__(256, (CIN >= 64 ? 1 : 2)) void rs_conv_kernel(const
 
 // ---- element-wise passes ---------------------------------------------------------------------------------------------------------------
 // a = selu((y - mean) * sc + beta) on the valid positions, 0 on the borders (they are conv2's zero padding)
-__global__ __launch_bounds__(256) void rs_bn_act_kernel(const float* __restrict__ y, const float* __restrict__ stats, float* __restrict__ a, int C, int act, RsGeom q) {
+template <bool VW>
+__global__ __launch_bounds__(256) void rs_bn_act_kernel(const float* __restrict__ y, const float* __restrict__ stats, float* __restrict__ a, int C, int act, RsGeom q,
+                                                        const int* __restrict__ wt) {
     const int c4n = C >> 2;
     const long long n4 = (long long)q.G * c4n;
     for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < n4; f += (long long)gridDim.x * 256) {
         const unsigned g = (unsigned)(f / c4n);
         const int c = (int)(f - (long long)g * c4n) * 4;
         f32x4 o = {0.f, 0.f, 0.f, 0.f};
-        if (rs_valid(q, g)) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(y + f * 4), mean = *reinterpret_cast<const f32x4*>(stats + c),
-                        sc = *reinterpret_cast<const f32x4*>(stats + 2 * C + c), be = *reinterpret_cast<const f32x4*>(stats + 3 * C + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float z = (v[e] - mean[e]) * sc[e] + be[e]; o[e] = act ? selu_f(z) : z; }
-        }
-        *reinterpret_cast<f32x4*>(a + f * 4) = o;
-    }
-}
-__global__ __launch_bounds__(256) void rs_bn_act_w_kernel(const float* __restrict__ y, const float* __restrict__ stats, float* __restrict__ a, int C, int act, RsGeom q,
-                                                          const int* __restrict__ wt) {
-    const int c4n = C >> 2;
-    const long long n4 = (long long)q.G * c4n;
-    for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < n4; f += (long long)gridDim.x * 256) {
-        const unsigned g = (unsigned)(f / c4n);
-        const int c = (int)(f - (long long)g * c4n) * 4;
-        f32x4 o = {0.f, 0.f, 0.f, 0.f};
-        if (rs_valid_w(q, wt, g)) {
+        if (rs_valid<VW>(q, wt, g)) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(y + f * 4), mean = *reinterpret_cast<const f32x4*>(stats + c),
                         sc = *reinterpret_cast<const f32x4*>(stats + 2 * C + c), be = *reinterpret_cast<const f32x4*>(stats + 3 * C + c);
 #pragma unroll
@@ -325,7 +296,7 @@ __global__ __launch_bounds__(256) void rs_bn_bwd_apply_kernel(float* __restrict_
         const unsigned g = (unsigned)(f / c4n);
         const int c = (int)(f - (long long)g * c4n) * 4;
         f32x4 o = {0.f, 0.f, 0.f, 0.f};
-        if (rs_valid(q, g)) {
+        if (rs_valid<false>(q, nullptr, g)) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(dz + f * 4), yy = *reinterpret_cast<const f32x4*>(y + f * 4);
             const f32x4 mean = *reinterpret_cast<const f32x4*>(stats + c), rstd = *reinterpret_cast<const f32x4*>(stats + C + c),
                         sc = *reinterpret_cast<const f32x4*>(stats + 2 * C + c);
@@ -350,18 +321,22 @@ __global__ void rs_bn_eval_stats_kernel(const float* gamma, const float* beta, c
 
 // ---- dense <-> bordered copies ------------------------------------------------------------------------------------------------------------
 // mode 0: dense [B*H*W, Cs] -> bordered [G, Cd] (channels >= Cs and borders zero);  mode 1: bordered [G, Cs] -> dense [B*H*W, Cd] (first Cd channels)
-__global__ __launch_bounds__(256) void rs_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, int Cs, int Cd, int H, int mode, RsGeom q) {
-    if (mode == 0) {
+// VW (mode 0 only): the dense rows are Ws <= W columns wide (Ws >= every width); columns beyond the utterance's width are written as zeros
+// and not read
+template <bool VW>
+__global__ __launch_bounds__(256) void rs_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, int Cs, int Cd, int H, int mode, RsGeom q,
+                                                      int Ws, const int* __restrict__ wt) {
+    if (VW || mode == 0) {
         const long long n = (long long)q.G * Cd;
         for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
             const unsigned g = (unsigned)(e / Cd);
             const int c = (int)(e - (long long)g * Cd);
             float v = 0.f;
-            if (c < Cs && rs_valid(q, g)) {
+            if (c < Cs && rs_valid<VW>(q, wt, g)) {
                 const unsigned row = g / (unsigned)q.Wp;
                 const unsigned b = row / (unsigned)q.RPU;
                 const int r = (int)(row - b * q.RPU), col = (int)(g - row * (unsigned)q.Wp);
-                v = src[(((long long)b * H + (r - q.r_lo)) * q.W + (col - 1)) * Cs + c];
+                if (!VW || col <= Ws) v = src[(((long long)b * H + (r - q.r_lo)) * (VW ? Ws : q.W) + (col - 1)) * Cs + c];
             }
             dst[e] = v;
         }
@@ -376,24 +351,6 @@ __global__ __launch_bounds__(256) void rs_copy_kernel(const float* __restrict__ 
             const int r = (int)(bh - b * H);
             dst[e] = src[(((b * q.RPU) + r + q.r_lo) * q.Wp + col + 1) * Cs + c];
         }
-    }
-}
-
-// dense [B * H * Ws, Cs] (Ws >= every width) -> bordered [G, Cd]: columns beyond the utterance's width are written as zeros and not read
-__global__ __launch_bounds__(256) void rs_copy_w_kernel(const float* __restrict__ src, float* __restrict__ dst, int Cs, int Cd, int H, int Ws, RsGeom q,
-                                                        const int* __restrict__ wt) {
-    const long long n = (long long)q.G * Cd;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
-        const unsigned g = (unsigned)(e / Cd);
-        const int c = (int)(e - (long long)g * Cd);
-        float v = 0.f;
-        if (c < Cs && rs_valid_w(q, wt, g)) {
-            const unsigned row = g / (unsigned)q.Wp;
-            const unsigned b = row / (unsigned)q.RPU;
-            const int r = (int)(row - b * q.RPU), col = (int)(g - row * (unsigned)q.Wp);
-            if (col <= Ws) v = src[(((long long)b * H + (r - q.r_lo)) * Ws + (col - 1)) * Cs + c];
-        }
-        dst[e] = v;
     }
 }
 
@@ -571,64 +528,35 @@ __global__ __launch_bounds__(256) void rs_wgrad_reduce_kernel(const float* __res
 // ---- attention pooling over the [H, W] map (model/wav2vec2_aasist.py:527-541): e_S[h][c] = sum_w x[h][w][c] softmax_w(l[h][.][c]) + pos_S[h][c],
 // e_T[w][c] = sum_h x[h][w][c] softmax_h(l[.][w][c]).  One block per (utterance, four channels): both maps' slices of that channel quad
 // sit in LDS ([H][W] float4 each), a thread owns whole rows (softmax over W) and then whole columns (softmax over H).
+// VW, utterances of different widths: block b pools over its columns 1..wt[b] alone (the soft-max over the time axis and both sums); the rows
+// of eT at and beyond the width are written as zeros.  Columns beyond the width are not read (the LDS rows keep their stride W).
+template <bool VW>
 __global__ __launch_bounds__(256) void rs_attn_pool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ l, const float* __restrict__ pos,
-                                                               float* __restrict__ eS, float* __restrict__ eT, int C, int H, int W, RsGeom q) {
+                                                               float* __restrict__ eS, float* __restrict__ eT, int C, int H, int W, RsGeom q,
+                                                               const int* __restrict__ wt) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     f32x4* LX = reinterpret_cast<f32x4*>(lds);
     f32x4* LL = LX + H * W;
     const int b = blockIdx.x, c4 = blockIdx.y, tid = threadIdx.x;
-    const size_t base = (size_t)b * q.RPU * q.Wp;
-    for (int e = tid; e < H * W; e += 256) {
-        const int h = e / W, w = e - h * W;
-        const size_t g = base + (size_t)(h + 1) * q.Wp + (w + 1);
-        LX[e] = *reinterpret_cast<const f32x4*>(x + g * C + 4 * c4);
-        LL[e] = *reinterpret_cast<const f32x4*>(l + g * C + 4 * c4);
-    }
-    __syncthreads();
-    for (int r = tid; r < H + W; r += 256) {
-        const bool row = r < H;
-        const int n = row ? W : H, i0 = row ? r * W : r - H, st = row ? 1 : W;
-        f32x4 mx = LL[i0];
-        for (int k = 1; k < n; ++k) { const f32x4 v = LL[i0 + k * st]; for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], v[e]); }
-        f32x4 den = {0.f, 0.f, 0.f, 0.f}, num = den;
-        for (int k = 0; k < n; ++k) {
-            const f32x4 v = LL[i0 + k * st], xv = LX[i0 + k * st];
-            for (int e = 0; e < 4; ++e) { const float p = __expf(v[e] - mx[e]); den[e] += p; num[e] = fmaf(p, xv[e], num[e]); }
-        }
-        f32x4 o;
-        for (int e = 0; e < 4; ++e) o[e] = num[e] / den[e];
-        if (row) {
-            if (pos) o += *reinterpret_cast<const f32x4*>(pos + (size_t)r * C + 4 * c4);
-            *reinterpret_cast<f32x4*>(eS + ((size_t)b * H + r) * C + 4 * c4) = o;
-        } else {
-            *reinterpret_cast<f32x4*>(eT + ((size_t)b * W + (r - H)) * C + 4 * c4) = o;
-        }
-    }
-}
-// The same for utterances of different widths: block b pools over its columns 1..wt[b] alone (the soft-max over the time axis and both sums);
-// the rows of eT at and beyond the width are written as zeros.  Columns beyond the width are not read.
-__global__ __launch_bounds__(256) void rs_attn_pool_fwd_w_kernel(const float* __restrict__ x, const float* __restrict__ l, const float* __restrict__ pos,
-                                                                 float* __restrict__ eS, float* __restrict__ eT, int C, int H, int W, RsGeom q,
-                                                                 const int* __restrict__ wt) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    f32x4* LX = reinterpret_cast<f32x4*>(lds);
-    f32x4* LL = LX + H * W;
-    const int b = blockIdx.x, c4 = blockIdx.y, tid = threadIdx.x;
-    int Wb = rs_width(q, wt, b);
-    Wb = Wb < 1 ? 1 : Wb;                    // uniform in the block
+    int Wb = W;                                  // the columns this block pools over: uniform in the block
+    if constexpr (VW) { Wb = rs_width(q, wt, b); Wb = Wb < 1 ? 1 : Wb; }
     const size_t base = (size_t)b * q.RPU * q.Wp;
     for (int e = tid; e < H * Wb; e += 256) {
         const int h = e / Wb, w = e - h * Wb;
         const size_t g = base + (size_t)(h + 1) * q.Wp + (w + 1);
-        LX[h * W + w] = *reinterpret_cast<const f32x4*>(x + g * C + 4 * c4);
-        LL[h * W + w] = *reinterpret_cast<const f32x4*>(l + g * C + 4 * c4);
+        int i = e;
+        if constexpr (VW) i = h * W + w;
+        LX[i] = *reinterpret_cast<const f32x4*>(x + g * C + 4 * c4);
+        LL[i] = *reinterpret_cast<const f32x4*>(l + g * C + 4 * c4);
     }
     __syncthreads();
     for (int r = tid; r < H + W; r += 256) {
         const bool row = r < H;
-        if (!row && r - H >= Wb) {
-            *reinterpret_cast<f32x4*>(eT + ((size_t)b * W + (r - H)) * C + 4 * c4) = f32x4{0.f, 0.f, 0.f, 0.f};
-            continue;
+        if constexpr (VW) {
+            if (!row && r - H >= Wb) {
+                *reinterpret_cast<f32x4*>(eT + ((size_t)b * W + (r - H)) * C + 4 * c4) = f32x4{0.f, 0.f, 0.f, 0.f};
+                continue;
+            }
         }
         const int n = row ? Wb : H, i0 = row ? r * W : r - H, st = row ? 1 : W;
         f32x4 mx = LL[i0];
@@ -884,7 +812,7 @@ extern "C" int scl_rs_bn_act(const float* y, const float* stats, float* a, int C
     RsGeom q;
     if (!rs_fill_geom(*geom, &q)) return SCL_EINVAL;
     const long long n4 = (long long)q.G * (C / 4);
-    hipLaunchKernelGGL(rs_bn_act_kernel, dim3((unsigned)((n4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, y, stats, a, C, act, q);
+    hipLaunchKernelGGL(rs_bn_act_kernel<false>, dim3((unsigned)((n4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, y, stats, a, C, act, q, (const int*)nullptr);
     return scl_check_launch("rs_bn_act");
 }
 
@@ -895,7 +823,7 @@ extern "C" int scl_rs_bn_act_w(const float* y, const float* stats, float* a, int
     RsGeom q;
     if (!rs_fill_geom(*geom, &q)) return SCL_EINVAL;
     const long long n4 = (long long)q.G * (C / 4);
-    hipLaunchKernelGGL(rs_bn_act_w_kernel, dim3((unsigned)((n4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, y, stats, a, C, act, q, widths);
+    hipLaunchKernelGGL(rs_bn_act_kernel<true>, dim3((unsigned)((n4 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, y, stats, a, C, act, q, widths);
     return scl_check_launch("scl_rs_bn_act_w");
 }
 
@@ -922,7 +850,8 @@ extern "C" int scl_rs_copy(const float* src, float* dst, int Cs, int Cd, int to_
     if (!rs_fill_geom(*geom, &q)) return SCL_EINVAL;
     const int H = geom->r_hi - geom->r_lo + 1;
     const long long n = to_dense ? (long long)geom->B * H * q.W * Cd : (long long)q.G * Cd;
-    hipLaunchKernelGGL(rs_copy_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, src, dst, Cs, Cd, H, to_dense ? 1 : 0, q);
+    hipLaunchKernelGGL(rs_copy_kernel<false>, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, src, dst, Cs, Cd, H, to_dense ? 1 : 0, q, 0,
+                       (const int*)nullptr);
     return scl_check_launch("rs_copy");
 }
 
@@ -932,8 +861,9 @@ extern "C" int scl_rs_attn_pool_fwd(const float* x, const float* l, const float*
     if (!rs_fill_geom(*geom, &q)) return SCL_EINVAL;
     const size_t lds = (size_t)2 * geom->H * geom->W * 16;
     SCL_REQUIRE(lds <= 160 * 1024, "rs_attn_pool_fwd: map of %d x %d positions exceeds the LDS", geom->H, geom->W);
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)rs_attn_pool_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(rs_attn_pool_fwd_kernel, dim3(geom->B, C / 4), dim3(256), lds, (hipStream_t)stream, x, l, pos, eS, eT, C, geom->H, geom->W, q);
+    if (lds > 65536) (void)hipFuncSetAttribute((const void*)rs_attn_pool_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(rs_attn_pool_fwd_kernel<false>, dim3(geom->B, C / 4), dim3(256), lds, (hipStream_t)stream, x, l, pos, eS, eT, C, geom->H, geom->W, q,
+                       (const int*)nullptr);
     return scl_check_launch("rs_attn_pool_fwd");
 }
 extern "C" int scl_rs_copy_w(const float* src, float* dst, int Cs, int Cd, int src_w, const SclRsGeom* geom, const int32_t* widths, void* stream) {
@@ -944,7 +874,7 @@ extern "C" int scl_rs_copy_w(const float* src, float* dst, int Cs, int Cd, int s
     if (!rs_fill_geom(*geom, &q)) return SCL_EINVAL;
     const int H = geom->r_hi - geom->r_lo + 1;
     const long long n = (long long)q.G * Cd;
-    hipLaunchKernelGGL(rs_copy_w_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, src, dst, Cs, Cd, H, src_w, q, widths);
+    hipLaunchKernelGGL(rs_copy_kernel<true>, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, src, dst, Cs, Cd, H, 0, q, src_w, widths);
     return scl_check_launch("scl_rs_copy_w");
 }
 
@@ -957,8 +887,8 @@ extern "C" int scl_rs_attn_pool_fwd_w(const float* x, const float* l, const floa
     if (!rs_fill_geom(*geom, &q)) return SCL_EINVAL;
     const size_t lds = (size_t)2 * geom->H * geom->W * 16;
     SCL_REQUIRE(lds <= 160 * 1024, "scl_rs_attn_pool_fwd_w: map of %d x %d positions exceeds the LDS", geom->H, geom->W);
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)rs_attn_pool_fwd_w_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(rs_attn_pool_fwd_w_kernel, dim3(geom->B, C / 4), dim3(256), lds, (hipStream_t)stream, x, l, pos, eS, eT, C, geom->H, geom->W, q, widths);
+    if (lds > 65536) (void)hipFuncSetAttribute((const void*)rs_attn_pool_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(rs_attn_pool_fwd_kernel<true>, dim3(geom->B, C / 4), dim3(256), lds, (hipStream_t)stream, x, l, pos, eS, eT, C, geom->H, geom->W, q, widths);
     return scl_check_launch("scl_rs_attn_pool_fwd_w");
 }
 

@@ -249,6 +249,17 @@ def conv2d(x, weight, bias=None, stride=(1, 1), padding=(0, 0), dtype=torch.floa
 
 
 # ---- BatchNorm (+ activation) --------------------------------------------------------------------------------------------------------
+def _bn_param_grads(ctx, C, dev, has_w, has_b):
+    """Where a BatchNorm backward's finishing kernel puts dgamma / dbeta: (dg, db, accumulate).  accumulate: both parameters carry an
+    attached, contiguous f32 .grad (the plugins' flat gradient buffer) and nothing is being captured - the kernel adds into them (what
+    AccumulateGrad would do with two more launches) and autograd gets no parameter gradient back.  Otherwise fresh buffers to hand back."""
+    if ctx.in_place is not None and has_w and has_b and not torch.cuda.is_current_stream_capturing():
+        gw, gb = ctx.in_place[0].grad, ctx.in_place[1].grad
+        if all(g is not None and g.dtype == torch.float32 and g.is_contiguous() for g in (gw, gb)):
+            return gw, gb, True
+    return (torch.empty(C, device=dev) if has_w else None), (torch.empty(C, device=dev) if has_b else None), False
+
+
 class _BatchNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, nbt, training, momentum, eps, act, grad_in_place=False):
@@ -274,17 +285,9 @@ class _BatchNormFn(torch.autograd.Function):
         part = torch.empty(ops.bn_nslabs(N) * 2 * C, dtype=torch.float64, device=dev)
         sums = torch.empty(2 * C, device=dev)
         dx = torch.empty_like(xc)
-        if ctx.in_place is not None and has_w and has_b and not torch.cuda.is_current_stream_capturing():
-            # both parameters carry an attached, contiguous f32 .grad (the plugins' flat gradient buffer): the finishing kernel adds into
-            # them (what AccumulateGrad would do with two more launches) and autograd gets no parameter gradient back
-            gw, gb = ctx.in_place[0].grad, ctx.in_place[1].grad
-            if all(g is not None and g.dtype == torch.float32 and g.is_contiguous() for g in (gw, gb)):
-                ops.bn_bwd(dyc, y, xc, mean, rstd, weight, N, C, act, training, part, sums, gw, gb, dx, accumulate=True)
-                return dx, None, None, None, None, None, None, None, None, None, None
-        dg = torch.empty(C, device=dev) if has_w else None
-        db = torch.empty(C, device=dev) if has_b else None
-        ops.bn_bwd(dyc, y, xc, mean, rstd, weight, N, C, act, training, part, sums, dg, db, dx)
-        return dx, dg, db, None, None, None, None, None, None, None, None
+        dg, db, acc = _bn_param_grads(ctx, C, dev, has_w, has_b)
+        ops.bn_bwd(dyc, y, xc, mean, rstd, weight, N, C, act, training, part, sums, dg, db, dx, accumulate=acc)
+        return (dx,) + ((None, None) if acc else (dg, db)) + (None,) * 8
 
 
 class _BatchNormMaskedFn(torch.autograd.Function):
@@ -313,16 +316,9 @@ class _BatchNormMaskedFn(torch.autograd.Function):
         part = torch.empty(ops.bn_masked_nslabs(B, H, W) * 2 * C, dtype=torch.float64, device=dev)
         sums = torch.empty(2 * C + 4, device=dev)
         dx = torch.empty_like(xc)
-        none = (None,) * 9
-        if ctx.in_place is not None and has_w and has_b and not torch.cuda.is_current_stream_capturing():
-            gw, gb = ctx.in_place[0].grad, ctx.in_place[1].grad      # as _BatchNormFn.backward: the finishing kernel adds into attached .grad views
-            if all(g is not None and g.dtype == torch.float32 and g.is_contiguous() for g in (gw, gb)):
-                ops.bn_bwd_masked(dyc, y, xc, mean, rstd, weight, B, H, W, C, act, valid, counts, part, sums, gw, gb, dx, accumulate=True)
-                return (dx, None, None) + none
-        dg = torch.empty(C, device=dev) if has_w else None
-        db = torch.empty(C, device=dev) if has_b else None
-        ops.bn_bwd_masked(dyc, y, xc, mean, rstd, weight, B, H, W, C, act, valid, counts, part, sums, dg, db, dx)
-        return (dx, dg, db) + none
+        dg, db, acc = _bn_param_grads(ctx, C, dev, has_w, has_b)
+        ops.bn_bwd_masked(dyc, y, xc, mean, rstd, weight, B, H, W, C, act, valid, counts, part, sums, dg, db, dx, accumulate=acc)
+        return (dx,) + ((None, None) if acc else (dg, db)) + (None,) * 9
 
 
 def batch_norm(x, bn, act=ACT_NONE, grad_in_place=False, valid=None, counts=None):
