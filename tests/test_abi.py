@@ -1,6 +1,8 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads without a GPU and exports every
-symbol declared in include/scl_hip.h; the ctypes table and the header agree; argument validation
-returns error codes instead of crashing; the product path refuses to run without a GPU (no fallback)."""
+symbol declared in include/scl_hip.h; the ctypes table and the header list the same NAMES (names only: the table's argument
+types are written by hand and are not compared with the declarations; struct field order and flag constants:
+tests/test_abi_header_cpu.py); argument validation returns error codes instead of crashing; the product path refuses to
+run without a GPU (no fallback)."""
 import ctypes
 import os
 import re
