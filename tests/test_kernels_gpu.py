@@ -176,6 +176,47 @@ def test_pad_rows_col2im_weight_packs(dev):
     assert torch.equal(dw, dwk.view(Co, k, Ci).permute(0, 2, 1))
 
 
+@pytest.mark.parametrize("Co,Ci,k,stride", [(16, 8, 3, 2), (16, 8, 2, 2), (8, 8, 10, 5), (8, 16, 3, 1), (8, 8, 4, 3)])
+def test_conv_weight_pack_backward_data_operand(dev, Co, Ci, k, stride):
+    """wd of conv_weight_pack, the right operand of every data-gradient GEMM of the conv stack: [k tap blocks][co][ci], phases ascending,
+    descending tap inside a phase — bit-equal to a reference built by index; and the phase-split product over its blocks,
+    dz[s u + p] = sum_q dy[u - q] W[p + s q], equals conv_transpose1d with the bf16-rounded weight in fp64."""
+    w = torch.randn(Co, Ci, k, generator=g(11))
+    wk = torch.full((Co, k * Ci), float("nan"), dtype=torch.bfloat16, device=dev)
+    wd = torch.full((k, Co, Ci), float("nan"), dtype=torch.bfloat16, device=dev)
+    ops.conv_weight_pack(w.to(dev), wk, Co, Ci, k, wd=wd, stride=stride)
+    wb = w.to(torch.bfloat16)
+    ref_wk = torch.empty(Co, k * Ci, dtype=torch.bfloat16)
+    for j in range(k):
+        ref_wk[:, j * Ci:(j + 1) * Ci] = wb[:, :, j]
+    assert torch.equal(wk.cpu(), ref_wk)
+    taps = [j for p in range(stride) for j in sorted(range(p, k, stride), reverse=True)]
+    assert sorted(taps) == list(range(k))
+    ref_wd = torch.stack([wb[:, :, j] for j in taps])
+    assert torch.equal(wd.cpu(), ref_wd)
+    # functional: one product per output phase over wd's blocks, as the encoder launches them
+    wd64 = wd.cpu().double()
+    for Tin in (4 * k + 1, 4 * k + 2, 4 * k + stride + 3):
+        Tout = (Tin - k) // stride + 1
+        dy = torch.randn(2, Tout, Co, generator=g(12), dtype=torch.float64)
+        dz = torch.full((2, Tin, Ci), float("nan"), dtype=torch.float64)
+        blk = 0
+        for p in range(stride):
+            nq = len(range(p, k, stride))
+            for u in range((Tin - 1 - p) // stride + 1):
+                acc = torch.zeros(2, Ci, dtype=torch.float64)
+                for i in range(nq):      # the GEMM row [dy[u - (nq - 1)] .. dy[u]] against blocks blk .. blk + nq - 1
+                    t = u - (nq - 1) + i
+                    if 0 <= t < Tout:
+                        acc += dy[:, t] @ wd64[blk + i]
+                dz[:, stride * u + p] = acc
+            blk += nq
+        assert blk == k
+        ref = F.conv_transpose1d(dy.transpose(1, 2), wb.double(), stride=stride).transpose(1, 2)
+        ref = torch.cat([ref, torch.zeros(2, Tin - ref.shape[1], Ci, dtype=torch.float64)], dim=1)      # left-over input frames
+        assert (dz - ref).abs().max() <= 1e-12 * ref.abs().max()
+
+
 @pytest.mark.parametrize("E,G,K", [(32, 4, 8), (64, 4, 16), (1024, 16, 128)])
 def test_posconv_weight_norm_pack_and_bwd(dev, E, G, K):
     Cg = E // G
