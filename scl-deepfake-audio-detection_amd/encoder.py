@@ -1136,6 +1136,8 @@ class Encoder:
                       self.b(fe % 0 + "2.1.bias"), d["dz"][0], d["conv0_ws"], P.g(self.n(fe % 0 + "0.weight")),
                       P.g(self.n(fe % 0 + "0.bias")), P.g(self.n(fe % 0 + "2.1.weight")), P.g(self.n(fe % 0 + "2.1.bias")),
                       B, L, C, cfg.conv_kernels[0], cfg.conv_strides[0], stats=d["conv0_stats"])
+        # names for d(xin[0]) and d(x0) (references to the f32 buffers the backward ended in: nothing behind the positional conv writes them)
+        d["dxin0"], d["dx0"] = dx, dx0
         return slots
 
     def _qkv_view(self, pn, kind):
