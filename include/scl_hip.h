@@ -407,8 +407,11 @@ int scl_attn_fwd(const void* qkv, void* ctx, float* lse, int B, int T, int H, in
 int scl_attn_fwd_fp8(const void* qkv, void* ctx, float* lse, int B, int T, int H, int D, float scale, void* stream);
 int scl_attn_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, float* bias_part, int B, int T,
                  int H, int D, float scale, float drop_p, uint32_t drop_seed, void* stream);
-/* Streaming attention for head dim 64 and any T >= 1 (csrc/attention_long.hip; kernel bodies in csrc/attn_stream_body.h, shared with the
- * _varlen and _packed entry points below): K / V blocks of 64 keys through LDS, online fp32
+/* Streaming attention for any T >= 1 and head dim D = 64 (csrc/attention_long.hip; kernel bodies in csrc/attn_stream_body.h, shared with the
+ * _varlen and _packed entry points below) or D = 72..128 in steps of 8 (csrc/attention_wide.hip: the same bodies on a head dim padded to
+ * 96 or 128 in registers and LDS, csrc/attn_wide_body.h; in memory a head stays D columns wide and nothing beyond column D of a head is
+ * read or written).  Every streaming entry below dispatches on D likewise and refuses any other D with SCL_EINVAL ("needs head dim 64,
+ * or 72..128 in steps of 8"); scl_attn_fwd_packed_f32 takes 64 only.  K / V blocks of 64 keys through LDS, online fp32
  * soft-max; no T x T buffer.  Same operands, layouts, dropout mask index and outputs as scl_attn_fwd / scl_attn_bwd (row r = (b, h, q) of
  * lse and of the mask).  The encoder's path above 512 frames (and 225-512 with SCL_ATTN_LONG=1).
  * bwd: P recomputed from lse, delta = rowsum(dO o O) into ws (scl_attn_long_ws_bytes(B, T, H) bytes); dK / dV per block of 128 keys,
@@ -436,8 +439,8 @@ int scl_attn_fwd_varlen_drop(const void* qkv, void* ctx, float* lse, const int32
 /* scl_attn_bwd_long with per-utterance key counts: delta, dK / dV per block of 128 keys, dQ per block of 64 queries, no atomics, bitwise
  * reproducible.  Query tiles and key blocks run to klen[b]; a block that starts at or beyond klen[b] writes zeros and leaves at once.  EVERY
  * row of dqkv [B, T, 3, H, 64] is written: rows >= klen[b] are exactly 0, and those rows of qkv / ctx / dctx / lse are never read (they may
- * hold NaN).  With drop_p = 0, rows < klen[b] carry the bits scl_attn_bwd_long gives for that utterance alone at T = klen[b].  Head dim 64
- * only; ws: scl_attn_long_ws_bytes(B, T, H) bytes. */
+ * hold NaN).  With drop_p = 0, rows < klen[b] carry the bits scl_attn_bwd_long gives for that utterance alone at T = klen[b].  Head dims
+ * as scl_attn_fwd_long (dqkv [B, T, 3, H, D]); ws: scl_attn_long_ws_bytes(B, T, H) bytes. */
 int scl_attn_bwd_varlen(const void* qkv, const void* ctx, const void* dctx, const float* lse, const int32_t* klen, void* dqkv, void* ws, int B,
                         int T, int H, int D, float scale, float drop_p, uint32_t drop_seed, void* stream);
 /* scl_softmax_fwd_f32 / _long over the first klen[r / rows_per_utt] columns of row r (R % rows_per_utt == 0; rows_per_utt = H * T for
@@ -468,7 +471,7 @@ int scl_meanpool_bwd_varlen_f32(const float* demb, const float* pre, float* dpre
  * scl_attn_fwd_packed / _drop: scl_attn_fwd_varlen / _drop on qkv [Mq, 3 H D] -> ctx [Mq, H D] with utterance b's rows at row0[b] instead of
  * b * T.  lse [B, H, T] and the dropout mask index ((b*H + h)*T + q)*T + k stay in the padded space: row row0[b] + t of ctx carries the bits
  * of row b * T + t of the padded kernel, and lse is the same array.  Nothing is stored into a row at or beyond an utterance's end (it is the
- * next utterance's); rows [Mv, Mq) of ctx are written as 0; rows >= Mq are not touched.  Head dim 64 only. */
+ * next utterance's); rows [Mv, Mq) of ctx are written as 0; rows >= Mq are not touched.  Head dims as scl_attn_fwd_long. */
 int scl_packed_check_rows(const int32_t* row0_host, int B, int T, int Mq);
 int scl_attn_fwd_packed(const void* qkv, void* ctx, float* lse, const int32_t* row0, int B, int T, int H, int D, int Mq, float scale,
                         void* stream);

@@ -2,10 +2,12 @@
 // the looped fp32 row soft-max of the fp32 scoring path.  The encoder routes here above the 512 frames the materialised-score path
 // (attention.hip: a whole score row in registers) accepts; nothing of size T^2 is written to memory.
 //
+// Head dim 64 is compiled here; the entries hand head dims 72..128 to attention_wide.hip (the same bodies with a padded head dim).
 // The forward, delta and dQ kernels are the bodies of attn_stream_body.h (the tile scheme, the operand layouts and the dropout mask index are
 // described there) with Rows::Fixed: utterance b at rows b*T, Tb = T, no length array.  attention_varlen.hip and attention_packed.hip hold
 // the same bodies for a zero-padded and a packed variable-length batch.  The dK / dV kernel has a body of its own here.
 #include "attn_stream_body.h"
+#include "attn_wide.h"      // head dims 72..128: attention_wide.hip
 
 namespace {
 
@@ -153,7 +155,9 @@ __global__ __launch_bounds__(256) void softmax_fwd_f32_long_kernel(const float* 
 extern "C" int scl_attn_fwd_long(const void* qkv, void* ctx, float* lse, int B, int T, int H, int D, float scale, float drop_p,
                                  uint32_t drop_seed, void* stream) {
     SCL_REQUIRE(qkv && ctx && lse && B > 0 && H > 0 && T >= 1 && drop_p >= 0.f && drop_p < 1.f, "attn_fwd_long: bad args");
-    SCL_REQUIRE(D == LD, "attn_fwd_long: needs head dim 64 (got D=%d)", D);
+    if (scl_attn_wide_takes(D))
+        return scl_attn_wide_fwd(SCL_ROWS_FIXED, "scl_attn_fwd_long", qkv, ctx, lse, nullptr, B, T, H, D, 0, scale, drop_p, drop_seed, stream);
+    SCL_REQUIRE(D == LD, "attn_fwd_long: " SCL_ATTN_HEAD_DIMS " (got D=%d)", D);
     const int nqb = (T + LQB - 1) / LQB;
     SCL_REQUIRE((int64_t)B * H * nqb < 0x7FFFFFFF, "attn_fwd_long: grid too large");
     const dim3 grid((unsigned)(B * H * nqb));
@@ -174,7 +178,10 @@ extern "C" long long scl_attn_long_ws_bytes(int B, int T, int H) {
 extern "C" int scl_attn_bwd_long(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, void* ws, int B, int T,
                                  int H, int D, float scale, float drop_p, uint32_t drop_seed, void* stream) {
     SCL_REQUIRE(qkv && ctx && dctx && lse && dqkv && ws && B > 0 && H > 0 && T >= 1 && drop_p >= 0.f && drop_p < 1.f, "attn_bwd_long: bad args");
-    SCL_REQUIRE(D == LD, "attn_bwd_long: needs head dim 64 (got D=%d)", D);
+    if (scl_attn_wide_takes(D))
+        return scl_attn_wide_bwd(SCL_ROWS_FIXED, "scl_attn_bwd_long", qkv, ctx, dctx, lse, nullptr, dqkv, ws, B, T, H, D, 0, scale, drop_p, drop_seed,
+                                 stream);
+    SCL_REQUIRE(D == LD, "attn_bwd_long: " SCL_ATTN_HEAD_DIMS " (got D=%d)", D);
     const int nqb = (T + LQB - 1) / LQB, nkw = (T + LKW - 1) / LKW;
     SCL_REQUIRE((int64_t)B * H * nqb < 0x7FFFFFFF, "attn_bwd_long: grid too large");
     hipStream_t s = (hipStream_t)stream;

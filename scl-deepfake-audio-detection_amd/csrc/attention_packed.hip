@@ -15,9 +15,11 @@
 //                                 belong to the next one.  Nothing is stored at or beyond Tb, and a 64-query / 128-key block that starts
 //                                 there returns before its first barrier without a store.  Rows [Mv, Mq) are written as zeros (ctx by the
 //                                 forward, dqkv by the backward): the gradients of rows that belong to nobody are exactly 0.
+// Head dim 64 is compiled here; the entries hand head dims 72..128 to attention_wide.hip (the same bodies with a padded head dim).
 //   scl_pack_rows                 dst[row0[b] + t] = src[b*T + t] for t < Tb; dst rows [Mv, Mq) = 0 (padded source rows are not read).
 //   scl_unpack_rows               dst[b*T + t] = t < Tb ? src[row0[b] + t] : 0.  Either way every row of the destination is written.
 #include "attn_stream_body.h"
+#include "attn_wide.h"      // head dims 72..128: attention_wide.hip
 
 namespace {
 
@@ -92,8 +94,10 @@ extern "C" int scl_packed_check_rows(const int32_t* row0_host, int B, int T, int
     return 0;
 }
 
-#define PACKED_ATTN_ARGS(name)                                                                                              \
-    SCL_REQUIRE(D == LD, name ": needs head dim 64 (got D=%d)", D);                                                         \
+// WIDE: the call that hands head dims 72..128 to attention_wide.hip (which checks Mq and the grid itself)
+#define PACKED_ATTN_ARGS(name, WIDE)                                                                                        \
+    if (scl_attn_wide_takes(D)) return WIDE;                                                                                \
+    SCL_REQUIRE(D == LD, name ": " SCL_ATTN_HEAD_DIMS " (got D=%d)", D);                                                    \
     SCL_REQUIRE(Mq >= B && (int64_t)Mq <= ((int64_t)B * T + 63) / 64 * 64, name ": need B <= Mq <= roundup(B * T, 64)");     \
     const int nqb = (T + LQB - 1) / LQB;                                                                                    \
     SCL_REQUIRE((int64_t)B * H * nqb < 0x7FFFFFFF, name ": grid too large")
@@ -101,7 +105,7 @@ extern "C" int scl_packed_check_rows(const int32_t* row0_host, int B, int T, int
 extern "C" int scl_attn_fwd_packed(const void* qkv, void* ctx, float* lse, const int32_t* row0, int B, int T, int H, int D, int Mq, float scale,
                                    void* stream) {
     SCL_REQUIRE(qkv && ctx && lse && row0 && B > 0 && H > 0 && T >= 1, "attn_fwd_packed: bad args");
-    PACKED_ATTN_ARGS("attn_fwd_packed");
+    PACKED_ATTN_ARGS("attn_fwd_packed", scl_attn_wide_fwd(SCL_ROWS_PACKED, "scl_attn_fwd_packed", qkv, ctx, lse, row0, B, T, H, D, Mq, scale, 0.f, 0u, stream));
     hipLaunchKernelGGL(attn_fwd_packed_kernel<false>, dim3((unsigned)(B * H * nqb)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv,
                        (bf16_t*)ctx, lse, (const int*)row0, T, H, nqb, B, Mq, scale, 0.f, 0u);
     return scl_check_launch("scl_attn_fwd_packed");
@@ -110,7 +114,8 @@ extern "C" int scl_attn_fwd_packed(const void* qkv, void* ctx, float* lse, const
 extern "C" int scl_attn_fwd_packed_drop(const void* qkv, void* ctx, float* lse, const int32_t* row0, int B, int T, int H, int D, int Mq, float scale,
                                         float drop_p, uint32_t drop_seed, void* stream) {
     SCL_REQUIRE(qkv && ctx && lse && row0 && B > 0 && H > 0 && T >= 1 && drop_p >= 0.f && drop_p < 1.f, "attn_fwd_packed_drop: bad args");
-    PACKED_ATTN_ARGS("attn_fwd_packed_drop");
+    PACKED_ATTN_ARGS("attn_fwd_packed_drop",
+                     scl_attn_wide_fwd(SCL_ROWS_PACKED, "scl_attn_fwd_packed_drop", qkv, ctx, lse, row0, B, T, H, D, Mq, scale, drop_p, drop_seed, stream));
     const dim3 grid((unsigned)(B * H * nqb));
     if (drop_p > 0.f)
         hipLaunchKernelGGL(attn_fwd_packed_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)ctx, lse,
@@ -126,7 +131,8 @@ extern "C" int scl_attn_bwd_packed(const void* qkv, const void* ctx, const void*
                                    int B, int T, int H, int D, int Mq, float scale, float drop_p, uint32_t drop_seed, void* stream) {
     SCL_REQUIRE(qkv && ctx && dctx && lse && row0 && dqkv && ws && B > 0 && H > 0 && T >= 1 && drop_p >= 0.f && drop_p < 1.f,
                 "attn_bwd_packed: bad args");
-    PACKED_ATTN_ARGS("attn_bwd_packed");
+    PACKED_ATTN_ARGS("attn_bwd_packed", scl_attn_wide_bwd(SCL_ROWS_PACKED, "scl_attn_bwd_packed", qkv, ctx, dctx, lse, row0, dqkv, ws, B, T, H, D, Mq,
+                                                          scale, drop_p, drop_seed, stream));
     const int nkw = (T + LKW - 1) / LKW;
     hipStream_t s = (hipStream_t)stream;
     float* delta = (float*)ws;

@@ -21,9 +21,11 @@
 //   scl_meanpool_bwd_varlen      scl_meanpool_bwd (activation derivative and head-dropout mask fused) scaled by 1 / len[b]; rows
 //                                t >= len[b] are written as 0.
 // The device-side counts are clamped to [1, T] for memory safety; scl_varlen_check_lengths validates the host copy before the upload.
-// The attention kernels are the bodies of attn_stream_body.h in the padded layout (Rows::Padded); attention_long.hip holds the same bodies
+// The attention kernels are the bodies of attn_stream_body.h in the padded layout (Rows::Padded), compiled here for head dim 64; the
+// entries hand head dims 72..128 to attention_wide.hip.  attention_long.hip holds the same bodies
 // for batches without a length array (Rows::Fixed) and attention_packed.hip for frames packed back to back (Rows::Packed).
 #include "attn_stream_body.h"
+#include "attn_wide.h"      // head dims 72..128: attention_wide.hip
 
 namespace {
 
@@ -163,7 +165,9 @@ extern "C" int scl_varlen_check_lengths(const int32_t* len_host, int B, int T) {
 extern "C" int scl_attn_fwd_varlen(const void* qkv, void* ctx, float* lse, const int32_t* klen, int B, int T, int H, int D, float scale,
                                    void* stream) {
     SCL_REQUIRE(qkv && ctx && lse && klen && B > 0 && H > 0 && T >= 1, "attn_fwd_varlen: bad args");
-    SCL_REQUIRE(D == LD, "attn_fwd_varlen: needs head dim 64 (got D=%d)", D);
+    if (scl_attn_wide_takes(D))
+        return scl_attn_wide_fwd(SCL_ROWS_PADDED, "scl_attn_fwd_varlen", qkv, ctx, lse, klen, B, T, H, D, 0, scale, 0.f, 0u, stream);
+    SCL_REQUIRE(D == LD, "attn_fwd_varlen: " SCL_ATTN_HEAD_DIMS " (got D=%d)", D);
     const int nqb = (T + LQB - 1) / LQB;
     SCL_REQUIRE((int64_t)B * H * nqb < 0x7FFFFFFF, "attn_fwd_varlen: grid too large");
     hipLaunchKernelGGL(attn_fwd_varlen_kernel<false>, dim3((unsigned)(B * H * nqb)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv,
@@ -174,7 +178,9 @@ extern "C" int scl_attn_fwd_varlen(const void* qkv, void* ctx, float* lse, const
 extern "C" int scl_attn_fwd_varlen_drop(const void* qkv, void* ctx, float* lse, const int32_t* klen, int B, int T, int H, int D, float scale,
                                         float drop_p, uint32_t drop_seed, void* stream) {
     SCL_REQUIRE(qkv && ctx && lse && klen && B > 0 && H > 0 && T >= 1 && drop_p >= 0.f && drop_p < 1.f, "attn_fwd_varlen_drop: bad args");
-    SCL_REQUIRE(D == LD, "attn_fwd_varlen_drop: needs head dim 64 (got D=%d)", D);
+    if (scl_attn_wide_takes(D))
+        return scl_attn_wide_fwd(SCL_ROWS_PADDED, "scl_attn_fwd_varlen_drop", qkv, ctx, lse, klen, B, T, H, D, 0, scale, drop_p, drop_seed, stream);
+    SCL_REQUIRE(D == LD, "attn_fwd_varlen_drop: " SCL_ATTN_HEAD_DIMS " (got D=%d)", D);
     const int nqb = (T + LQB - 1) / LQB;
     SCL_REQUIRE((int64_t)B * H * nqb < 0x7FFFFFFF, "attn_fwd_varlen_drop: grid too large");
     const dim3 grid((unsigned)(B * H * nqb));
@@ -192,7 +198,10 @@ extern "C" int scl_attn_bwd_varlen(const void* qkv, const void* ctx, const void*
                                    int B, int T, int H, int D, float scale, float drop_p, uint32_t drop_seed, void* stream) {
     SCL_REQUIRE(qkv && ctx && dctx && lse && klen && dqkv && ws && B > 0 && H > 0 && T >= 1 && drop_p >= 0.f && drop_p < 1.f,
                 "attn_bwd_varlen: bad args");
-    SCL_REQUIRE(D == LD, "attn_bwd_varlen: needs head dim 64 (got D=%d)", D);
+    if (scl_attn_wide_takes(D))
+        return scl_attn_wide_bwd(SCL_ROWS_PADDED, "scl_attn_bwd_varlen", qkv, ctx, dctx, lse, klen, dqkv, ws, B, T, H, D, 0, scale, drop_p, drop_seed,
+                                 stream);
+    SCL_REQUIRE(D == LD, "attn_bwd_varlen: " SCL_ATTN_HEAD_DIMS " (got D=%d)", D);
     const int nqb = (T + LQB - 1) / LQB, nkw = (T + LKW - 1) / LKW;
     SCL_REQUIRE((int64_t)B * H * nqb < 0x7FFFFFFF, "attn_bwd_varlen: grid too large");
     hipStream_t s = (hipStream_t)stream;

@@ -1,6 +1,10 @@
 // attn_stream_body.h — streaming ("flash") attention for head dim 64 and any clip length (T >= 1), forward and backward, as device-function
 // bodies shared by the three row layouts of a batch (everything is internal to the including file and force-inlined into its kernels).
 // Nothing of size T^2 is written to memory.
+// Head dims 72..128 (XLS-R 1B: 80, 2B: 120) run the same scheme on a head dim padded to 96 or 128 in registers and LDS: attn_wide_body.h,
+// compiled by attention_wide.hip, which takes Rows / UttRows / zero_tail_vectors and the block sizes from here.  The two sets of bodies are
+// kept textually apart (templated on the padded head dim, the kernels of head dim 64 compiled to another schedule): a change to the
+// tile scheme has to be made in both.
 //
 // Operands and outputs as scl_attn_fwd / scl_attn_bwd: qkv / dqkv bf16 [rows, 3, H, 64]; ctx / dctx bf16 [rows, H*64]; lse f32 [B, H, T]
 // = log sum_k exp(scale * q.k).  Attention dropout draws keep-mask hash(seed, ((b*H + h)*T + q)*T + k), the index of the fused kernels

@@ -12,6 +12,7 @@ Layout decisions (MI355X-first, not fairseq's):
   * every buffer is allocated once per (B, L) and reused across steps (no allocator traffic).
 """
 import collections
+import collections.abc
 import contextlib
 import os
 
@@ -31,8 +32,9 @@ WGRAD_GROUP_MIN_KSTEPS = 16      # from 1024 rows on (measured: 11 x 199 rows 16
 # BASELINE.json configs[4] names fp8 attention: csrc/attention_fp8.hip (e4m3 operands, fp32 accumulation) for the no-grad bf16 forward.  Opt-in:
 # the reference is fp32 and the fused forward is bound by its soft-max VALU work, not by the matrix pipe (profiles/r4_attn_fp8_probe.txt).
 ATTN_FP8 = os.environ.get("SCL_ATTN_FP8", "0") == "1"
-# Attention above 512 frames (64-wide heads): the streaming kernels of csrc/attention_long.hip, no T x T buffer.  SCL_ATTN_LONG=1 sends
-# 225-512 frames there too (same-box A/B against the materialised-score path, which stays the default there).
+# Attention above 512 frames: the streaming kernels of csrc/attention_long.hip (64-wide heads) and csrc/attention_wide.hip (72- to
+# 128-wide heads), no T x T buffer.  SCL_ATTN_LONG=1 sends 225-512 frames there too (same-box A/B against the materialised-score path,
+# which stays the default there).
 ATTN_LONG = os.environ.get("SCL_ATTN_LONG", "0") == "1"
 MAT_ATTN_MAX_T = 512      # the materialised path's soft-max keeps a whole score row in registers (csrc/attention.hip)
 # fp32 scoring path above 512 frames: utterances per chunk of the materialised f32 attention such that S (and Pm) stay within this many bytes
@@ -52,6 +54,14 @@ PACK_ROWS = 512
 # time; SCL_VARLEN_PACK does not reach the fp32 path.  64-wide heads only.
 SCORE_PACK = os.environ.get("SCL_SCORE_PACK", "0") == "1"
 
+
+def stream_attn_takes(head_dim):
+    """Whether the streaming attention kernels (fixed, zero-padded and packed rows, bf16) take this head dim: 64, or 72..128 in steps of 8
+    (XLS-R 300M: 64, 1B: 80, 2B: 120).  The fused on-chip kernels and the packed fp32 kernel take 64 only."""
+    return head_dim == 64 or (64 < head_dim <= 128 and head_dim % 8 == 0)
+
+
+STREAM_ATTN_HEAD_DIMS = "head dim 64, or 72..128 in steps of 8"
 
 VARLEN_SETS = 4      # buffer sets kept per path for variable-length scoring batches (every distinct padded shape is a set of its own)
 
@@ -191,6 +201,16 @@ class W2VConfig:
         return W2VConfig(conv_dim=32, embed=64, layers=2, heads=4, ffn=128, pos_k=16, pos_groups=4, final_dim=16,
                          latent_vars=8, latent_groups=2)
 
+    @staticmethod
+    def xlsr_1b(**kw):
+        """XLS-R 1B as fairseq publishes its config (80-wide heads); the conv stack and the positional convolution of the 300M model."""
+        return W2VConfig(embed=1280, layers=48, heads=16, ffn=5120, final_dim=1024, **kw)
+
+    @staticmethod
+    def xlsr_2b(**kw):
+        """XLS-R 2B as fairseq publishes its config (120-wide heads); the conv stack and the positional convolution of the 300M model."""
+        return W2VConfig(embed=1920, layers=48, heads=16, ffn=7680, final_dim=1024, **kw)
+
     def conv_lens(self, L):
         out = []
         for k, s in zip(self.conv_kernels, self.conv_strides):
@@ -208,6 +228,28 @@ class W2VConfig:
     def min_samples(self):
         """The shortest clip that yields one frame (400 samples for the XLS-R stack)."""
         return self.samples_for(1)
+
+
+W2V_ARCHS = {"xlsr_300m": W2VConfig, "xlsr_1b": W2VConfig.xlsr_1b, "xlsr_2b": W2VConfig.xlsr_2b, "tiny": lambda **kw: W2VConfig.tiny()}
+
+
+def w2v_config_from(args):
+    """The encoder a YAML names (needs no GPU).  `w2v_arch`: one of W2V_ARCHS ("xlsr_300m" when absent: the reference's only encoder;
+    "tiny" for tests and plumbing), or a mapping of W2VConfig fields such as {embed: 1280, layers: 48, heads: 16, ffn: 5120, final_dim: 1024}
+    (fields left out keep the 300M model's values).  `encoder_layerdrop` of the YAML applies to every arch but "tiny"."""
+    arch = args.get("w2v_arch", "xlsr_300m")
+    layerdrop = float(args.get("encoder_layerdrop", 0.0))
+    if isinstance(arch, collections.abc.Mapping):
+        fields = dict(arch)
+        fields.setdefault("encoder_layerdrop", layerdrop)
+        try:
+            return W2VConfig(**fields)
+        except TypeError as e:
+            raise ValueError("w2v_arch: %s; the fields are those of W2VConfig" % e) from None
+    if arch not in W2V_ARCHS:
+        raise ValueError("w2v_arch: unknown encoder %r; the names are %s, or give a mapping of W2VConfig fields"
+                         % (arch, ", ".join(sorted(W2V_ARCHS))))
+    return W2V_ARCHS[arch](encoder_layerdrop=layerdrop)
 
 
 def param_specs(cfg, prefix="ssl_model.model."):
@@ -381,16 +423,16 @@ class Encoder:
         d["m1"], d["r1"] = [f32(Mr) for _ in range(cfg.layers)], [f32(Mr) for _ in range(cfg.layers)]
         d["qkv"] = [bf(Mr * 3 * E + slack) for _ in range(cfg.layers)]
         d["fused_attn"] = (E // H == 64) and T <= 224      # scores stay on chip (csrc/attention.hip); else materialised path
-        # streaming attention (csrc/attention_long.hip): above 512 frames, or from 225 frames with SCL_ATTN_LONG=1
-        d["long_attn"] = (E // H == 64) and not d["fused_attn"] and (T > MAT_ATTN_MAX_T or ATTN_LONG)
+        # streaming attention (csrc/attention_long.hip, csrc/attention_wide.hip): above 512 frames, or from 225 frames with SCL_ATTN_LONG=1
+        d["long_attn"] = stream_attn_takes(E // H) and not d["fused_attn"] and (T > MAT_ATTN_MAX_T or ATTN_LONG)
         if varlen:
-            if E // H != 64:
-                raise SclError("encoder: variable-length batches on the bf16 path run the streaming attention, which takes head dim 64 "
-                               "(got %d); the fp32 scoring path takes any head dim" % (E // H))
+            if not stream_attn_takes(E // H):
+                raise SclError("encoder: variable-length batches on the bf16 path run the streaming attention, which takes %s "
+                               "(got %d); the fp32 scoring path takes any head dim" % (STREAM_ATTN_HEAD_DIMS, E // H))
             d["fused_attn"], d["long_attn"] = False, True
         if T > MAT_ATTN_MAX_T and not d["long_attn"]:
-            raise SclError("encoder: %d frames need the streaming attention, which takes head dim 64 (got %d); other head dims are limited "
-                           "to %d frames (%d samples)" % (T, E // H, MAT_ATTN_MAX_T, L))
+            raise SclError("encoder: %d frames need the streaming attention, which takes %s (got %d); other head dims are limited "
+                           "to %d frames (%d samples)" % (T, STREAM_ATTN_HEAD_DIMS, E // H, MAT_ATTN_MAX_T, L))
         if d["fused_attn"] or d["long_attn"]:
             d["lse"] = [f32(B * H * T) for _ in range(cfg.layers)]
         if d["long_attn"]:

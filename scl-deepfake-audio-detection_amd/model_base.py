@@ -9,7 +9,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .encoder import Encoder, RowLayout, VarlenSets, W2VConfig, shape_entry
+from .encoder import Encoder, RowLayout, VarlenSets, shape_entry, w2v_config_from
 from .params import FlatParams
 
 HEAD_DIM = 128
@@ -95,11 +95,9 @@ class FlatModel(nn.Module):
         if self.device.type != "cuda":
             raise RuntimeError("scl_amd.Model needs an MI355X device: the product path has no CPU fallback")
         self.is_train = is_train
-        if w2v_cfg is None:
-            # optional YAML key `w2v_arch`: "xlsr_300m" (default, the reference's only encoder) or "tiny" (tests / plumbing)
-            w2v_cfg = W2VConfig.tiny() if args.get("w2v_arch", "xlsr_300m") == "tiny" else \
-                W2VConfig(encoder_layerdrop=float(args.get("encoder_layerdrop", 0.0)))
-        self.cfg = w2v_cfg
+        # optional YAML key `w2v_arch`: a name ("xlsr_300m", the default and the reference's only encoder; "xlsr_1b", "xlsr_2b"; "tiny") or
+        # a mapping of W2VConfig fields (encoder.w2v_config_from)
+        self.cfg = w2v_config_from(args) if w2v_cfg is None else w2v_cfg
 
     def _make_params(self, specs):
         """Once the parameter specs are known: the flat buffer.  The sub-class then registers its views under the reference's names and puts

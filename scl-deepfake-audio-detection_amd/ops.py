@@ -493,7 +493,8 @@ def softmax_fwd_f32_long(S, P, R, T, ldS, Tp):
 
 
 def attn_fwd_long(qkv, ctx, lse, B, T, H, D, scale, drop_p=0.0, drop_seed=0):
-    """Streaming attention forward (head dim 64, any T): the operands and outputs of attn_fwd."""
+    """Streaming attention forward (head dim 64, or 72..128 in steps of 8; any T): the operands and outputs of attn_fwd.  The same head
+    dims hold for attn_bwd_long and for the _varlen and _packed entries (not for attn_fwd_packed_f32: 64 only)."""
     return _call("scl_attn_fwd_long", _p(qkv), _p(ctx), _p(lse), B, T, H, D, float(scale), float(drop_p), int(drop_seed), _stream())
 
 
