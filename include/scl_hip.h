@@ -411,7 +411,7 @@ int scl_attn_bwd(const void* qkv, const void* ctx, const void* dctx, const float
  * _varlen and _packed entry points below) or D = 72..128 in steps of 8 (csrc/attention_wide.hip: the same bodies on a head dim padded to
  * 96 or 128 in registers and LDS, csrc/attn_wide_body.h; in memory a head stays D columns wide and nothing beyond column D of a head is
  * read or written).  Every streaming entry below dispatches on D likewise and refuses any other D with SCL_EINVAL ("needs head dim 64,
- * or 72..128 in steps of 8"); scl_attn_fwd_packed_f32 takes 64 only.  K / V blocks of 64 keys through LDS, online fp32
+ * or 72..128 in steps of 8"), scl_attn_fwd_packed_f32 included (csrc/attention_f32_wide.hip).  K / V blocks of 64 keys through LDS, online fp32
  * soft-max; no T x T buffer.  Same operands, layouts, dropout mask index and outputs as scl_attn_fwd / scl_attn_bwd (row r = (b, h, q) of
  * lse and of the mask).  The encoder's path above 512 frames (and 225-512 with SCL_ATTN_LONG=1).
  * bwd: P recomputed from lse, delta = rowsum(dO o O) into ws (scl_attn_long_ws_bytes(B, T, H) bytes); dK / dV per block of 128 keys,
@@ -493,7 +493,9 @@ int scl_unpack_rows(const void* src, void* dst, int is_f32, const int32_t* row0,
  * cores: every operand (Q, K, V and the exponentials) is the pair hi = bf16(x), lo = bf16(x - hi) and every product hi hi + hi lo + lo hi
  * with f32 accumulation — always the pair form, whatever SCL_GEMM_F32X3 the caller's GEMMs carry.  Deterministic; an utterance gets the
  * bits it gets alone.  Nothing is loaded from or stored into a row at or beyond an utterance's end; rows [Mv, Mq) of ctx are written as
- * 0; rows >= Mq are not touched.  Head dim 64 only; qkv and ctx 16-byte aligned. */
+ * 0; rows >= Mq are not touched.  Head dim 64, or 72..128 in steps of 8 (csrc/attention_f32_wide.hip: the same scheme on a head dim padded
+ * to 96 or 128 in registers and LDS, K / V blocks of 32 keys; in memory a head stays D floats wide and nothing beyond column D of a head
+ * is read or written); any other D is refused with SCL_EINVAL.  qkv and ctx 16-byte aligned. */
 int scl_attn_fwd_packed_f32(const float* qkv, float* ctx, const int32_t* row0, int B, int T, int H, int D, int Mq, float scale,
                             void* stream);
 

@@ -1,7 +1,8 @@
 // attention_f32.hip — streaming attention with fp32 accuracy over packed valid frames: the scoring path's attention (Encoder.forward_f32
 // with packed=(row0, Mq)) without a T x T score buffer and without the padded rows.
 //
-//   scl_attn_fwd_packed_f32   qkv f32 [Mq, 3, H, 64] -> ctx f32 [Mq, H*64]; utterance b owns rows row0[b] .. row0[b + 1] - 1 (row0 int32
+//   scl_attn_fwd_packed_f32   qkv f32 [Mq, 3, H, 64] -> ctx f32 [Mq, H*64] (head dims 72..128 in steps of 8: the entry hands them to
+//                             attention_f32_wide.hip, the same scheme on a padded head dim); utterance b owns rows row0[b] .. row0[b + 1] - 1 (row0 int32
 //                             [B + 1] on the device, the layout of attention_packed.hip: Tb and the first row are clamped as UttRows<Rows::Packed>
 //                             does, Mv = row0[B] is read on the device).  Forward only: no lse, no dropout.
 //
@@ -22,6 +23,7 @@
 // THE STORES are those of the bf16 packed forward: no row at or beyond an utterance's end is loaded or stored, a query block that starts
 // beyond Tb leaves before its first barrier, rows [Mv, Mq) of ctx are written as zeros by every launch, rows >= Mq are never touched.
 #include "attn_stream_body.h"
+#include "attn_wide.h"      // head dims 72..128: scl_attn_wide_fwd_f32 (attention_f32_wide.hip)
 
 namespace {
 
@@ -189,12 +191,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_packed_f32_kernel(const float
 extern "C" int scl_attn_fwd_packed_f32(const float* qkv, float* ctx, const int32_t* row0, int B, int T, int H, int D, int Mq, float scale,
                                        void* stream) {
     SCL_REQUIRE(qkv && ctx && row0 && B > 0 && H > 0 && T >= 1, "attn_fwd_packed_f32: bad args");
-    SCL_REQUIRE(D == LD, "attn_fwd_packed_f32: needs head dim 64 (got D=%d)", D);
+    SCL_REQUIRE(D == LD || scl_attn_wide_takes(D), "attn_fwd_packed_f32: " SCL_ATTN_HEAD_DIMS " (got D=%d)", D);
     SCL_REQUIRE(Mq >= B && Mq % 64 == 0 && (int64_t)Mq <= ((int64_t)B * T + 63) / 64 * 64,
                 "attn_fwd_packed_f32: need B <= Mq <= roundup(B * T, 64), a multiple of 64 (got Mq=%d)", Mq);
     SCL_REQUIRE(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)ctx & 15) == 0, "attn_fwd_packed_f32: qkv and ctx must be 16-byte aligned");
     const int nqb = (T + LQB - 1) / LQB;
     SCL_REQUIRE((int64_t)B * H * nqb < 0x7FFFFFFF, "attn_fwd_packed_f32: grid too large");
+    if (D != LD) return scl_attn_wide_fwd_f32(qkv, ctx, row0, B, T, H, D, Mq, scale, stream);
     hipLaunchKernelGGL(attn_fwd_packed_f32_kernel, dim3((unsigned)(B * H * nqb)), dim3(256), 0, (hipStream_t)stream, qkv, ctx, (const int*)row0,
                        T, H, nqb, B, Mq, scale);
     return scl_check_launch("scl_attn_fwd_packed_f32");

@@ -1,6 +1,7 @@
-// attn_wide.h — the launchers of attention_wide.hip: the streaming attention for head dims 72..128 (D % 8 == 0), all three row layouts.
-// They are internal to the library (hidden, C++ linkage): the C ABI entries of attention_long.hip, attention_varlen.hip and
-// attention_packed.hip validate their arguments, then hand a head dim that scl_attn_wide_takes over to them.
+// attn_wide.h — the launchers of attention_wide.hip and attention_f32_wide.hip: the streaming attention for head dims 72..128 (D % 8 == 0),
+// all three row layouts in bf16 and the packed fp32 forward.  They are internal to the library (hidden, C++ linkage): the C ABI entries of
+// attention_long.hip, attention_varlen.hip, attention_packed.hip and attention_f32.hip validate their arguments, then hand a head dim that
+// scl_attn_wide_takes over to them.
 #pragma once
 #include <cstdint>
 
@@ -19,3 +20,7 @@ __attribute__((visibility("hidden"))) int scl_attn_wide_fwd(SclAttnRows rows, co
 __attribute__((visibility("hidden"))) int scl_attn_wide_bwd(SclAttnRows rows, const char* who, const void* qkv, const void* ctx, const void* dctx,
                                                             const float* lse, const int32_t* lens, void* dqkv, void* ws, int B, int T, int H, int D,
                                                             int Mq, float scale, float drop_p, uint32_t drop_seed, void* stream);
+// attention_f32_wide.hip: the fp32 pair-form forward over packed rows, with the arguments of scl_attn_fwd_packed_f32 (attention_f32.hip),
+// which validates them first
+__attribute__((visibility("hidden"))) int scl_attn_wide_fwd_f32(const float* qkv, float* ctx, const int32_t* row0, int B, int T, int H, int D,
+                                                                int Mq, float scale, void* stream);

@@ -51,13 +51,14 @@ VARLEN_PACK = os.environ.get("SCL_VARLEN_PACK", "0") == "1"
 PACK_ROWS = 512
 # The same layout for the fp32 scoring path (forward_f32 with packed=(row0, Mq)): its attention is then the streaming pair-form kernel of
 # csrc/attention_f32.hip — no T x T score buffers, no chunk loop, no padded rows in the layers.  Opt-in (SCL_SCORE_PACK=1), read at call
-# time; SCL_VARLEN_PACK does not reach the fp32 path.  64-wide heads only.
+# time; SCL_VARLEN_PACK does not reach the fp32 path.  The head dims of the streaming family (stream_attn_takes): 72..128 run
+# csrc/attention_f32_wide.hip behind the same entry.
 SCORE_PACK = os.environ.get("SCL_SCORE_PACK", "0") == "1"
 
 
 def stream_attn_takes(head_dim):
-    """Whether the streaming attention kernels (fixed, zero-padded and packed rows, bf16) take this head dim: 64, or 72..128 in steps of 8
-    (XLS-R 300M: 64, 1B: 80, 2B: 120).  The fused on-chip kernels and the packed fp32 kernel take 64 only."""
+    """Whether the streaming attention kernels (fixed, zero-padded and packed rows in bf16, packed rows in fp32) take this head dim: 64,
+    or 72..128 in steps of 8 (XLS-R 300M: 64, 1B: 80, 2B: 120).  The fused on-chip kernels take 64 only."""
     return head_dim == 64 or (64 < head_dim <= 128 and head_dim % 8 == 0)
 
 
@@ -850,7 +851,8 @@ class Encoder:
         packed: (row0, Mq) with frames, as in forward() — the conv stack, zero_tail_rows(x0) and the positional convolution stay padded;
         its f32 result is packed into the other ping-pong buffer, the layers and the final LayerNorm run over Mq rows with the streaming
         fp32 attention of csrc/attention_f32.hip (no S / Pm buffers, no chunk loop above 512 frames), and the output is unpacked into
-        the padded [B*T, E] buffer with zero rows beyond each utterance.  64-wide heads only."""
+        the padded [B*T, E] buffer with zero rows beyond each utterance.  The head dims of stream_attn_takes (72..128:
+        csrc/attention_f32_wide.hip); any other raises NotImplementedError."""
         cfg, P = self.cfg, self.P
         B, L = x.shape
         C, E, H, Fd, K, G = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k, cfg.pos_groups
@@ -864,9 +866,9 @@ class Encoder:
         # above 512 frames the materialised attention runs in chunks of `bc` utterances (S / Pm sized per chunk, <= F32_ATTN_CHUNK_BYTES)
         long_attn = T > MAT_ATTN_MAX_T and not layout.packed
         bc = max(1, min(B, F32_ATTN_CHUNK_BYTES // (4 * H * T * Tp))) if long_attn else B
-        if layout.packed and D != 64:
-            raise NotImplementedError("encoder: SCL_SCORE_PACK=1 needs 64-wide attention heads (this encoder's are %d wide): the "
-                                      "packed fp32 attention kernel takes head dim 64 only" % D)
+        if layout.packed and not stream_attn_takes(D):
+            raise NotImplementedError("encoder: SCL_SCORE_PACK=1 needs 64-wide attention heads, or 72..128 in steps of 8 (this encoder's "
+                                      "are %d wide): the packed fp32 attention kernels take %s" % (D, STREAM_ATTN_HEAD_DIMS))
         R = Mp if layout.packed else M      # row capacity of the layer buffers: every packed row count of the shape
         nstat = max(B * Ts[1], R)      # LayerNorm statistics: the widest row count of the path
 

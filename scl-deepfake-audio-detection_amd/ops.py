@@ -494,7 +494,7 @@ def softmax_fwd_f32_long(S, P, R, T, ldS, Tp):
 
 def attn_fwd_long(qkv, ctx, lse, B, T, H, D, scale, drop_p=0.0, drop_seed=0):
     """Streaming attention forward (head dim 64, or 72..128 in steps of 8; any T): the operands and outputs of attn_fwd.  The same head
-    dims hold for attn_bwd_long and for the _varlen and _packed entries (not for attn_fwd_packed_f32: 64 only)."""
+    dims — those of the streaming family — hold for attn_bwd_long, for the _varlen and _packed entries and for attn_fwd_packed_f32."""
     return _call("scl_attn_fwd_long", _p(qkv), _p(ctx), _p(lse), B, T, H, D, float(scale), float(drop_p), int(drop_seed), _stream())
 
 
@@ -609,8 +609,9 @@ def attn_bwd_packed(qkv, ctx, dctx, lse, row0, dqkv, ws, B, T, H, D, Mq, scale, 
 
 
 def attn_fwd_packed_f32(qkv, ctx, row0, B, T, H, D, Mq, scale):
-    """The fp32 scoring path's attention on packed rows (csrc/attention_f32.hip): qkv f32 [Mq, 3, H, 64] -> ctx f32 [Mq, H * 64], streaming,
-    bf16-pair products (always: F32X3 does not reach it); nothing is stored past an utterance's end, ctx rows [row0[B], Mq) are written as 0."""
+    """The fp32 scoring path's attention on packed rows (csrc/attention_f32.hip): qkv f32 [Mq, 3, H, D] -> ctx f32 [Mq, H * D], streaming,
+    bf16-pair products (always: F32X3 does not reach it); nothing is stored past an utterance's end, ctx rows [row0[B], Mq) are written as 0.
+    The head dims of the streaming family: 64, or 72..128 in steps of 8 (csrc/attention_f32_wide.hip); any other raises SclError."""
     assert qkv.dtype == torch.float32 and ctx.dtype == torch.float32 and row0.numel() >= B + 1
     assert qkv.numel() >= Mq * 3 * H * D and ctx.numel() >= Mq * H * D
     return _call("scl_attn_fwd_packed_f32", _p(qkv), _p(ctx), _p(_klen(row0)), B, T, H, D, int(Mq), float(scale), _stream())
