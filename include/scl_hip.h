@@ -49,7 +49,7 @@ int scl_stream_wait_stream(void* waiter, void* signaler);
 #define SCL_KID_AUG  1   /* the RawBoost chain: scl_fir_multi_f32, scl_clip_stats_f32, scl_isd_scatter_f32, scl_clip_affine_f32 */
 #define SCL_KID_MAX  8
 /* bit 0: the library was built with -DSCL_EXPERIMENTS (the opt-in GEMM experiments: 256x128 / 256x256 ping-pong tiles, two workgroups per
- * CU, persistent blocks, start stagger).  The shipped library is built without; their flags / environment switches are then ignored. */
+ * CU, start stagger).  The shipped library is built without; their flags / environment switches are then ignored. */
 int scl_build_flags(void);
 int scl_prof_enable(int kid, int on);
 /* create n_pairs event pairs ahead of time: the first profiled step would otherwise pay hipEventCreate for every launch inside the
@@ -185,8 +185,10 @@ int scl_posconv_mfma(const void* xpad, const void* w, float* C, const float* bia
  * clock} at kernel entry, after the prologue, after the K loop, after the epilogue (blocks 0 .. nblocks-1, nblocks <= 4096). */
 int scl_debug_gemm_stamps(unsigned long long* out, int nblocks);
 /* diagnostic: launches so far (this process) that took the persistent wide-tile kernel (gemm_w8.hip, w8p: one resident block per CU
- * walks several tiles, next tile's first K stage requested before the epilogue).  Environment SCL_GEMM_PERSIST: 0 (default) never, 1
- * when a launch has more than one round of tiles, 8 .. 256 = that many resident blocks whenever the kernel is legal (tests). */
+ * walks several tiles, the next tile's first two K stages requested before the epilogue's stores).  Environment SCL_W8_PERSIST, read
+ * per launch: 0 never, unset / 1 when the launch has at least two tiles per resident block (K-contiguous A, no split-K, no batch, an
+ * epilogue without a residual operand), 8 .. 256 = that many resident blocks whenever the kernel is legal (tests).  The launch log
+ * (scl_prof_read_launches) names these launches variant 8. */
 long long scl_debug_gemm_persistent_launches(void);
 
 /* Split-K with the epilogue kept: run `desc` as a plain split-K GEMM into f32 slabs ([nslabs][M][N], slab stride `stride` elements:

@@ -448,8 +448,7 @@ __global__ __launch_bounds__(256, 1) void scl_gemm_deep_kernel(const GemmK d) {
 // (A 128x128 / BK = 32 / 5-stage variant that doubles the bytes in flight per CU was measured 4-19 % SLOWER than the kernel
 // above on every encoder shape — the extra barrier per 16 MFMAs costs more than the deeper prefetch returns — and removed.)
 
-// The 256x128 ("big") and 256x256 ping-pong ("p8") kernels and the two-workgroups-per-CU / persistent experiments of gemm_x2.hip /
-// gemm_w8.hip lost every A/B against the default family and are NOT part of the shipped library: they are compiled
+// The 256x128 ("big") and 256x256 ping-pong ("p8") kernels and the two-workgroups-per-CU experiment of gemm_x2.hip lost every A/B against the default family and are NOT part of the shipped library: they are compiled
 // only with -DSCL_EXPERIMENTS (SCL_BUILD_DEFINES=-DSCL_EXPERIMENTS python scl-deepfake-audio-detection_amd/build.py), for the record and
 // for their bit-identity tests.  Unused instantiations cost the default path 5-15 % through the instruction cache.
 #ifdef SCL_EXPERIMENTS
@@ -1020,7 +1019,10 @@ extern "C" int scl_gemm_bf16(const SclGemmDesc* dp, void* stream) {
 #else
         const bool deep = false;
 #endif
-        prof.note(d.M, d.N, d.K, d.flags, (int)zdim, x2 ? 3 : (w8 ? (plan.variant == 2 ? 6 : 1 + plan.variant) : (deep ? 7 : 0)));
+        // kernel variant of the launch log: 0 128x128, 1 / 2 wide 208- / 256-row tile, 3 two blocks per CU, 6 wide 112-row tile, 7 deep ring,
+        // 8 wide 208-row tile on persistent blocks (gemm_w8.hip, w8p)
+        const bool w8p = w8 && scl_gemm_w8_persist_blocks(k, at, bt, plan, zdim) > 0;
+        prof.note(d.M, d.N, d.K, d.flags, (int)zdim, x2 ? 3 : (w8p ? 8 : (w8 ? (plan.variant == 2 ? 6 : 1 + plan.variant) : (deep ? 7 : 0))));
         if (x2) {
 #ifdef SCL_EXPERIMENTS
             scl_gemm_x2_launch(k, at, bt, plan, zdim, s);

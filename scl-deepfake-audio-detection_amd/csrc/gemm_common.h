@@ -322,6 +322,7 @@ struct W8Plan { int variant, tiles_m, tile_m; long long tiles, cost; int ncu = 0
 bool scl_gemm_w8_plan(const GemmK& k, bool at, bool bt, const SclGemmDesc& d, long long zdim, int ncu, W8Plan* plan);
 int scl_gemm_read_stamps(unsigned long long* out, int nblocks);
 long long scl_gemm_w8p_launches();
+int scl_gemm_w8_persist_blocks(const GemmK& k, bool at, bool bt, const W8Plan& plan, long long zdim);      // resident blocks of the persistent kernel, 0: one-tile blocks
 int scl_gemm_w8_launch(GemmK& k, bool at, bool bt, const W8Plan& plan, long long zdim, hipStream_t s);
 constexpr int W8_GROUP_MAX = 8;      // members of a grouped launch (scl_gemm_bf16_group / _part)
 bool scl_gemm_w8_group_member_ok(const GemmK& k, bool at, bool bt, const SclGemmDesc& d);

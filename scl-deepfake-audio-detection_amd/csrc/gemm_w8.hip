@@ -607,61 +607,96 @@ __global__ __launch_bounds__(512, 2) void scl_gemm_w8s_group_kernel(const GemmGr
     w8s_tile<AT, BT, RB0, RB1, true>(*(const GemmK*)&gp->k[mem], smem, t, gp->ntiles[mem], 0);      // (one instantiation in the shipped library: the tile body is 120 KB of code)
 }
 
-#ifdef SCL_EXPERIMENTS      // opt-in experiment, not part of the shipped library (see gemm.hip)
 // ---- persistent single-barrier variant ("w8p") -----------------------------------------------------------------------------
 // One block per CU stays resident and walks the tiles v = blockIdx.x, + gridDim.x, ... (gridDim.x a multiple of 8: v & 7, the XCD of
-// tile_coords, is the block's own).  Why: with one 160-KiB block per CU nothing overlaps a block's retirement, the dispatch of the
-// next one, its argument loads and the first LDS-DMA round trip — at K = 1024 a 208 x 256 tile spends 23 us in its 16 K steps and
-// 35 us on the CU (fc1 forward, plain stores: 141 us for 4 rounds; the vendor library's persistent kernel: 117 us).  Here
-//   * K step nk-2 of a tile stages the NEXT tile's K-stage 0 instead of out-of-range pieces (A into the ring slot that is free,
-//     B into the image just consumed): it lands under the last two K steps;
-//   * the epilogue runs in the 96 KiB that do not hold that stage: a wave's transposition block is two 4-KiB halves (two 16-row
-//     blocks per pass) at ITS OWN piece offsets of the two free A slots, its R staging the same 4 KiB of the free B image — so
-//     after its last pass a wave stages K-stage 1 of the next tile straight into those regions without a block-wide barrier;
-//   * the next K loop starts on stage 0 (landed before the epilogue), its first wait covers stage 1 and the epilogue's stores.
+// tile_coords, is the block's own, so its operand panels stay in that XCD's L2).  Why: with one 160-KiB block per CU nothing overlaps a
+// block's retirement, the dispatch of the next one, its argument loads and the first LDS-DMA round trip (stamps: 1.7 + 1.4 us of a
+// 208 x 256 x 1024 tile, and the epilogue's 5.4 us start only after the rings have drained).
+// The K loop is w8s_body's, and the tiles of a block are ONE K stream through the same rings: steps nk-2 and nk-1 of a tile request
+// K stages 0 and 1 of the NEXT tile where they would request out-of-range pieces — A at the first half of the step into the free slot of
+// the ring of 3, B behind the step's barrier into the image that barrier retired.  When the loop ends both stages are in flight or
+// landed, BEFORE the first store of the epilogue (vmcnt retires in order: requested behind the stores, stage 1 would make the next
+// tile's first barrier wait for every store's acknowledgement and then for a whole L2 -> LDS round trip), and exactly one 32-KiB A slot
+// is free: the one of K step nk-1, which every wave finished reading before that step's barrier.
+// The epilogue runs in that slot: a wave owns the 4 KiB at ITS OWN piece offsets (one 16-row x 64-column f32 block per pass, 7 or 6
+// passes, column sums carried between passes so that a lane adds its rows in the order of w8s's two 4-block passes) — so step 0 of the
+// next tile, whose A pieces go to the same 4 KiB, needs no block-wide barrier after the epilogue, only the wave's own LDS reads retired.
+// That step's barrier then waits for the acknowledgement of the stores under the first half-step's MFMAs; stage 0 landed long before.
 // Same tile, same K order, same epilogue arithmetic and column-sum partial rows as w8s: bit-identical results.
-// The descriptor is NOT kept in scalar registers across the K loops (w8s already spills some; here the epilogue's and the loaders'
-// fields would be live through every K step of every tile): the hand-over step and the epilogue re-read it from the kernel-argument
-// segment through a pointer the compiler cannot trace back (scalar loads, a few hundred cycles once per tile).
+// EK: the epilogue kind (gemm_w8_epi.h) is a template parameter — one straight-line epilogue per kernel, 13 copies of it (7 + 6 passes)
+// instead of 13 x every kind.  Kinds without a residual operand only (1, 2, 5): R staging needs 4 KiB per wave outside the wave's block,
+// and the rings have none to spare during the hand-over; those launches stay on w8s.  RB0 / RB1: 7 + 6 (208 rows) for every kind, 8 + 8
+// (256 rows) for the conv stack's two shapes — that form fits the 256 registers only with w8p_lane below.
+// Measured against one-tile blocks (profiles/persist_handover.txt): fc1 forward 131.1 -> 125.1 us, QKV forward 82.8 -> 79.1, the conv
+// stack's forward / data-gradient launches -11 ... -30 %; the train step 39.12 -> 38.58 ms.
+// The descriptor is NOT kept in scalar registers across the K loops: the hand-over step and the epilogue re-read it from the
+// kernel-argument segment through a pointer the compiler cannot trace back (scalar loads, a few hundred cycles once per tile).
 typedef const __attribute__((address_space(4))) GemmK* W8KArg;
 __device__ __forceinline__ const GemmK* w8p_args(W8KArg p) {
     asm volatile("" : "+s"(p));
     return (const GemmK*)p;
 }
-template <bool AT, bool BT, int RBW>
-__device__ __forceinline__ void w8p_body(const GemmK& d, W8KArg kp, char* smem, const char* Ab, const char* Bb, int ab, int tiles_m, int tiles_n,
-                                         int lane, int wave, int wc) {
+// The lane id, recomputed where the hand-over step and the epilogue need it, behind an asm the compiler cannot look through: what is
+// derived from it there (piece offsets, transposition addresses) is then not hoisted out of the tile loop and kept in vector registers
+// across every K step — with the 256-row tile's 128 accumulators that hoisting was the difference between 256 registers and a private segment.
+__device__ __forceinline__ int w8p_lane() {
+    int l = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    asm volatile("" : "+v"(l));
+    return l;
+}
+constexpr int W8_EPI_KEY = SCL_GEMM_C_F32 | SCL_GEMM_C2_F32 | SCL_GEMM_R_F32 | SCL_GEMM_HAS_BIAS | SCL_GEMM_HAS_C2 | SCL_GEMM_DROPOUT |
+                           (0xF << SCL_GEMM_ACT_SHIFT) | (0xF << SCL_GEMM_RMODE_SHIFT) | (0xF << SCL_GEMM_RACT_SHIFT);
+// the epilogue kind of gemm_w8_epi.h the persistent kernels are built for (1, 2, 5), or 0
+inline int w8p_epi_kind(int flags) {
+    const int f = flags & W8_EPI_KEY, fb = f & ~SCL_GEMM_HAS_BIAS;
+    if (fb == 0) return 1;
+    if (f == (SCL_GEMM_HAS_BIAS | SCL_GEMM_HAS_C2 | (5 << SCL_GEMM_ACT_SHIFT))) return 2;
+    if (fb == SCL_GEMM_C_F32) return 5;
+    return 0;
+}
+
+template <bool AT, bool BT, int RBW, int EK>
+__device__ __forceinline__ void w8p_body(W8KArg kp, char* smem, const int ab, const int lane, const int wave, const int wc) {
     typedef typename W8Sel<AT>::type LA;
     typedef typename W8Sel<BT>::type LB;
-    const unsigned stepA = LA::kstep(d.A), stepB = LB::kstep(d.B);
-    const int nk = d.K / BK;                                       // >= 3, no split-K (host)
-    const int ntiles = tiles_m * tiles_n, G = gridDim.x;
+    typedef W8SRead<AT, BT, RBW> RD;
+    constexpr int NRD = RBW + 4, OPA = AT ? 2 : 1, OPB = BT ? 2 : 1;
+    constexpr int RQ0 = 4, RQ1 = 8, RQ2 = NRD;      // (RBW >= 6)
+    static_assert(RBW >= 6 && RBW <= 8, "w8p_body: 6 to 8 row blocks per wave");
+    auto ops_upto = [](int n) constexpr { return (n > 0 ? OPB : 0) + (n > 1 ? (n - 1 < RBW ? n - 1 : RBW) * OPA : 0) + (n > RBW + 1 ? (n - RBW - 1) * OPB : 0); };
     const int nbk = wc * 4;
     char* const bimg = smem + W8_NA * W8_OPB;
     char *a_cur = smem, *a_nxt = smem + W8_OPB, *a_fill = smem + 2 * W8_OPB;
-    int bpar = 0;                                                  // B image that holds K-stage 0 of the current tile
-    int v = blockIdx.x, tm, tn;
-    tile_coords(v, ntiles, tiles_m, tiles_n, tm, tn, d.group_m);
-    const int tile_m = d.tile_m, Mrows = d.M, group_m = d.group_m;
-    int m0 = tm * tile_m, n0 = tn * W8_BN, mlimit = min(Mrows, m0 + tile_m);
     LA la;
     LB lb;
-    la.init(d.A, Ab, m0, mlimit, lane, wave);
-    lb.init(d.B, Bb, n0, d.N, lane, wave);
     la.set_batched(false); lb.set_batched(false);
+    int nk, tile_m, Mrows, group_m, tiles_m, tiles_n, m0, n0, mlimit;
+    unsigned stepA, stepB;
+    int v = blockIdx.x;
+    {
+        const GemmK* d0 = w8p_args(kp);
+        nk = d0->K / BK;                                           // >= 3, no split-K, one problem (host)
+        tile_m = d0->tile_m; Mrows = d0->M; group_m = d0->group_m;
+        tiles_m = __builtin_amdgcn_readfirstlane((Mrows + tile_m - 1) / tile_m);
+        tiles_n = (d0->N + W8_BN - 1) / W8_BN;
+        if (v >= tiles_m * tiles_n) return;                        // a forced grid larger than the tile count: nothing to walk
+        stepA = LA::kstep(d0->A); stepB = LB::kstep(d0->B);
+        int tm, tn;
+        tile_coords(v, tiles_m * tiles_n, tiles_m, tiles_n, tm, tn, group_m);
+        m0 = tm * tile_m; n0 = tn * W8_BN; mlimit = min(Mrows, m0 + tile_m);
+        la.init(d0->A, reinterpret_cast<const char*>(d0->A.ptr), m0, mlimit, lane, wave);
+        lb.init(d0->B, reinterpret_cast<const char*>(d0->B.ptr), n0, d0->N, lane, wave);
+    }
+    const int ntiles = tiles_m * tiles_n, G = gridDim.x;
     la.template issue2<0>(a_cur, wave, 0u, true); la.template issue2<2>(a_cur, wave, 0u, true);
     lb.template issue2<0>(bimg, wave, 0u, true); lb.template issue2<2>(bimg, wave, 0u, true);
     la.template issue2<0>(a_nxt, wave, stepA, true); la.template issue2<2>(a_nxt, wave, stepA, true);
     lb.template issue2<0>(bimg + W8_OPB, wave, stepB, true); lb.template issue2<2>(bimg + W8_OPB, wave, stepB, true);
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#define W8S_READ(FA, FB, TA, TB, KS)                                                        \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) FB[j] = w8_frag<BT>(TB, nbk + j, KS, lane); \
-    _Pragma("unroll") for (int i = 0; i < RBW; ++i) FA[i] = w8_frag<AT>(TA, ab + i, KS, lane);
-#define W8S_MFMA(FA, FB)                                                                    \
-    _Pragma("unroll") for (int i = 0; i < RBW; ++i)                                         \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j)                                       \
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FB[j], FA[i], acc[i][j], 0, 0, 0);
+    int bpar = 0;                                                  // B image that holds K stage 0 of the current tile
+    unsigned soffA = stepA, soffB = stepB;                         // K stage 1 is in flight, stage 0 visible
+    int m0n = 0, n0n = 0, mlimn = 0;
     for (;;) {
         f32x4 acc[RBW][4];
 #pragma unroll
@@ -669,118 +704,131 @@ __device__ __forceinline__ void w8p_body(const GemmK& d, W8KArg kp, char* smem, 
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         bf16x8 fa0[RBW], fa1[RBW], fb0[4], fb1[4];
-        const int vn = v + G;
-        const bool has_next = vn < ntiles;
-        int m0n = 0, n0n = 0, mlimn = 0;
-        if (has_next) {
-            tile_coords(vn, ntiles, tiles_m, tiles_n, tm, tn, group_m);
-            m0n = tm * tile_m; n0n = tn * W8_BN; mlimn = min(Mrows, m0n + tile_m);
-        }
-        unsigned soffA = stepA, soffB = stepB;                     // K-stage 1 is in flight, stage 0 visible
-        W8S_READ(fa0, fb0, a_cur, bimg + bpar * W8_OPB, 0)
+        const bool has_next = v + G < ntiles;
+        lds_wait_upto(0);      // no scalar load or epilogue read may be pending when the loop starts (w8s_body)
+        __builtin_amdgcn_sched_barrier(0);
+        RD::template go<0, NRD, true>(fa0, fb0, a_cur, bimg + bpar * W8_OPB, ab, nbk, 0, lane);
         for (int kt = 0; kt < nk; ++kt) {
             char* tB = bimg + ((kt + bpar) & 1) * W8_OPB;
-            const bool hand = kt + 2 == nk;                        // this step stages the next tile's K-stage 0
-            const bool live2 = kt + 2 < nk || (hand && has_next);
+            const bool live2 = kt + 2 < nk || has_next;            // the tile's last two steps stage the next tile's K stages 0 and 1
             soffA += stepA; soffB += stepB;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            W8S_READ(fa1, fb1, a_cur, tB, 1)
-            __builtin_amdgcn_sched_barrier(0);
-            W8S_MFMA(fa0, fb0)
-            __builtin_amdgcn_sched_barrier(0);
-            if (hand && has_next) {      // the current tile's last A stage was requested at kt-1
-                const GemmK* dh = w8p_args(kp);
-                la.init(dh->A, reinterpret_cast<const char*>(dh->A.ptr), m0n, mlimn, lane, wave);
+            if (kt + 2 == nk) {      // hand-over: the current tile's last A and B stages were requested at step nk-3
+                soffA = 0u; soffB = 0u;
+                if (has_next) {
+                    int tm, tn;
+                    tile_coords(v + G, ntiles, tiles_m, tiles_n, tm, tn, group_m);
+                    m0n = tm * tile_m; n0n = tn * W8_BN; mlimn = min(Mrows, m0n + tile_m);
+                    const GemmK* dh = w8p_args(kp);
+                    const int ln = w8p_lane();
+                    la.init(dh->A, reinterpret_cast<const char*>(dh->A.ptr), m0n, mlimn, ln, wave);
+                    lb.init(dh->B, reinterpret_cast<const char*>(dh->B.ptr), n0n, dh->N, ln, wave);
+                    lds_wait_upto(0);      // the scalar loads above: none pending under the counted waits below
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
-            {
-                const unsigned sa = hand ? 0u : soffA;
-                la.template issue2<0>(a_fill, wave, sa, live2); la.template issue2<2>(a_fill, wave, sa, live2);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            // the two halves of a K step: w8s_body's, see there for the order of reads, waits, MFMA quarters and pieces
+#define W8P_Q_FIRST(j, R0, R1)                                                                                               \
+            RD::template go<R0, R1, false>(fa1, fb1, a_cur, tB, ab, nbk, 1, lane);                                           \
+            __builtin_amdgcn_sched_barrier(0);                                                                               \
+            lds_wait_upto((3 - (j)) * OPB + ops_upto(R1));                                                                   \
+            __builtin_amdgcn_sched_barrier(0);                                                                               \
+            _Pragma("unroll") for (int i = 0; i < RBW; ++i)                                                                  \
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb0[j], fa0[i], acc[i][j], 0, 0, 0);                     \
+            __builtin_amdgcn_sched_barrier(0);                                                                               \
+            la.issue1(a_fill, wave, soffA, live2, j);                                                                        \
+            __builtin_amdgcn_sched_barrier(0);
+            W8P_Q_FIRST(0, 0, RQ0) W8P_Q_FIRST(1, RQ0, RQ1) W8P_Q_FIRST(2, RQ1, RQ2) W8P_Q_FIRST(3, RQ2, NRD)
+#undef W8P_Q_FIRST
+            lds_wait_upto(0);                                   // set 1 complete, and with it this wave's last read of K stage kt
+            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");    // all but this step's A pieces: K stage kt+1 has landed — at kt = 0 of a later tile also: the previous epilogue's stores are acknowledged
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
-            if (hand && has_next) {
-                const GemmK* dh = w8p_args(kp);
-                lb.init(dh->B, reinterpret_cast<const char*>(dh->B.ptr), n0n, dh->N, lane, wave);
-            }
-            {
-                const unsigned sb = hand ? 0u : soffB;
-                lb.template issue2<0>(tB, wave, sb, live2); lb.template issue2<2>(tB, wave, sb, live2);
-            }
-            if (kt + 1 < nk) { W8S_READ(fa0, fb0, a_nxt, bimg + (((kt + bpar) & 1) ^ 1) * W8_OPB, 0) }
+            const char* tBn = bimg + (((kt + bpar) & 1) ^ 1) * W8_OPB;
+#define W8P_B_ISSUE(j) if ((j) < 2) { lb.issue1(tB, wave, soffB, live2, 2 * (j)); lb.issue1(tB, wave, soffB, live2, 2 * (j) + 1); }
+#define W8P_Q_SECOND(j, R0, R1)                                                                                              \
+            RD::template go<R0, R1, false>(fa0, fb0, a_nxt, tBn, ab, nbk, 0, lane);                                          \
+            __builtin_amdgcn_sched_barrier(0);                                                                               \
+            _Pragma("unroll") for (int i = 0; i < RBW; ++i)                                                                  \
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1[j], fa1[i], acc[i][j], 0, 0, 0);                     \
+            __builtin_amdgcn_sched_barrier(0);                                                                               \
+            W8P_B_ISSUE(j)                                                                                                   \
             __builtin_amdgcn_sched_barrier(0);
-            W8S_MFMA(fa1, fb1)
-            __builtin_amdgcn_sched_barrier(0);
+            W8P_Q_SECOND(0, 0, RQ0) W8P_Q_SECOND(1, RQ0, RQ1) W8P_Q_SECOND(2, RQ1, RQ2) W8P_Q_SECOND(3, RQ2, NRD)
+#undef W8P_Q_SECOND
+#undef W8P_B_ISSUE
             char* t = a_cur; a_cur = a_nxt; a_nxt = a_fill; a_fill = t;
         }
-        // a_cur: stage 0 of the next tile (or zeros); a_nxt: the zero pieces of step nk-1; a_fill: K tile nk-1; B image
-        // (nk-1+bpar)&1: zero pieces.  Everything has landed and every wave is past its last fragment read after this barrier.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        char* const bfree = bimg + ((nk - 1 + bpar) & 1) * W8_OPB;
+        // a_cur / a_nxt: K stages 0 / 1 of the next tile (or zero pieces); a_fill: K stage nk-1, retired by the last barrier — the
+        // epilogue's slot.  The last half-step read fragments nothing uses (w8s_body): they must have returned before their registers are.
+        lds_wait_upto(0);
+        __builtin_amdgcn_sched_barrier(0);
         {
-            const GemmK& d = *w8p_args(kp);      // shadows the kernel's by-value copy on purpose
-            const float* bias = (d.flags & SCL_GEMM_HAS_BIAS) ? d.bias : nullptr;
+            const GemmK& d = *w8p_args(kp);
+            const int ln = w8p_lane();
+            const float* bias = (EK == 2 || (d.flags & SCL_GEMM_HAS_BIAS)) ? d.bias : nullptr;
             char* wlds = a_fill + wave * 4096;
-            const int bstride = (int)(a_nxt - a_fill);
-            char* wextra = bfree + wave * 4096;
             float* cs0 = d.colsum ? d.colsum + ((long long)(m0 / tile_m) * 4 + (wave >> 2) * 2) * d.N : nullptr;
             float cs[8];
 #pragma unroll
-            for (int pr = 0; pr < (RBW + 1) / 2; ++pr) {
-                if (pr == 0 || pr == 2) {
+            for (int b = 0; b < RBW; ++b) {
+                if (b == 0 || b == 4) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) cs[j] = 0.f;
                 }
-                if (2 * pr + 1 < RBW) {
-                    f32x4 (&a2)[2][4] = *reinterpret_cast<f32x4 (*)[2][4]>(&acc[2 * pr]);
-                    w8_epilogue_pass<2, 0>(d, a2, 2, wlds, wextra, m0 + (ab + 2 * pr) * 16, n0 + wc * 64, mlimit, 0ll, bias, lane, nullptr,
-                                        cs0 ? cs : nullptr, bstride);
-                } else {
-                    f32x4 (&a1)[1][4] = *reinterpret_cast<f32x4 (*)[1][4]>(&acc[2 * pr]);
-                    w8_epilogue_pass<1, 0>(d, a1, 1, wlds, wextra, m0 + (ab + 2 * pr) * 16, n0 + wc * 64, mlimit, 0ll, bias, lane, nullptr,
-                                        cs0 ? cs : nullptr, bstride);
-                }
-                if (cs0 && (pr == 1 || pr == (RBW + 1) / 2 - 1)) w8_colsum_store(d, cs, cs0 + (pr >> 1) * d.N, n0 + wc * 64, lane);
+                f32x4 (&a1)[1][4] = *reinterpret_cast<f32x4 (*)[1][4]>(&acc[b]);
+                // the carry is passed unconditionally: a pointer that may be null keeps the array in a private segment
+                w8_epilogue_pass_k<1, EK>(d, a1, 1, wlds, wlds, m0 + (ab + b) * 16, n0 + wc * 64, mlimit, 0ll, bias, ln, nullptr, cs, 4096);
+                if (cs0 && (b == 3 || b == RBW - 1)) w8_colsum_store(d, cs, cs0 + (b >> 2) * d.N, n0 + wc * 64, ln);
             }
         }
         if (!has_next) break;
-        // K-stage 1 of the next tile into this wave's own epilogue regions (its LDS reads have returned: their values were stored)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        la.template issue2<0>(a_nxt, wave, stepA, true); la.template issue2<2>(a_nxt, wave, stepA, true);
-        lb.template issue2<0>(bfree, wave, stepB, true); lb.template issue2<2>(bfree, wave, stepB, true);
         bpar = (bpar + nk) & 1;
-        v = vn; m0 = m0n; n0 = n0n; mlimit = mlimn;
+        v += G; m0 = m0n; n0 = n0n; mlimit = mlimn;
     }
-#undef W8S_READ
-#undef W8S_MFMA
 }
 
-template <bool AT, bool BT, int RB0, int RB1>
-__global__ __launch_bounds__(512, 2) void scl_gemm_w8p_kernel(const GemmK d) {
+template <bool AT, bool BT, int EK, int RB0, int RB1>
+__global__ __launch_bounds__(512, 2) void scl_gemm_persist_w8_kernel(const GemmK d) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // 0..7
-    const int wr = wave >> 2, wc = wave & 3;
-    const int tiles_m = (d.M + d.tile_m - 1) / d.tile_m, tiles_n = (d.N + W8_BN - 1) / W8_BN;
-    const char* Ab = reinterpret_cast<const char*>(d.A.ptr);
-    const char* Bb = reinterpret_cast<const char*>(d.B.ptr);
     W8KArg kp = (W8KArg)__builtin_amdgcn_kernarg_segment_ptr();
-    if (RB0 == RB1) {
-        w8p_body<AT, BT, RB0>(d, kp, smem, Ab, Bb, wr * RB0, tiles_m, tiles_n, lane, wave, wc);
-    } else if (wr == 0) {
-        w8p_body<AT, BT, RB0>(d, kp, smem, Ab, Bb, 0, tiles_m, tiles_n, lane, wave, wc);
+    if (RB0 == RB1) w8p_body<AT, BT, RB0, EK>(kp, smem, (wave >> 2) * RB0, lane, wave, wave & 3);
+    else if ((wave >> 2) == 0) w8p_body<AT, BT, RB0, EK>(kp, smem, 0, lane, wave, wave & 3);
+    else w8p_body<AT, BT, RB1, EK>(kp, smem, RB0, lane, wave, wave & 3);
+}
+
+template <bool AT, bool BT, int EK, int RB0, int RB1>
+void w8p_launch_k(const GemmK& k, dim3 grid, hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)scl_gemm_persist_w8_kernel<AT, BT, EK, RB0, RB1>, hipFuncAttributeMaxDynamicSharedMemorySize, W8_LDS);
+        attr_set = true;
+    }
+    SCL_LAUNCH((scl_gemm_persist_w8_kernel<AT, BT, EK, RB0, RB1>), grid, dim3(512), W8_LDS, s, k);
+}
+// Instantiated: what the dispatcher uses.  K-contiguous A only (forward and data-gradient launches).  208-row tiles: kinds 1, 2, 5 with
+// either B layout.  256-row tiles (the conv stack's long launches): f32 [+ bias] forward (NN) and plain bf16 data gradient (NT) only.
+bool w8p_built(bool bt, int ek, int variant) {
+    if (variant == 0) return ek == 1 || ek == 2 || ek == 5;
+    return variant == 1 && ((!bt && ek == 5) || (bt && ek == 1));
+}
+void w8p_launch(const GemmK& k, bool bt, int ek, int variant, dim3 grid, hipStream_t s) {
+    if (variant == 1) {
+        if (!bt) w8p_launch_k<false, false, 5, 8, 8>(k, grid, s);
+        else w8p_launch_k<false, true, 1, 8, 8>(k, grid, s);
+    } else if (!bt) {
+        if (ek == 1) w8p_launch_k<false, false, 1, 7, 6>(k, grid, s);
+        else if (ek == 2) w8p_launch_k<false, false, 2, 7, 6>(k, grid, s);
+        else w8p_launch_k<false, false, 5, 7, 6>(k, grid, s);
     } else {
-        w8p_body<AT, BT, RB1>(d, kp, smem, Ab, Bb, RB0, tiles_m, tiles_n, lane, wave, wc);
+        if (ek == 1) w8p_launch_k<false, true, 1, 7, 6>(k, grid, s);
+        else if (ek == 2) w8p_launch_k<false, true, 2, 7, 6>(k, grid, s);
+        else w8p_launch_k<false, true, 5, 7, 6>(k, grid, s);
     }
 }
 
-#endif  // SCL_EXPERIMENTS
 
 template <int RB0, int RB1>
 void w8_launch_rb(const GemmK& k, bool at, bool bt, dim3 grid, hipStream_t s, int mode) {
@@ -794,26 +842,9 @@ void w8_launch_rb(const GemmK& k, bool at, bool bt, dim3 grid, hipStream_t s, in
         (void)hipFuncSetAttribute((const void*)scl_gemm_w8s_kernel<false, true, RB0, RB1>, hipFuncAttributeMaxDynamicSharedMemorySize, W8_LDS);
         (void)hipFuncSetAttribute((const void*)scl_gemm_w8s_kernel<true, false, RB0, RB1>, hipFuncAttributeMaxDynamicSharedMemorySize, W8_LDS);
         (void)hipFuncSetAttribute((const void*)scl_gemm_w8s_kernel<true, true, RB0, RB1>, hipFuncAttributeMaxDynamicSharedMemorySize, W8_LDS);
-#ifdef SCL_EXPERIMENTS
-        if constexpr (RB0 == 7) {
-            (void)hipFuncSetAttribute((const void*)scl_gemm_w8p_kernel<false, false, RB0, RB1>, hipFuncAttributeMaxDynamicSharedMemorySize, W8_LDS);
-            (void)hipFuncSetAttribute((const void*)scl_gemm_w8p_kernel<false, true, RB0, RB1>, hipFuncAttributeMaxDynamicSharedMemorySize, W8_LDS);
-            (void)hipFuncSetAttribute((const void*)scl_gemm_w8p_kernel<true, false, RB0, RB1>, hipFuncAttributeMaxDynamicSharedMemorySize, W8_LDS);
-        }
-#endif
         attr_set = true;
     }
     const dim3 block(512);
-#ifdef SCL_EXPERIMENTS
-    if constexpr (RB0 == 7) {      // the persistent loop exists for the 208-row tile only (scl_gemm_w8_launch never asks for it with 256 rows)
-        if (mode == 2) {      // grid = resident blocks (never both operands transposed: those launches take the ping-pong loop)
-            if (!at && !bt) SCL_LAUNCH((scl_gemm_w8p_kernel<false, false, RB0, RB1>), grid, block, W8_LDS, s, k);
-            else if (!at && bt) SCL_LAUNCH((scl_gemm_w8p_kernel<false, true, RB0, RB1>), grid, block, W8_LDS, s, k);
-            else SCL_LAUNCH((scl_gemm_w8p_kernel<true, false, RB0, RB1>), grid, block, W8_LDS, s, k);
-            return;
-        }
-    }
-#endif
     if (mode == 1) {
         if (!at && !bt) SCL_LAUNCH((scl_gemm_w8s_kernel<false, false, RB0, RB1>), grid, block, W8_LDS, s, k);
         else if (!at && bt) SCL_LAUNCH((scl_gemm_w8s_kernel<false, true, RB0, RB1>), grid, block, W8_LDS, s, k);
@@ -937,6 +968,28 @@ int scl_gemm_read_stamps(unsigned long long* out, int nblocks) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(scl_gemm_stamps), sizeof(unsigned long long) * 8 * (size_t)nblocks) == hipSuccess ? 0 : -1;
 }
 
+// Resident blocks of the persistent kernel (w8p) for this launch, 0 = the launch stays on one-tile blocks.  Rule: a tiling and kind the kernel is built
+// for (w8p_built: 208-row tiles, and 256-row tiles for the conv stack's two shapes), A K-contiguous, one un-batched problem without split-K, an epilogue kind the kernel is built for (w8p_epi_kind, under the straight-line
+// kinds' alignment conditions of w8_epilogue_pass), at least 3 K steps, and at least two tiles for every resident block.
+// SCL_W8_PERSIST (read per launch): 0 = never, unset / 1 = by the rule, 8 .. 256 = that many resident blocks whenever the kernel is
+// legal (tests: several tiles per block on small problems, or more blocks than tiles).
+int scl_gemm_w8_persist_blocks(const GemmK& k, bool at, bool bt, const W8Plan& plan, long long zdim) {
+    const char* pe = getenv("SCL_W8_PERSIST");
+    const int pv = (pe && *pe) ? atoi(pe) : 1;
+    const char* me = getenv("SCL_W8_MODE");
+    static const bool epi_generic = [] { const char* e = getenv("SCL_W8_EPI_GENERIC"); return e && atoi(e) != 0; }();
+    if (pv <= 0 || (me && *me && atoi(me) != 1) || epi_generic) return 0;
+    if (plan.variant > 1 || at || zdim != 1 || k.splitk != 1 || k.K / BK < 3 || (k.flags & SCL_GEMM_STAMPS)) return 0;
+    const int ek = w8p_epi_kind(k.flags);
+    if (!ek || !w8p_built(bt, ek, plan.variant) || ((unsigned)k.flags & SCL_GEMM_C_SPLIT3) || !k.vec_ok || (k.ldc & 7) || (k.c_rbstride & 7)) return 0;
+    if (pv >= 8) return pv > 256 ? 256 : (pv & ~7);
+    const long long ncu = plan.ncu >= 8 ? plan.ncu : 256;
+    const long long rounds = (plan.tiles + ncu - 1) / ncu;
+    long long G = (((plan.tiles + rounds - 1) / rounds) + 7) & ~7ll;      // equal rounds on every block, a multiple of 8
+    if (G > (ncu & ~7ll)) G = ncu & ~7ll;
+    return (G >= 8 && plan.tiles >= 2 * G) ? (int)G : 0;
+}
+
 int scl_gemm_w8_launch(GemmK& k, bool at, bool bt, const W8Plan& plan, long long zdim, hipStream_t s) {
     k.tile_m = plan.tile_m;
     k.debug = 0;
@@ -969,26 +1022,17 @@ int scl_gemm_w8_launch(GemmK& k, bool at, bool bt, const W8Plan& plan, long long
         const int stg = sg ? atoi(sg) : 0;
         if (stg > 0 && plan.tiles > 256 && zdim == 1) k.debug |= (stg & 0xFF) << 8;
     }
-    // persistent blocks (w8p): SCL_GEMM_PERSIST = 0 (default) never, 1 when the launch has more than one round of tiles, 8 .. 256 =
-    // that many resident blocks whenever the kernel is legal (tests: several tiles per block on small problems).  Opt-in: measured
-    // on MI355X against one-tile blocks (tools/persist_probe.py, profiles/r3_gemm_persistent_vs_one_tile.txt) it is equal within
-    // +-2 % on the encoder's 3- and 4-round launches — the first K step of the next tile still waits (in-order vmcnt) for the
-    // epilogue's stores, whose drain into HBM, with every CU storing at once, is what a block switch already overlapped — and the
-    // 256-row variant spills.  In the full train step SCL_GEMM_PERSIST=1 is much SLOWER (84.8 vs 47.4 ms: +0.5 ms per persistent
-    // launch): the w8p kernels are the only ones in the step with a private segment (48-96 B of scratch from their register
-    // pressure), and a kernel that needs scratch between kernels that do not costs a queue-side scratch set-up per dispatch.  Kept
-    // as a tested, documented experiment; do not switch it on for training.
-    const char* pe = getenv("SCL_GEMM_PERSIST");
-    const int pv = pe ? atoi(pe) : 0;
-    if (mode == 1 && pv > 0 && !(at && bt) && zdim == 1 && k.splitk == 1 && k.K / BK >= 3 && !(k.flags & SCL_GEMM_STAMPS)) {
-        const long long ncu = plan.ncu >= 8 ? plan.ncu : 256;
-        const long long rounds = (plan.tiles + ncu - 1) / ncu;
-        long long G = pv >= 8 ? (pv & ~7) : ((((plan.tiles + rounds - 1) / rounds) + 7) & ~7ll);      // equal rounds on every block, a multiple of 8
-        if (G > (ncu & ~7ll) && pv < 8) G = ncu & ~7ll;
-        // the 208-row variant only — the 256-row one spilled under the persistent loop's register pressure (2 x slower) and is not built
-        if (plan.variant == 0 && (pv >= 8 || rounds >= 2) && G >= 8 && G < plan.tiles) { mode = 2; g = dim3((unsigned)G, 1, 1); ++w8p_launches; }
-    }
 #endif
+    // persistent blocks (w8p): one resident block per CU walks its tiles, both first K stages of the next tile requested ahead of the
+    // epilogue's stores (scl_gemm_w8_persist_blocks: the rule and the SCL_W8_PERSIST switch)
+    if (mode == 1) {
+        const int G = scl_gemm_w8_persist_blocks(k, at, bt, plan, zdim);
+        if (G > 0) {
+            ++w8p_launches;
+            w8p_launch(k, bt, w8p_epi_kind(k.flags), plan.variant, dim3((unsigned)G, 1, 1), s);
+            return 0;
+        }
+    }
     if (plan.variant == 2) w8_launch_43(k, bt, g, s);
     else if (plan.variant == 0) w8_launch_rb<7, 6>(k, at, bt, g, s, mode);
     else w8_launch_rb<8, 8>(k, at, bt, g, s, mode);

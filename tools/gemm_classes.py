@@ -79,7 +79,7 @@ def alg_bytes(meta, H):
     return rd, out
 
 
-GEMM_RE = re.compile(r"scl_gemm_(w8s_group_|w8s_|w8_|dma_|w8p_|x2_)?kernel|posconv_mfma_kernel|posconv_wgrad_kernel")
+GEMM_RE = re.compile(r"scl_gemm_(w8s_group_|w8s_|w8_|dma_|persist_w8_|x2_)?kernel|posconv_mfma_kernel|posconv_wgrad_kernel")
 
 
 def pmc_per_launch(path, counter, log):

@@ -1,4 +1,4 @@
-"""A/B of the persistent wide-tile blocks (gemm_w8.hip, w8p) against one-tile blocks (SCL_GEMM_PERSIST=0) on the encoder's multi-round
+"""A/B of the persistent wide-tile blocks (gemm_w8.hip, w8p) against one-tile blocks (SCL_W8_PERSIST=0) on the encoder's multi-round
 shapes and epilogues at batch 64 (M = 12736) or the M given: us per launch, interleaved rounds in one process, operands and outputs
 rotated over three buffer sets.  Environment is read per launch, so both variants run in the same process."""
 import os, sys
@@ -24,7 +24,7 @@ def bench(name, N, K, b_t, make_kw, variants, Mrows=None, a_op=None):
         sets.append((A, B, make_kw()))
     def run(i, env):
         A, B, (C, kw) = sets[i % 3]
-        os.environ["SCL_GEMM_PERSIST"] = env
+        os.environ["SCL_W8_PERSIST"] = env
         ops.gemm(Op(A, K), Op(B, N if b_t else K), C, Mr, N, K, b_t=b_t, **kw)
     times = {v: [] for v, _ in variants}
     for v, env in variants:

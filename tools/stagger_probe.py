@@ -1,4 +1,4 @@
-"""A/B of a start stagger of every other XCD (SCL_W8_STAGGER, units of ~3.9 us) -- derived from: A/B of the persistent wide-tile blocks (gemm_w8.hip, w8p) against one-tile blocks (SCL_GEMM_PERSIST=0) on the encoder's multi-round
+"""A/B of a start stagger of every other XCD (SCL_W8_STAGGER, units of ~3.9 us) -- derived from: A/B of the persistent wide-tile blocks (gemm_w8.hip, w8p) against one-tile blocks (SCL_W8_PERSIST=0) on the encoder's multi-round
 shapes and epilogues at batch 64 (M = 12736) or the M given: us per launch, interleaved rounds in one process, operands and outputs
 rotated over three buffer sets.  Environment is read per launch, so both variants run in the same process."""
 import os, sys
