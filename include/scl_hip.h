@@ -522,7 +522,9 @@ int scl_conv0_bwd(const float* x, const float* w, const float* bias, const float
 /* ------------------------------------------------------------------------------------------ */
 /* s[b][i][j] = sum_o tanh(sum_d W[o][d] x[b][i][d] x[b][j][d] + bias[o]) * a[t(i,j)][o];  t = 0 (i, j < n1), 1 (i, j >= n1),
  * 2 (mixed); the homogeneous layer passes n1 = N and only a[0] is used.  All f32.  x [B,N,D], W [Do,D], a [3,Do], s [B,N,N];
- * D in {32, 64}, Do <= 64, N <= 128.  Temperature and softmax stay with the caller. */
+ * D in {32, 64}, Do <= 64.  N <= 1024 for (D, Do) in {(64, 64), (64, 32), (32, 32)} (up to 128 nodes the whole-graph matrix-core kernels,
+ * above that tiled ones whose LDS does not grow with N); N <= 128 for every other Do.  scl_gat_score_nblocks(N) = ceil(N * N / 256) up to
+ * 128 nodes, ceil(N / 8) above.  Temperature and softmax stay with the caller. */
 int scl_gat_score_nblocks(int N);
 int scl_gat_score_fwd(const float* x, const float* W, const float* bias, const float* a, float* s, int B, int N, int D, int Do, int n1,
                       void* stream);

@@ -16,11 +16,17 @@
 //   d W[o][d] = sum_pairs d pre_o * x_i[d] x_j[d]                    (d pre tile in LDS, 16 outputs per thread)
 //   d p[d]    = sum_o d pre_o W[o][d]  -> dP[b][i][j][d] in HBM (the only N*N*D tensor), gathered by a second kernel into
 //   d x_i[d]  = sum_j (dP[i][j][d] + dP[j][i][d]) * x_j[d]           (deterministic: no atomics anywhere)
+//
+// Graph sizes: up to GAT_MAXN = 128 nodes the kernels keep a whole graph's x in LDS; 129 .. GAT_CAP = 1024 nodes (clips beyond 387 frames:
+// nT = T / 3 temporal nodes) run the tiled matrix-core forms further down, whose LDS does not grow with N.
 #include "common.h"
 
 namespace {
 
-constexpr int GAT_MAXN = 128;     // nodes per graph
+constexpr int GAT_MAXN = 128;     // nodes per graph of the whole-graph-in-LDS kernels (and of the scalar forms' byte-wide pair indices)
+constexpr int GAT_CAP = 1024;     // nodes per graph of the tiled matrix-core forms (999 temporal nodes: a 960,000-sample clip)
+constexpr int GAT_JT = 128;       // tiled forms: nodes j staged per tile
+constexpr int GAT_IPB = 8;        // tiled forms: nodes i a block owns (at most)
 constexpr int GAT_PAIRS = 256;    // pairs (= threads) per block
 constexpr int GAT_DPS = 68;       // row stride (floats) of the backward's d-pre tile [pair][o]: 16-byte aligned, 4-way banked
 
@@ -408,6 +414,219 @@ __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_bwd_mfma_kernel(const 
     for (int e = tid; e < 4 * Do; e += GAT_PAIRS) pb[(size_t)Do * D + e] = (red[e] + red[4 * Do + e]) + (red[8 * Do + e] + red[12 * Do + e]);
 }
 
+// ---- tiled matrix-core forms (N > GAT_MAXN) -----------------------------------------------------------------------------------------------
+// The same arithmetic per unit (one node i x 16 nodes j), but the LDS no longer holds the graph: a block owns ipb <= GAT_IPB consecutive
+// nodes i, keeps their rows of x for its whole life, and walks j in tiles of GAT_JT rows staged one after another into the same buffer
+// (two barriers per tile; a tile is (i1 - i0) * 8 units of ~64 MFMAs for a 32 KB load, so the re-staging is a few percent).  Rows of a tile
+// at or beyond N are zero and their pairs are masked as before.  The pair type comes from the global i and j, so n1 may fall anywhere in
+// any tile.  Units are dealt to the waves in a fixed order and the block partials are summed as in the whole-graph kernel: deterministic.
+template <int D>
+__device__ __forceinline__ void gat_stage_rows(float* xs, const float* __restrict__ xb, int r0, int rows, int N) {      // [rows][D + 1] <- x rows r0 .., rows >= N zero
+    for (int e = threadIdx.x; e < rows * D; e += GAT_PAIRS) {
+        const int r = e / D, d = e - r * D;
+        xs[r * (D + 1) + d] = r0 + r < N ? xb[(int64_t)(r0 + r) * D + d] : 0.f;
+    }
+}
+
+template <int D, int Do>
+__global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_fwd_tiled_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                                          const float* __restrict__ bias, const float* __restrict__ a,
+                                                                          float* __restrict__ s, int N, int n1) {
+    constexpr int NS = D / 4, NOB = Do / 16, XP = D + 1;
+    extern __shared__ float sm[];
+    float* xi = sm;                      // [GAT_IPB][XP]: the block's own rows
+    float* xj = sm + GAT_IPB * XP;       // [GAT_JT][XP]: the current tile of rows j
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int nblk = gridDim.x, ipb = (N + nblk - 1) / nblk;      // <= GAT_IPB (scl_gat_score_nblocks)
+    const int i0 = blockIdx.x * ipb, i1 = min(N, i0 + ipb);
+    const float* xb = x + (int64_t)b * N * D;
+    gat_stage_rows<D>(xi, xb, i0, GAT_IPB, N);
+    float wr[NOB][NS], bo[NOB], av[3][NOB];
+#pragma unroll
+    for (int ob = 0; ob < NOB; ++ob) {
+        const int o = 16 * ob + li;
+        bo[ob] = bias[o];
+#pragma unroll
+        for (int t = 0; t < 3; ++t) av[t][ob] = a[t * Do + o];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) wr[ob][k] = W[(size_t)o * D + 4 * k + g];
+    }
+    for (int t0 = 0; t0 < N; t0 += GAT_JT) {
+        __syncthreads();      // the previous tile's readers are done
+        gat_stage_rows<D>(xj, xb, t0, GAT_JT, N);
+        __syncthreads();
+        const int njb = (min(N - t0, GAT_JT) + 15) / 16;
+        for (int u = wave; u < (i1 - i0) * njb; u += GAT_PAIRS / 64) {
+            const int il = u / njb, jl = (u % njb) * 16, i = i0 + il, j0 = t0 + jl;
+            f32x4 acc[NOB];
+#pragma unroll
+            for (int ob = 0; ob < NOB; ++ob) acc[ob] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                const float pv = xi[il * XP + 4 * k + g] * xj[(jl + li) * XP + 4 * k + g];
+#pragma unroll
+                for (int ob = 0; ob < NOB; ++ob) acc[ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv, wr[ob][k], acc[ob], 0, 0, 0);
+            }
+            float sc[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = j0 + 4 * g + r;
+                const int ty = gat_type(i, j < N ? j : 0, n1);
+                float v = 0.f;
+#pragma unroll
+                for (int ob = 0; ob < NOB; ++ob) v += gat_tanh(acc[ob][r] + bo[ob]) * (ty == 0 ? av[0][ob] : (ty == 1 ? av[1][ob] : av[2][ob]));
+                sc[r] = lanes16_sum(v);
+            }
+            if (li == 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { const int j = j0 + 4 * g + r; if (j < N) s[((int64_t)b * N + i) * N + j] = sc[r]; }
+            }
+        }
+    }
+}
+
+template <int D, int Do>
+__global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_bwd_tiled_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                                          const float* __restrict__ bias, const float* __restrict__ a,
+                                                                          const float* __restrict__ ds, float* __restrict__ dP,
+                                                                          float* __restrict__ part, int N, int n1) {
+    constexpr int NS = D / 4, NOB = Do / 16, NDB = D / 16, NSO = Do / 4, XP = D + 1, TP = Do + 1, XROWS = GAT_IPB + GAT_JT;
+    extern __shared__ float sm[];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+    float* xi = sm;                                        // [GAT_IPB][XP]
+    float* xj = sm + GAT_IPB * XP;                         // [GAT_JT][XP]
+    float* Tw = sm + XROWS * XP + wave * 16 * TP;          // this wave's dpre tile [16 pairs][TP]
+    float* red = sm + XROWS * XP + 4 * 16 * TP;            // [4 waves][4 * Do]: db | da0 | da1 | da2
+    const int nblk = gridDim.x, ipb = (N + nblk - 1) / nblk;      // <= GAT_IPB (scl_gat_score_nblocks)
+    const int i0 = blockIdx.x * ipb, i1 = min(N, i0 + ipb);
+    const float* xb = x + (int64_t)b * N * D;
+    gat_stage_rows<D>(xi, xb, i0, GAT_IPB, N);
+    float wr[NOB][NS], wt[NDB][NSO], bo[NOB], av[3][NOB];
+#pragma unroll
+    for (int ob = 0; ob < NOB; ++ob) {
+        const int o = 16 * ob + li;
+        bo[ob] = bias[o];
+#pragma unroll
+        for (int t = 0; t < 3; ++t) av[t][ob] = a[t * Do + o];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) wr[ob][k] = W[(size_t)o * D + 4 * k + g];
+    }
+#pragma unroll
+    for (int db = 0; db < NDB; ++db)
+#pragma unroll
+        for (int k = 0; k < NSO; ++k) wt[db][k] = W[(size_t)(4 * k + g) * D + 16 * db + li];      // W^T: row d = 16 db + li, k <-> o = 4 k + g
+    f32x4 dwa[NOB][NDB];
+#pragma unroll
+    for (int ob = 0; ob < NOB; ++ob)
+#pragma unroll
+        for (int db = 0; db < NDB; ++db) dwa[ob][db] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float dbs[NOB], das[3][NOB];
+#pragma unroll
+    for (int ob = 0; ob < NOB; ++ob) { dbs[ob] = 0.f; das[0][ob] = 0.f; das[1][ob] = 0.f; das[2][ob] = 0.f; }
+    for (int t0 = 0; t0 < N; t0 += GAT_JT) {
+        __syncthreads();      // the previous tile's readers are done
+        gat_stage_rows<D>(xj, xb, t0, GAT_JT, N);
+        __syncthreads();
+        const int njb = (min(N - t0, GAT_JT) + 15) / 16;
+        for (int u = wave; u < (i1 - i0) * njb; u += GAT_PAIRS / 64) {
+            const int il = u / njb, jl = (u % njb) * 16, i = i0 + il, j0 = t0 + jl;
+            f32x4 acc[NOB];
+#pragma unroll
+            for (int ob = 0; ob < NOB; ++ob) acc[ob] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                const float pv = xi[il * XP + 4 * k + g] * xj[(jl + li) * XP + 4 * k + g];
+#pragma unroll
+                for (int ob = 0; ob < NOB; ++ob) acc[ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv, wr[ob][k], acc[ob], 0, 0, 0);
+            }
+            // this lane: outputs o = 16 ob + li of the pairs (i, j0 + 4 g + r)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = j0 + 4 * g + r;
+                const float gd = j < N ? ds[((int64_t)b * N + i) * N + j] : 0.f;
+                const int ty = gat_type(i, j < N ? j : 0, n1);
+#pragma unroll
+                for (int ob = 0; ob < NOB; ++ob) {
+                    const float h = gat_tanh(acc[ob][r] + bo[ob]);
+                    const float at = ty == 0 ? av[0][ob] : (ty == 1 ? av[1][ob] : av[2][ob]);
+                    const float gh = gd * h;
+                    das[0][ob] += ty == 0 ? gh : 0.f; das[1][ob] += ty == 1 ? gh : 0.f; das[2][ob] += ty == 2 ? gh : 0.f;
+                    const float dpre = gd * at * (1.0f - h * h);
+                    dbs[ob] += dpre;
+                    acc[ob][r] = dpre;
+                    Tw[(4 * g + r) * TP + 16 * ob + li] = dpre;
+                }
+            }
+            // dW[o][d] += sum_pairs dpre[pair][o] p[pair][d]:  rows = o, k = pairs (k index g <-> pair 4 g + r), columns = d
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+#pragma unroll
+                for (int db = 0; db < NDB; ++db) {
+                    const float pv = xi[il * XP + 16 * db + li] * xj[(jl + 4 * g + r) * XP + 16 * db + li];
+#pragma unroll
+                    for (int ob = 0; ob < NOB; ++ob) dwa[ob][db] = __builtin_amdgcn_mfma_f32_16x16x4f32(acc[ob][r], pv, dwa[ob][db], 0, 0, 0);
+                }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the tile's writes are this wave's own: in order, complete before the reads below
+            // dp^T[d][pair] = sum_o W[o][d] dpre[pair][o]:  rows = d, k = o, columns = pairs (j0 + li)
+            f32x4 dpa[NDB];
+#pragma unroll
+            for (int db = 0; db < NDB; ++db) dpa[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < NSO; ++k) {
+                const float tv = Tw[li * TP + 4 * k + g];
+#pragma unroll
+                for (int db = 0; db < NDB; ++db) dpa[db] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[db][k], tv, dpa[db], 0, 0, 0);
+            }
+            if (j0 + li < N) {
+                float* out = dP + (((int64_t)b * N + i) * N + j0 + li) * D;
+#pragma unroll
+                for (int db = 0; db < NDB; ++db) *reinterpret_cast<f32x4*>(out + 16 * db + 4 * g) = dpa[db];
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the reads are done before the next unit overwrites the tile
+        }
+    }
+    // ---- block partials, as in gat_score_bwd_mfma_kernel: dW through LDS wave by wave in order, then db / da
+    float* pb = part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * ((size_t)Do * D + 4 * Do);
+    __syncthreads();
+    float* wsum = sm;                                      // [Do * D] <= XROWS * XP (x is no longer needed); does not reach red
+    for (int w4 = 0; w4 < 4; ++w4) {
+        if (wave == w4) {
+#pragma unroll
+            for (int ob = 0; ob < NOB; ++ob)
+#pragma unroll
+                for (int db = 0; db < NDB; ++db)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int idx = (16 * ob + 4 * g + r) * D + 16 * db + li;
+                        wsum[idx] = (w4 == 0 ? 0.f : wsum[idx]) + dwa[ob][db][r];
+                    }
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < Do * D; e += GAT_PAIRS) pb[e] = wsum[e];
+#pragma unroll
+    for (int ob = 0; ob < NOB; ++ob) {
+        float v[4] = {dbs[ob], das[0][ob], das[1][ob], das[2][ob]};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            v[q] += __shfl_xor(v[q], 16, 64);
+            v[q] += __shfl_xor(v[q], 32, 64);
+            if (g == 0) red[wave * 4 * Do + q * Do + 16 * ob + li] = v[q];
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < 4 * Do; e += GAT_PAIRS) pb[(size_t)Do * D + e] = (red[e] + red[4 * Do + e]) + (red[8 * Do + e] + red[12 * Do + e]);
+}
+
+template <int D, int Do>
+constexpr size_t gat_tiled_lds(bool bwd) {      // independent of N: 35 KB forward, 56 KB backward at (64, 64)
+    size_t f = (size_t)(GAT_IPB + GAT_JT) * (D + 1);
+    if (bwd) f += 4 * 16 * (Do + 1) + 16 * Do;
+    return f * sizeof(float);
+}
+static_assert(gat_tiled_lds<64, 64>(true) <= 64 * 1024, "the tiled forms stay under the default dynamic-LDS limit");
+
 template <int D, int Do>
 size_t gat_mfma_lds(int N, bool bwd) {
     size_t f = (size_t)(N + 16) * (D + 1);
@@ -417,15 +636,32 @@ size_t gat_mfma_lds(int N, bool bwd) {
 
 }  // namespace
 
-extern "C" int scl_gat_score_nblocks(int N) { return (N * N + GAT_PAIRS - 1) / GAT_PAIRS; }
+// Up to GAT_MAXN nodes: one block per 256 pairs, as the whole-graph kernels always had.  Beyond: one block per GAT_IPB nodes i (the tiled
+// forms), so the partial-sum buffer grows with N, not with N * N.
+extern "C" int scl_gat_score_nblocks(int N) {
+    return N <= GAT_MAXN ? (N * N + GAT_PAIRS - 1) / GAT_PAIRS : (N + GAT_IPB - 1) / GAT_IPB;
+}
+
+namespace {
+bool gat_is_mfma(int D, int Do) { return (D == 64 && (Do == 64 || Do == 32)) || (D == 32 && Do == 32); }
+}  // namespace
 
 extern "C" int scl_gat_score_fwd(const float* x, const float* W, const float* bias, const float* a, float* s, int B, int N, int D, int Do,
                                  int n1, void* stream) {
     SCL_REQUIRE(x && W && bias && a && s && B > 0, "gat_score_fwd: null pointer");
-    SCL_REQUIRE((D == 64 || D == 32) && Do >= 1 && Do <= 64 && N >= 1 && N <= GAT_MAXN && n1 >= 0 && n1 <= N,
+    SCL_REQUIRE((D == 64 || D == 32) && Do >= 1 && Do <= 64 && N >= 1 && (N <= GAT_MAXN || gat_is_mfma(D, Do)) && n1 >= 0 && n1 <= N,
                 "gat_score_fwd: need D in {32, 64}, Do <= 64, N <= 128 (D=%d Do=%d N=%d)", D, Do, N);
+    SCL_REQUIRE(N <= GAT_CAP, "gat_score_fwd: at most %d nodes per graph (N=%d)", GAT_CAP, N);
     dim3 grid(scl_gat_score_nblocks(N), B), block(GAT_PAIRS);
     hipStream_t st = (hipStream_t)stream;
+    if (N > GAT_MAXN) {
+#define GAT_FWD_TILED(DD, OO) hipLaunchKernelGGL((gat_score_fwd_tiled_kernel<DD, OO>), grid, block, (gat_tiled_lds<DD, OO>(false)), st, x, W, bias, a, s, N, n1)
+        if (D == 64 && Do == 64) GAT_FWD_TILED(64, 64);
+        else if (D == 64 && Do == 32) GAT_FWD_TILED(64, 32);
+        else GAT_FWD_TILED(32, 32);
+#undef GAT_FWD_TILED
+        return scl_check_launch("scl_gat_score_fwd");
+    }
 #define GAT_FWD_MFMA(DD, OO) hipLaunchKernelGGL((gat_score_fwd_mfma_kernel<DD, OO>), grid, block, (gat_mfma_lds<DD, OO>(N, false)), st, x, W, bias, a, s, N, n1, (const int*)nullptr, (const int*)nullptr)
     if (D == 64 && Do == 64) { GAT_FWD_MFMA(64, 64); return scl_check_launch("scl_gat_score_fwd"); }
     if (D == 64 && Do == 32) { GAT_FWD_MFMA(64, 32); return scl_check_launch("scl_gat_score_fwd"); }
@@ -461,10 +697,23 @@ extern "C" int scl_gat_score_fwd_var(const float* x, const float* W, const float
 extern "C" int scl_gat_score_bwd(const float* x, const float* W, const float* bias, const float* a, const float* ds, float* dP, float* part,
                                  float* dx, int B, int N, int D, int Do, int n1, void* stream) {
     SCL_REQUIRE(x && W && bias && a && ds && dP && part && dx && B > 0, "gat_score_bwd: null pointer");
-    SCL_REQUIRE((D == 64 || D == 32) && Do >= 1 && Do <= 64 && N >= 1 && N <= GAT_MAXN && n1 >= 0 && n1 <= N,
+    SCL_REQUIRE((D == 64 || D == 32) && Do >= 1 && Do <= 64 && N >= 1 && (N <= GAT_MAXN || gat_is_mfma(D, Do)) && n1 >= 0 && n1 <= N,
                 "gat_score_bwd: need D in {32, 64}, Do <= 64, N <= 128 (D=%d Do=%d N=%d)", D, Do, N);
+    SCL_REQUIRE(N <= GAT_CAP, "gat_score_bwd: at most %d nodes per graph (N=%d)", GAT_CAP, N);
     dim3 grid(scl_gat_score_nblocks(N), B), block(GAT_PAIRS);
     hipStream_t st = (hipStream_t)stream;
+    if (N > GAT_MAXN) {
+#define GAT_BWD_TILED(DD, OO)                                                                                                                         \
+    do {                                                                                                                                               \
+        hipLaunchKernelGGL((gat_score_bwd_tiled_kernel<DD, OO>), grid, block, (gat_tiled_lds<DD, OO>(true)), st, x, W, bias, a, ds, dP, part, N, n1);    \
+        hipLaunchKernelGGL((gat_dx_kernel<DD>), dim3(N, B), dim3(4 * DD), 0, st, dP, x, dx, N);                                                        \
+    } while (0)
+        if (D == 64 && Do == 64) GAT_BWD_TILED(64, 64);
+        else if (D == 64 && Do == 32) GAT_BWD_TILED(64, 32);
+        else GAT_BWD_TILED(32, 32);
+#undef GAT_BWD_TILED
+        return scl_check_launch("scl_gat_score_bwd");
+    }
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute((const void*)gat_score_bwd_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

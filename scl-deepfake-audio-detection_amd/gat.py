@@ -9,6 +9,9 @@ import torch
 
 from . import ops
 
+# The backward's only N * N * D tensor, dP [B, N, N, D] f32 (4.1 GB at B = 64, N = 500; 16.4 GB at B = 64 and the 999 nodes of a
+# 960,000-sample clip): beyond this it is a ValueError, not an allocator failure in the middle of a backward.
+MAX_DP_BYTES = 16 << 30
 
 class _GatScoreFn(torch.autograd.Function):
     @staticmethod
@@ -31,6 +34,9 @@ class _GatScoreFn(torch.autograd.Function):
         Do = W.shape[0]
         nb = ops.gat_score_nblocks(N) * B
         ncol = Do * D + 4 * Do
+        if B * N * N * D * 4 > MAX_DP_BYTES:
+            raise ValueError("gat_score backward: the pair-gradient scratch dP [B=%d, N=%d, N, D=%d] f32 is %.1f GiB, above the %d GiB bound "
+                             "(MAX_DP_BYTES); use a smaller batch" % (B, N, D, B * N * N * D * 4 / 2 ** 30, MAX_DP_BYTES >> 30))
         dP = torch.empty(B * N * N * D, device=x.device, dtype=torch.float32)
         part = torch.empty(nb, ncol, device=x.device, dtype=torch.float32)
         dx = torch.empty_like(x)
