@@ -236,6 +236,12 @@ int scl_bn_bwd(const float* dy, const float* y, const float* x, const float* mea
  * there (it may hold NaN / Inf).  mean / rstd [C]: scratch, written.  One apply launch, no zeroing pass.  C a power of two <= 2048; C % 4 == 0: 16-byte aligned pointers. */
 int scl_bn_eval_masked(const float* x, int B, int H, int W, int C, const float* gamma, const float* beta, const float* running_mean,
                        const float* running_var, float eps, int act, const int32_t* valid, float* mean, float* rstd, float* y, void* stream);
+/* The column-mask form of scl_bn_eval_masked: utterance b owns the columns w < widths[b] (int32 [B] on the GPU, clamped to 0..W) of every row
+ * of x [B, H, W, C].  Own columns: the bits scl_bn_fwd (training = 0) gives; at and beyond widths[b]: exactly 0.0f, selected, x not read. */
+int scl_bn_eval_cols(const float* x, int B, int H, int W, int C, const float* gamma, const float* beta, const float* running_mean,
+                     const float* running_var, float eps, int act, const int32_t* widths, float* mean, float* rstd, float* y, void* stream);
+/* In place: x[b][h][w][:] = 0.0f for w >= widths[b] (stored, whatever x held: NaN / Inf included); the own columns are not touched. */
+int scl_zero_cols(float* x, int B, int H, int W, int C, const int32_t* widths, void* stream);
 /* Train-mode BatchNorm + activation of a zero-padded variable-length batch of maps x [B, H, W, C]: utterance b owns the rows h < valid[b]
  * (int32 [B] on the GPU, clamped to 0..H as scl_bn_eval_masked clamps) and N_v = W * sum_b valid[b] is counted on the device from that array.
  * Mean and biased variance per channel over the N_v valid positions only (fixed-order reduction, fp64 partials, no atomics: two runs give the
@@ -538,6 +544,16 @@ int scl_gat_score_bwd(const float* x, const float* W, const float* bias, const f
  * [nodes[b]][nodes[b]] matrix, contiguous at the start of its Nmax * Nmax block.  The matrix-core forms only: (D, Do) in {(64, 64), (64, 32), (32, 32)}. */
 int scl_gat_score_fwd_var(const float* x, const float* W, const float* bias, const float* a, float* s, const int32_t* nodes, const int32_t* n1,
                           int B, int Nmax, int D, int Do, void* stream);
+/* Nmax <= 128: the whole-graph kernel; 129 .. 1024: the tiled one with N_b, n1_b per utterance (blocks of 8 rows; a block at or beyond N_b
+ * returns before any barrier; the j tile loop ends at N_b; fixed 35 KB of LDS).  Above 128 nodes n1 == NULL is refused: a homogeneous layer
+ * passes nodes as n1.
+ *
+ * Masked soft-max and aggregation in one pass (scoring): out[b][i][:] = sum_{j < nodes[b]} softmax_j(s[b][i][j] / temp) * x[b][j][:] for
+ * i < nodes[b] - F.softmax(s / temp, -1) @ x without the attention matrix in HBM.  s in scl_gat_score_fwd_var's layout, x [B, Nmax, D],
+ * D in {32, 64}, out [B, Nmax, D] whose rows i >= nodes[b] are WRITTEN AS ZEROS.  Scores and x rows at and beyond nodes[b] are not read.
+ * one_row != 0: s [B, Nmax] is one score row per utterance and out is [B, D] (the master node's softmax over the nodes).  Nmax <= 1024. */
+int scl_gat_softmax_agg_var(const float* s, const float* x, const int32_t* nodes, float* out, int B, int Nmax, int D, int one_row, float temp,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* AASIST RawNet2-style encoder: the six Residual_blocks (model/wav2vec2_aasist.py:377-433,     */

@@ -41,7 +41,7 @@ VARLEN_SCORING_MODELS = ("wav2vec2_btse",)
 
 
 def _scores_varlen(name):
-    return name in VARLEN_MODELS or name in VARLEN_SCORING_MODELS or os.environ.get(VARLEN_SCORING_OPT_IN.get(name, ""), "0") == "1"
+    return name in VARLEN_MODELS or name in VARLEN_SCORING_MODELS or os.environ.get(VARLEN_SCORING_OPT_IN.get(name, ""), "0") in ("1", "long")
 
 
 class EarlyStop:

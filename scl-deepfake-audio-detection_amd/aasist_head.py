@@ -15,7 +15,8 @@ utterance only through a convolution's taps, the soft-max over the time axis and
 written as exact zeros (selected, not multiplied) at and beyond the utterance's width — what the convolution's zero border holds for the
 utterance alone — the attention pooling runs over the utterance's own columns, and the graph kernels take their node counts per utterance
 (node_counts; csrc/resstack.hip, gat.hip, graph.hip).  The masks live in the fused kernels, so the mode has their limits:
-min_frames() .. max_frames() frames per utterance.
+min_frames() .. max_frames() frames per utterance.  Beyond them AasistHead.forward_frames_long (aasist_long.py, SCL_AASIST_LENGTHS=long) keeps the
+same contract on the per-layer composition with count tables, up to 3074 frames.
 
 Reference quirks kept on purpose: Residual_block applies conv1 to its INPUT (the bn1+SELU result is discarded, :414-420; in training
 that BatchNorm still updates its running statistics); the temporal / spectral attention pools share one 1x1-conv score map.
@@ -274,6 +275,12 @@ class AasistHead(nn.Module):
         blocks = [blk[0] for blk in self.encoder]
         e_S, e_T = resstack.res_stack_pool_widths(x, counts["W"], blocks, self.first_bn1, self.attention, self.pos_S)
         return graph.graph_module_counts(e_S, e_T, self, counts)
+
+    def forward_frames_long(self, feats, frames):
+        """forward_frames for utterances of up to aasist_long.MAX_FRAMES = 3074 frames (1024 temporal nodes): the same contract on the
+        per-layer composition with count tables (aasist_long.py), independent of SCL_AASIST_FUSED / SCL_AASIST_FUSED_GRAPH."""
+        from . import aasist_long
+        return aasist_long.forward_frames_long(self, feats, frames)
 
     def graph_unfused(self, e_S, e_T):
         """The graph module as a composition of per-operation autograd Functions (round 2): the fall-back for graph sizes the fused

@@ -428,18 +428,34 @@ __device__ __forceinline__ void gat_stage_rows(float* xs, const float* __restric
     }
 }
 
-template <int D, int Do>
+// VAR (scoring): graphs of different sizes in one batch, as the whole-graph VAR kernel above.  N is the batch's Nmax (x [B, Nmax, D], the
+// grid ceil(Nmax / GAT_IPB) blocks of GAT_IPB rows each); the utterance's own N_b = nodes[b] and n1_b = n1s[b] replace N and n1 everywhere
+// below: the tile loop ends at N_b, the pair type is the utterance's own, s is its own [N_b][N_b] matrix at the start of its Nmax * Nmax
+// block.  A block whose first row is at or beyond N_b leaves before the first barrier; all of this is uniform in a workgroup.  A pair's
+// arithmetic does not depend on which block owns its row, so the bits are those of the utterance scored alone by the fixed form.
+template <int D, int Do, bool VAR = false>
 __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_fwd_tiled_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                                           const float* __restrict__ bias, const float* __restrict__ a,
-                                                                          float* __restrict__ s, int N, int n1) {
+                                                                          float* __restrict__ s, int N, int n1, const int* __restrict__ nodes = nullptr,
+                                                                          const int* __restrict__ n1s = nullptr) {
     constexpr int NS = D / 4, NOB = Do / 16, XP = D + 1;
     extern __shared__ float sm[];
     float* xi = sm;                      // [GAT_IPB][XP]: the block's own rows
     float* xj = sm + GAT_IPB * XP;       // [GAT_JT][XP]: the current tile of rows j
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
-    const int nblk = gridDim.x, ipb = (N + nblk - 1) / nblk;      // <= GAT_IPB (scl_gat_score_nblocks)
+    const float* xb = x + (int64_t)b * N * D;      // the padded batch's stride (VAR: N is still Nmax here)
+    float* sb = s + (int64_t)b * N * N;
+    int ipb = GAT_IPB;
+    if (VAR) {
+        const int Nmax = N;
+        N = nodes[b]; N = N < 1 ? 1 : (N > Nmax ? Nmax : N);
+        n1 = n1s ? n1s[b] : N; n1 = n1 < 0 ? 0 : (n1 > N ? N : n1);
+        if ((int)blockIdx.x * GAT_IPB >= N) return;
+    } else {
+        const int nblk = gridDim.x;
+        ipb = (N + nblk - 1) / nblk;      // <= GAT_IPB (scl_gat_score_nblocks)
+    }
     const int i0 = blockIdx.x * ipb, i1 = min(N, i0 + ipb);
-    const float* xb = x + (int64_t)b * N * D;
     gat_stage_rows<D>(xi, xb, i0, GAT_IPB, N);
     float wr[NOB][NS], bo[NOB], av[3][NOB];
 #pragma unroll
@@ -479,7 +495,7 @@ __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_fwd_tiled_kernel(const
             }
             if (li == 0) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { const int j = j0 + 4 * g + r; if (j < N) s[((int64_t)b * N + i) * N + j] = sc[r]; }
+                for (int r = 0; r < 4; ++r) { const int j = j0 + 4 * g + r; if (j < N) sb[(int64_t)i * N + j] = sc[r]; }
             }
         }
     }
@@ -619,6 +635,98 @@ __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_bwd_tiled_kernel(const
     for (int e = tid; e < 4 * Do; e += GAT_PAIRS) pb[(size_t)Do * D + e] = (red[e] + red[4 * Do + e]) + (red[8 * Do + e] + red[12 * Do + e]);
 }
 
+// Masked soft-max and aggregation in one pass (scoring): out[b][i][:] = sum_{j < N_b} softmax_j(s[b][i][j] / temp) * x[b][j][:] for the rows
+// i < N_b, what F.softmax(s / temp, -1) followed by att @ x computes, without the [N][N] attention matrix in HBM.  s is read once, in the
+// layout scl_gat_score_fwd_var writes (the utterance's own [N_b][N_b] matrix at the start of its Nmax * Nmax block); x is [B, Nmax, D].
+// A block owns AGG_IPB = 16 rows i and walks j in tiles of AGG_JT = 64: the tile's scores become p = exp(s / temp - m) against a running row
+// maximum m (the running sum and the accumulators are rescaled by exp(m_old - m_new) when it moves), p and the x tile wait in LDS, and wave w
+// adds P [16 x 64] * x [64 x 16 columns w] on the f32 matrix core.  LDS is fixed: 16 x 65 + 64 x (D + 16) floats, 24.5 KB at D = 64.  Scores
+// and x rows at and beyond N_b are never read (p = 0 and x = 0 are selected).  Rows i >= N_b of out are WRITTEN AS ZEROS.  ONE = true: a
+// single score row per utterance (s [B, Nmax], out [B, D]): the master node's softmax(am, dim = -2)^T x.  The tile and row partition is
+// fixed, so an utterance's bits do not depend on the batch it sits in.
+constexpr int AGG_IPB = 16, AGG_JT = 64, AGG_PS = AGG_JT + 1;
+
+__device__ __forceinline__ float lanes16_max_x(float v) {
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+    return v;
+}
+__device__ __forceinline__ float lanes16_sum_x(float v) {
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+template <int D, bool ONE>
+__global__ __launch_bounds__(256) void gat_softmax_agg_kernel(const float* __restrict__ s, const float* __restrict__ x, const int* __restrict__ nodes,
+                                                              float* __restrict__ out, int Nmax, float temp) {
+    constexpr int NOB = D / 16, XS = D + 16;
+    __shared__ float ps[AGG_IPB * AGG_PS];      // p of the tile [row][j]
+    __shared__ float xs[AGG_JT * XS];           // x rows of the tile
+    __shared__ float rs[2 * AGG_IPB];           // per row: this tile's rescale factor | at the end the running sum
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+    int N = nodes[b]; N = N < 1 ? 1 : (N > Nmax ? Nmax : N);
+    const int rows = ONE ? 1 : N, rows_max = ONE ? 1 : Nmax;
+    const int i0 = blockIdx.x * AGG_IPB;
+    float* ob_ = out + (int64_t)b * rows_max * D;
+    if (i0 >= rows) {      // a block wholly beyond the utterance's rows: zeros, and out before any barrier (uniform in the workgroup)
+        for (int e = tid; e < AGG_IPB * D; e += 256) { const int r = i0 + e / D; if (r < rows_max) ob_[(int64_t)r * D + (e % D)] = 0.f; }
+        return;
+    }
+    const float* sb = s + (int64_t)b * (ONE ? Nmax : (int64_t)Nmax * Nmax);
+    const float* xb = x + (int64_t)b * Nmax * D;
+    const int row = tid >> 4, c = tid & 15, gi = i0 + row;      // the soft-max stage: 16 threads per row, 4 scores each
+    const bool own = gi < rows;
+    float m_run = -INFINITY, l_run = 0.f;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t0 = 0; t0 < N; t0 += AGG_JT) {
+        float v[4], tmax = -INFINITY;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = t0 + c + 16 * q;
+            v[q] = (own && j < N) ? sb[(int64_t)gi * N + j] / temp : -INFINITY;
+            tmax = fmaxf(tmax, v[q]);
+        }
+        tmax = lanes16_max_x(tmax);
+        const float m_new = fmaxf(m_run, tmax);
+        const float sc = (m_new == -INFINITY) ? 0.f : expf(m_run - m_new);      // rows beyond the utterance keep p = 0, sc = 0
+        float psum = 0.f;
+        __syncthreads();      // the previous tile's readers are done
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float p = v[q] == -INFINITY ? 0.f : expf(v[q] - m_new);
+            ps[row * AGG_PS + c + 16 * q] = p;
+            psum += p;
+        }
+        l_run = l_run * sc + lanes16_sum_x(psum);
+        m_run = m_new;
+        if (c == 0) rs[row] = sc;
+        for (int e = tid; e < AGG_JT * D; e += 256) {
+            const int r = e / D, d = e - r * D;
+            xs[r * XS + d] = t0 + r < N ? xb[(int64_t)(t0 + r) * D + d] : 0.f;
+        }
+        __syncthreads();
+        if (wave < NOB) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] *= rs[4 * g + r];
+#pragma unroll
+            for (int kk = 0; kk < AGG_JT / 4; ++kk)
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ps[li * AGG_PS + 4 * kk + g], xs[(4 * kk + g) * XS + 16 * wave + li], acc, 0, 0, 0);
+        }
+    }
+    __syncthreads();
+    if (c == 0) rs[AGG_IPB + row] = l_run;
+    __syncthreads();
+    if (wave < NOB) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = i0 + 4 * g + r;
+            if (i < rows) ob_[(int64_t)i * D + 16 * wave + li] = acc[r] / rs[AGG_IPB + 4 * g + r];
+            else if (i < rows_max) ob_[(int64_t)i * D + 16 * wave + li] = 0.f;
+        }
+    }
+}
+
 template <int D, int Do>
 constexpr size_t gat_tiled_lds(bool bwd) {      // independent of N: 35 KB forward, 56 KB backward at (64, 64)
     size_t f = (size_t)(GAT_IPB + GAT_JT) * (D + 1);
@@ -680,16 +788,43 @@ extern "C" int scl_gat_score_fwd(const float* x, const float* W, const float* bi
 extern "C" int scl_gat_score_fwd_var(const float* x, const float* W, const float* bias, const float* a, float* s, const int32_t* nodes, const int32_t* n1,
                                      int B, int Nmax, int D, int Do, void* stream) {
     SCL_REQUIRE(x && W && bias && a && s && nodes && B > 0, "scl_gat_score_fwd_var: null pointer");
-    SCL_REQUIRE(((D == 64 && (Do == 64 || Do == 32)) || (D == 32 && Do == 32)) && Nmax >= 1 && Nmax <= GAT_MAXN,
-                "scl_gat_score_fwd_var: the matrix-core forms only: (D, Do) in {(64, 64), (64, 32), (32, 32)}, Nmax <= 128 (D=%d Do=%d Nmax=%d)", D, Do, Nmax);
+    SCL_REQUIRE(((D == 64 && (Do == 64 || Do == 32)) || (D == 32 && Do == 32)) && Nmax >= 1 && Nmax <= GAT_CAP,
+                "scl_gat_score_fwd_var: the matrix-core forms only: (D, Do) in {(64, 64), (64, 32), (32, 32)}, Nmax <= %d (D=%d Do=%d Nmax=%d)", GAT_CAP, D,
+                Do, Nmax);
+    SCL_REQUIRE(Nmax <= GAT_MAXN || n1, "scl_gat_score_fwd_var: above %d nodes the tiled form reads both tables: n1 == NULL is refused (a homogeneous "
+                "layer passes nodes as n1) (Nmax=%d)", GAT_MAXN, Nmax);
     dim3 grid(scl_gat_score_nblocks(Nmax), B), block(GAT_PAIRS);
     hipStream_t st = (hipStream_t)stream;
+    if (Nmax > GAT_MAXN) {    // the tiled form: ceil(Nmax / GAT_IPB) blocks of GAT_IPB rows per utterance (what scl_gat_score_nblocks gives above GAT_MAXN)
+#define GAT_FWD_TILED_VAR(DD, OO) hipLaunchKernelGGL((gat_score_fwd_tiled_kernel<DD, OO, true>), grid, block, (gat_tiled_lds<DD, OO>(false)), st, x, W, bias, a, s, Nmax, 0, nodes, n1)
+        if (D == 64 && Do == 64) GAT_FWD_TILED_VAR(64, 64);
+        else if (D == 64 && Do == 32) GAT_FWD_TILED_VAR(64, 32);
+        else GAT_FWD_TILED_VAR(32, 32);
+#undef GAT_FWD_TILED_VAR
+        return scl_check_launch("scl_gat_score_fwd_var");
+    }
 #define GAT_FWD_VAR(DD, OO) hipLaunchKernelGGL((gat_score_fwd_mfma_kernel<DD, OO, true>), grid, block, (gat_mfma_lds<DD, OO>(Nmax, false)), st, x, W, bias, a, s, Nmax, 0, nodes, n1)
     if (D == 64 && Do == 64) GAT_FWD_VAR(64, 64);
     else if (D == 64 && Do == 32) GAT_FWD_VAR(64, 32);
     else GAT_FWD_VAR(32, 32);
 #undef GAT_FWD_VAR
     return scl_check_launch("scl_gat_score_fwd_var");
+}
+
+// out[b][i][:] = sum_{j < nodes[b]} softmax_j(s[b][i][j] / temp) x[b][j][:], s as scl_gat_score_fwd_var lays it out, x [B, Nmax, D], out [B, Nmax, D]
+// with its rows i >= nodes[b] written as zeros.  one_row: s [B, Nmax] holds a single score row per utterance and out is [B, D].
+extern "C" int scl_gat_softmax_agg_var(const float* s, const float* x, const int32_t* nodes, float* out, int B, int Nmax, int D, int one_row, float temp,
+                                       void* stream) {
+    SCL_REQUIRE(s && x && nodes && out && B > 0 && B <= 65535, "scl_gat_softmax_agg_var: null pointer or batch beyond 65535");
+    SCL_REQUIRE((D == 64 || D == 32) && Nmax >= 1 && Nmax <= GAT_CAP && temp > 0.f, "scl_gat_softmax_agg_var: need D in {32, 64}, 1 <= Nmax <= %d, temp > 0 (D=%d Nmax=%d)",
+                GAT_CAP, D, Nmax);
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(one_row ? 1 : (Nmax + AGG_IPB - 1) / AGG_IPB, B), block(256);
+    if (D == 64 && one_row) hipLaunchKernelGGL((gat_softmax_agg_kernel<64, true>), grid, block, 0, st, s, x, nodes, out, Nmax, temp);
+    else if (D == 64) hipLaunchKernelGGL((gat_softmax_agg_kernel<64, false>), grid, block, 0, st, s, x, nodes, out, Nmax, temp);
+    else if (one_row) hipLaunchKernelGGL((gat_softmax_agg_kernel<32, true>), grid, block, 0, st, s, x, nodes, out, Nmax, temp);
+    else hipLaunchKernelGGL((gat_softmax_agg_kernel<32, false>), grid, block, 0, st, s, x, nodes, out, Nmax, temp);
+    return scl_check_launch("scl_gat_softmax_agg_var");
 }
 
 // dP: f32 [B, N*N, D] scratch; part: f32 [B * nblocks(N)][Do*D + 4*Do] partial sums (dW | dbias | da11 | da22 | da12), to be

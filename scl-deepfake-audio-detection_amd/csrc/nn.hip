@@ -318,6 +318,52 @@ __global__ __launch_bounds__(256) void bn_apply_masked_kernel(const float* __res
     }
 }
 
+// The column-mask forms (the AASIST stack's ragged axis is the map's column w, not its row h): utterance b owns the columns w < widths[b]
+// of x [B, H, W, C].  bn_apply_cols_kernel: eval BatchNorm + activation there with bn_elem's arithmetic (the bits of the unmasked kernel),
+// exactly 0 at and beyond (selected: x is not read).  zero_cols_kernel: in place, 0 stored at and beyond; the own columns are not touched.
+__device__ __forceinline__ int valid_cols(const int* __restrict__ widths, int b, int W) { const int v = widths[b]; return v < 0 ? 0 : (v > W ? W : v); }
+
+__global__ __launch_bounds__(256) void bn_apply_cols_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            const int* __restrict__ widths, long long per, int W, int C, int act, float* __restrict__ y) {
+    const int b = blockIdx.y;
+    const int wb = valid_cols(widths, b, W);
+    const float* __restrict__ xb = x + (long long)b * per;
+    float* __restrict__ yb = y + (long long)b * per;
+    if ((C & 3) == 0) {       // a 16-byte vector lies inside one position (h, w): own or padding as a whole
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < (per >> 2); q += (long long)gridDim.x * 256) {
+            const long long e = q << 2;
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            if ((int)((e / C) % W) < wb) o = bn_elem4(act, xb, mean, rstd, gamma, beta, e, (int)(e & (C - 1)));
+            *reinterpret_cast<float4*>(yb + e) = o;
+        }
+        return;
+    }
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long long)gridDim.x * 256) {
+        float o = 0.f;
+        if ((int)((e / C) % W) < wb) {
+            const int c = (int)(e & (C - 1));
+            o = bn_elem(act, xb[e], mean[c], rstd[c], gamma ? gamma[c] : 1.f, beta ? beta[c] : 0.f);
+        }
+        yb[e] = o;
+    }
+}
+
+__global__ __launch_bounds__(256) void zero_cols_kernel(float* __restrict__ x, const int* __restrict__ widths, long long per, int W, int C) {
+    const int b = blockIdx.y;
+    const int wb = valid_cols(widths, b, W);
+    float* __restrict__ xb = x + (long long)b * per;
+    if ((C & 3) == 0) {
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < (per >> 2); q += (long long)gridDim.x * 256) {
+            const long long e = q << 2;
+            if ((int)((e / C) % W) >= wb) *reinterpret_cast<float4*>(xb + e) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return;
+    }
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long long)gridDim.x * 256)
+        if ((int)((e / C) % W) >= wb) xb[e] = 0.f;
+}
+
 // backward, pass 1: per slab and channel (sum dz, sum dz * xhat) on bn_stats_kernel's partition - the masked form's slabs end at the
 // utterance's last valid row, so dy, y and x of the padding are not loaded
 template <bool MASKED>
@@ -631,6 +677,29 @@ extern "C" int scl_bn_eval_masked(const float* x, int B, int H, int W, int C, co
     const long long per = (long long)H * W * C;
     hipLaunchKernelGGL(bn_apply_masked_kernel, masked_grid(per, B, C), dim3(256), 0, s, x, mean, rstd, gamma, beta, valid, per, W * C, H, C, act, y);
     return scl_check_launch("scl_bn_eval_masked");
+}
+
+extern "C" int scl_bn_eval_cols(const float* x, int B, int H, int W, int C, const float* gamma, const float* beta, const float* running_mean,
+                                const float* running_var, float eps, int act, const int32_t* widths, float* mean, float* rstd, float* y, void* stream) {
+    SCL_REQUIRE(x && running_mean && running_var && widths && mean && rstd && y, "bn_eval_cols: null argument (running statistics: eval mode only)");
+    if (int rc = bn_masked_args_ok("bn_eval_cols", B, H, W, C, act, nullptr,
+                                   (uintptr_t)x | (uintptr_t)y | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)beta,
+                                   "x, y, mean, rstd, gamma, beta")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_finish_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, (const double*)nullptr, 0, 1, C, eps, 0.f, 0, const_cast<float*>(running_mean),
+                       const_cast<float*>(running_var), (long long*)nullptr, mean, rstd);
+    const long long per = (long long)H * W * C;
+    hipLaunchKernelGGL(bn_apply_cols_kernel, masked_grid(per, B, C), dim3(256), 0, s, x, mean, rstd, gamma, beta, widths, per, W, C, act, y);
+    return scl_check_launch("scl_bn_eval_cols");
+}
+
+extern "C" int scl_zero_cols(float* x, int B, int H, int W, int C, const int32_t* widths, void* stream) {
+    SCL_REQUIRE(x && widths && B >= 1 && B <= 65535 && H >= 1 && W >= 1 && C >= 1, "zero_cols: need x, widths, 1 <= B <= 65535, H, W, C >= 1");
+    SCL_REQUIRE((long long)H * W * C < (1ll << 31), "zero_cols: H * W * C of one utterance must stay below 2^31");
+    SCL_REQUIRE((C & 3) != 0 || ((uintptr_t)x & 15) == 0, "zero_cols: C %% 4 == 0 takes a 16-byte aligned x");
+    const long long per = (long long)H * W * C;
+    hipLaunchKernelGGL(zero_cols_kernel, masked_grid(per, B, C), dim3(256), 0, (hipStream_t)stream, x, widths, per, W, C);
+    return scl_check_launch("scl_zero_cols");
 }
 
 extern "C" int scl_bn_masked_nslabs(int B, int H, int W) {

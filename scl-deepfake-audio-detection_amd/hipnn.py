@@ -355,6 +355,28 @@ def batch_norm(x, bn, act=ACT_NONE, grad_in_place=False, valid=None, counts=None
                               momentum, bn.eps, act, grad_in_place)
 
 
+def batch_norm_cols(x, bn, act, widths):
+    """Eval-mode BatchNorm + `act` of x [B, H, W, C] under torch.no_grad() with the mask on the COLUMNS: utterance b owns w < widths[b]
+    (int32 [B] on the GPU) of every row and gets there the bits batch_norm gives without a mask; everything at and beyond is exactly 0,
+    whatever x holds (selected: not read).  The AASIST stack's ragged axis (aasist_long.py); `valid` of batch_norm masks the rows h."""
+    if bn.training or bn.running_mean is None or torch.is_grad_enabled() or x.dim() != 4:
+        raise NotImplementedError("hipnn.batch_norm_cols: a scoring mode (a BatchNorm in eval mode under torch.no_grad()) on a [B, H, W, C] map")
+    B, H, W, C = x.shape
+    xc = x.contiguous().float()
+    mean, rstd = torch.empty(C, device=x.device), torch.empty(C, device=x.device)
+    y = torch.empty_like(xc)
+    ops.bn_eval_cols(xc, B, H, W, C, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, act, widths, mean, rstd, y)
+    return y
+
+
+def zero_cols_(x, widths):
+    """In place, under torch.no_grad(): x [B, H, W, C] (contiguous f32) gets exact zeros stored at the columns w >= widths[b]."""
+    if torch.is_grad_enabled() or x.dim() != 4 or not x.is_contiguous() or x.dtype != torch.float32:
+        raise NotImplementedError("hipnn.zero_cols_: a contiguous f32 [B, H, W, C] map under torch.no_grad()")
+    ops.zero_cols(x, *x.shape, widths)
+    return x
+
+
 # ---- Linear / bmm ----------------------------------------------------------------------------------------------------------------------
 class _LinearFn(torch.autograd.Function):
     @staticmethod

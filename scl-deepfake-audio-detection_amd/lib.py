@@ -134,6 +134,8 @@ def _protos():
                         _i64, _i64, _vp], _i32),
         "scl_bn_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp], _i32),
         "scl_bn_eval_masked": ([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _vp], _i32),
+        "scl_bn_eval_cols": ([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _vp], _i32),
+        "scl_zero_cols": ([_vp, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
         "scl_pad_nhwc_f32": ([_vp, _i64, _i32, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _vp], _i32),
         "scl_conv_pack_weights": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
         "scl_conv_wgrad_finish": ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
@@ -217,6 +219,7 @@ def _protos():
         "scl_gat_score_fwd": ([_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
         "scl_gat_score_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
         "scl_gat_score_fwd_var": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
+        "scl_gat_softmax_agg_var": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp], _i32),
         "scl_dropout_rows": ([_vp, _vp, _i64, _i32, _i32, _i32, _u32, _f32, _vp], _i32),
         # resstack.hip
         "scl_rs_conv": ([P(SclRsConv), _vp], _i32),

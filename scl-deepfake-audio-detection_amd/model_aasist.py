@@ -34,25 +34,45 @@ class Model(FrontHeadModel):
         self.__dict__["pool_cfg"] = head.pool_cfg
         return head
 
+    LENGTHS_SWITCH = "SCL_AASIST_LENGTHS"
+
+    @staticmethod
+    def _lengths_mode():
+        """SCL_AASIST_LENGTHS, read at call time: "1" (the fused kernels, up to 242 frames), "long" (beyond them the per-layer composition
+        with count tables, up to 3074 frames) or off."""
+        v = os.environ.get(Model.LENGTHS_SWITCH, "0")
+        return v if v in ("1", "long") else "0"
+
     @staticmethod
     def _head_forward(mod, feats, frames=None):
-        return AasistHead.forward(mod, feats) if frames is None else AasistHead.forward_frames(mod, feats, frames)
-
-    LENGTHS_SWITCH = "SCL_AASIST_LENGTHS"
+        if frames is None:
+            return AasistHead.forward(mod, feats)
+        # long: a batch whose longest utterance fits the fused kernels takes them (the bits of SCL_AASIST_LENGTHS=1); any longer one goes whole
+        if Model._lengths_mode() == "long" and max(int(t) for t in frames) > aasist_head.max_frames(mod.pool_cfg):
+            return AasistHead.forward_frames_long(mod, feats, frames)
+        return AasistHead.forward_frames(mod, feats, frames)
 
     @property
     def head_takes_frames(self):
-        """forward(x, lengths) is opt-in for this plugin: SCL_AASIST_LENGTHS=1, read at call time."""
-        return os.environ.get(self.LENGTHS_SWITCH, "0") == "1"
+        """forward(x, lengths) is opt-in for this plugin: SCL_AASIST_LENGTHS=1 or =long, read at call time."""
+        return self._lengths_mode() != "0"
 
     def head_min_frames(self):
         return aasist_head.min_frames()
 
     def head_max_frames(self):
+        if self._lengths_mode() == "long":
+            from . import aasist_long
+            return aasist_long.MAX_FRAMES
         return aasist_head.max_frames(self.pool_cfg)
 
     def forward(self, x, lengths=None):
-        if lengths is not None and self.head_takes_frames and not AasistHead.frames_supported(self):
+        if lengths is not None and self._lengths_mode() == "long" and max(int(n) for n in lengths) > self.cfg.samples_for(aasist_head.max_frames(self.pool_cfg) + 1) - 1:
+            from . import aasist_long
+            if not aasist_long.widths_supported(self):      # the long path does not depend on SCL_AASIST_FUSED / SCL_AASIST_FUSED_GRAPH
+                raise NotImplementedError("wav2vec2_aasist: forward(x, lengths) beyond %d frames needs graph-attention widths among %r"
+                                          % (aasist_head.max_frames(self.pool_cfg), aasist_long.GAT_WIDTHS))
+        elif lengths is not None and self.head_takes_frames and not AasistHead.frames_supported(self):
             raise NotImplementedError("wav2vec2_aasist: forward(x, lengths) runs on the fused stack and graph kernels only: this configuration's "
                                       "shapes are not theirs, or SCL_AASIST_FUSED=0 is set")
         return super().forward(x, lengths)

@@ -787,9 +787,22 @@ def gat_score_fwd(x, W, bias, a, s, B, N, D, Do, n1):
 
 def gat_score_fwd_var(x, W, bias, a, s, nodes, n1, B, Nmax, D, Do):
     """gat_score_fwd for graphs of different sizes: nodes / n1 int32 [B] on the GPU (n1 None: the homogeneous layer); s holds utterance b's own
-    [nodes[b]][nodes[b]] matrix at the start of its Nmax * Nmax block."""
+    [nodes[b]][nodes[b]] matrix at the start of its Nmax * Nmax block.  Above 128 nodes (the tiled form, up to 1024) the entry wants both
+    tables: a homogeneous layer's n1 is its node count."""
     assert nodes.dtype == torch.int32 and nodes.numel() >= B and (n1 is None or (n1.dtype == torch.int32 and n1.numel() >= B))
+    assert s.numel() >= B * Nmax * Nmax and x.numel() >= B * Nmax * D
+    if n1 is None and Nmax > 128:
+        n1 = nodes
     _call("scl_gat_score_fwd_var", _p(x), _p(W), _p(bias), _p(a), _p(s), _p(nodes), None if n1 is None else _p(n1), B, Nmax, D, Do, _stream())
+
+
+def gat_softmax_agg_var(s, x, nodes, out, B, Nmax, D, temp, one_row=False):
+    """out[b, i] = sum_{j < nodes[b]} softmax_j(s[b, i, j] / temp) x[b, j] for i < nodes[b] (rows beyond: written as zeros); s in
+    gat_score_fwd_var's layout, x [B, Nmax, D], out [B, Nmax, D].  one_row: s [B, Nmax], out [B, D]."""
+    assert s.dtype == x.dtype == out.dtype == torch.float32 and s.is_contiguous() and x.is_contiguous() and out.is_contiguous()
+    assert x.numel() >= B * Nmax * D and s.numel() >= B * Nmax * (1 if one_row else Nmax) and out.numel() >= B * D * (1 if one_row else Nmax)
+    assert nodes.numel() >= B
+    _call("scl_gat_softmax_agg_var", _p(s), _p(x), _p(_klen(nodes)), _p(out), B, Nmax, D, 1 if one_row else 0, float(temp), _stream())
 
 
 def gat_score_bwd(x, W, bias, a, ds, dP, part, dx, B, N, D, Do, n1):
@@ -814,6 +827,19 @@ def bn_eval_masked(x, B, H, W, C, gamma, beta, running_mean, running_var, eps, a
     assert valid.numel() >= B
     _call("scl_bn_eval_masked", _p(x), B, H, W, C, _p(gamma), _p(beta), _p(running_mean), _p(running_var), eps, act, _p(_klen(valid)), _p(mean),
           _p(rstd), _p(y), _stream())
+
+
+def bn_eval_cols(x, B, H, W, C, gamma, beta, running_mean, running_var, eps, act, widths, mean, rstd, y):
+    """bn_eval_masked with the mask on the columns: utterance b owns w < widths[b] (int32 [B] on the GPU) of every row, exactly 0 beyond."""
+    assert widths.numel() >= B and x.numel() >= B * H * W * C and y.numel() >= B * H * W * C
+    _call("scl_bn_eval_cols", _p(x), B, H, W, C, _p(gamma), _p(beta), _p(running_mean), _p(running_var), eps, act, _p(_klen(widths)), _p(mean),
+          _p(rstd), _p(y), _stream())
+
+
+def zero_cols(x, B, H, W, C, widths):
+    """In place: x [B, H, W, C] f32 gets 0 stored at the columns w >= widths[b] (int32 [B] on the GPU)."""
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= B * H * W * C and widths.numel() >= B
+    _call("scl_zero_cols", _p(x), B, H, W, C, _p(_klen(widths)), _stream())
 
 
 def bn_bwd(dy, y, x, mean, rstd, gamma, N, C, act, training, part, sums, dgamma, dbeta, dx, accumulate=False):

@@ -24,11 +24,14 @@ _SIZES = {(16, 32), (32, 32), (32, 64), (64, 64)}
 
 
 MAX_W = 93      # RS_MAX_SPAN of resstack.hip: W + 3 positions of halo
+RS_MAX_SPAN = 96
 
 
 def supported(blocks, W=None):
     """The instantiated channel steps: 1 (carried as 16) | 32 | 64 -> 32 | 64, kernels (2,3) / (2,3) / (1,3); maps up to 93 positions wide."""
-    if W is not None and W > MAX_W:
+    # conv1's six taps span (W + 2) + 2 positions of the zero-bordered map and scl_rs_conv takes RS_MAX_SPAN = 96 of them: the fixed-length
+    # stack runs here up to 92 columns; at 93 (279 - 281 frames) it used to be sent here and refused by the kernel's own check
+    if W is not None and W + 4 > RS_MAX_SPAN:
         return False
     try:
         for i, blk in enumerate(blocks):
