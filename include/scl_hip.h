@@ -263,6 +263,22 @@ int scl_bn_fwd_masked(const float* x, int B, int H, int W, int C, const float* g
 int scl_bn_bwd_masked(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* gamma, int B,
                       int H, int W, int C, int act, const int32_t* valid, const int32_t* valid_host, float* part, float* sums,
                       float* dgamma, float* dbeta, float* dx, int accumulate, void* stream);
+/* The column-mask twins of scl_bn_fwd_masked / scl_bn_bwd_masked, as scl_bn_eval_cols is of scl_bn_eval_masked: utterance b owns the columns
+ * w < widths[b] (int32 [B] on the GPU, clamped to 0..W) of every row h of x [B, H, W, C], and N_v = H * sum_b widths[b] is counted on the device.
+ * Forward: mean and biased variance per channel over the N_v own positions (fixed-order fp64 slab partials, no atomics: two runs give the same
+ * bits; nothing at or beyond widths[b] is loaded); y = act((x - mean) * rstd * gamma + beta) for w < widths[b] and exactly +0.0f at and beyond,
+ * selected on the column.  Running statistics and num_batches_tracked as scl_bn_fwd_masked.  Backward: dbeta / dgamma (either may be NULL;
+ * accumulate != 0: ADDED to) and the sums over the own positions; dx by scl_bn_bwd_masked's expression for w < widths[b] and exactly +0.0f at
+ * and beyond, selected on the column (never on y == 0); dy, y and x are not read there.  widths_host: the same B counts in host memory, read
+ * only to refuse a batch without any own position.  part: scl_bn_masked_nslabs(B, H, W) * 2 * C DOUBLES - the row form's partition, walked over
+ * the utterance's own positions in (h, w) order; sums: f32 [2 * C + 1].  Shapes, channel counts and alignment as the row form.
+ * Batch statistics couple the utterances of a batch: unlike the scoring forms, an utterance's y depends on the batch it sits in. */
+int scl_bn_fwd_cols(const float* x, int B, int H, int W, int C, const float* gamma, const float* beta, float* running_mean,
+                    float* running_var, long long* num_batches_tracked, float momentum, float eps, int act, const int32_t* widths,
+                    const int32_t* widths_host, float* part, float* mean, float* rstd, float* y, void* stream);
+int scl_bn_bwd_cols(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* gamma, int B,
+                    int H, int W, int C, int act, const int32_t* widths, const int32_t* widths_host, float* part, float* sums,
+                    float* dgamma, float* dbeta, float* dx, int accumulate, void* stream);
 /* src [rows, C] contiguous f32 -> mapped (padded / dilated) destination, f32 or bf16 (row mapping as scl_bn_fwd's y2) */
 int scl_pad_nhwc_f32(const float* src, int64_t rows, int C, void* dst, int dst_bf16, int m_W, int m_HW, int64_t m_bs, int64_t m_rs,
                      int64_t m_cs, int64_t m_base, void* stream);
@@ -554,6 +570,23 @@ int scl_gat_score_fwd_var(const float* x, const float* W, const float* bias, con
  * one_row != 0: s [B, Nmax] is one score row per utterance and out is [B, D] (the master node's softmax over the nodes).  Nmax <= 1024. */
 int scl_gat_softmax_agg_var(const float* s, const float* x, const int32_t* nodes, float* out, int B, int Nmax, int D, int one_row, float temp,
                             void* stream);
+/* Backward of scl_gat_score_fwd_var (training on zero-padded batches): the VAR instantiation of scl_gat_score_bwd's matrix-core kernels with
+ * nodes[b] and n1[b] from the device tables, same widths and cap as the forward.  ds comes in the forward's ragged layout (the own
+ * [N_b][N_b] at the start of the Nmax * Nmax block, row stride N_b); dP: f32 [B, Nmax * Nmax, D] scratch, per utterance in the same layout;
+ * part: f32 [B * scl_gat_score_nblocks(Nmax)][Do*D + 4*Do] as scl_gat_score_bwd's - a block at or beyond N_b leaves before any barrier
+ * (workgroup-uniform) and writes its row as zeros, so the caller sums every row; dx f32 [B, Nmax, D] with its rows >= N_b written as exact
+ * zeros.  The j tile loop ends at N_b; x rows and ds entries beyond the own graph are never read.  No atomics: two runs give the same bits,
+ * and an utterance's dP and dx do not depend on the batch it sits in. */
+int scl_gat_score_bwd_var(const float* x, const float* W, const float* bias, const float* a, const float* ds, float* dP, float* part,
+                          float* dx, const int32_t* nodes, const int32_t* n1, int B, int Nmax, int D, int Do, void* stream);
+/* Backward of scl_gat_softmax_agg_var.  With P = softmax_j(s / temp) over the own nodes, recomputed from s by streaming (no [N, N] matrix
+ * but ds reaches HBM): dP = dout . x^T, ds = P o (dP - rowsum(P o dP)) / temp in the layout of s (entries beyond the own [N_b][N_b] are not
+ * written), dx = P^T . dout as f32 [B, Nmax, D] with its rows >= N_b written as exact zeros.  dout [B, Nmax, D] (rows >= N_b not read).
+ * stats: f32 [B, Nmax, 2] scratch (one_row: [B, 2]): the rows' soft-max maximum and sum, from the first kernel (16 rows per block, two walks
+ * over j in tiles of 64) to the second (16 nodes j per block, i in tiles of 64).  Fixed tile partition, fixed order, no atomics, fixed LDS:
+ * an utterance's ds and dx do not depend on the batch it sits in.  one_row != 0: s, ds [B, Nmax] and dout [B, D].  Nmax <= 1024, D in {32, 64}. */
+int scl_gat_softmax_agg_var_bwd(const float* s, const float* x, const int32_t* nodes, const float* dout, float* ds, float* dx, float* stats,
+                                int B, int Nmax, int D, int one_row, float temp, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* AASIST RawNet2-style encoder: the six Residual_blocks (model/wav2vec2_aasist.py:377-433,     */

@@ -38,10 +38,25 @@ VARLEN_SCORING_OPT_IN = {"wav2vec2_aasist": "SCL_AASIST_LENGTHS"}
 # --padding_type none with no switch, and likewise never routed into --padding_type zero --batch_size k training: the plugin's own
 # forward(x, lengths=...) in train mode is its training interface (the tokeniser runs per utterance)
 VARLEN_SCORING_MODELS = ("wav2vec2_btse",)
+# --padding_type zero --batch_size k TRAINING by opt-in: plugin -> the environment switch that turns its training mode with lengths on.  The
+# packs are zero-padded and masked only when that switch AND the plugin's scoring switch (VARLEN_SCORING_OPT_IN: validation scores under the
+# mask) are set, read when main() runs; with neither the plugin keeps its behaviour, with only one main() exits at start-up naming both
+VARLEN_TRAIN_OPT_IN = {"wav2vec2_aasist": "SCL_AASIST_TRAIN_LENGTHS"}
 
 
 def _scores_varlen(name):
     return name in VARLEN_MODELS or name in VARLEN_SCORING_MODELS or os.environ.get(VARLEN_SCORING_OPT_IN.get(name, ""), "0") in ("1", "long")
+
+
+def _train_opt_in(name):
+    """(training switch set, scoring switch set) of a VARLEN_TRAIN_OPT_IN plugin; (False, False) for every other model."""
+    if name not in VARLEN_TRAIN_OPT_IN:
+        return False, False
+    return os.environ.get(VARLEN_TRAIN_OPT_IN[name], "0") == "1", os.environ.get(VARLEN_SCORING_OPT_IN[name], "0") in ("1", "long")
+
+
+def _trains_varlen(name):
+    return name in VARLEN_MODELS or all(_train_opt_in(name))
 
 
 class EarlyStop:
@@ -419,6 +434,11 @@ def main(argv=None):
         sys.exit("main.py: --padding_type none needs a model that takes per-utterance lengths: wav2vec2_linear_nll only, or the scoring mode "
                  "of wav2vec2_resnet_nll (%s has no padding mask in its back-end); use --padding_type zero or repeat" % config["model"]["name"]
                  + ("" if switch is None else ".  %s=1 turns on this plugin's scoring mode with lengths" % switch))
+    if args.padding_type == "zero" and args.batch_size > 1 and len(set(_train_opt_in(config["model"]["name"]))) == 2:
+        name = config["model"]["name"]
+        sys.exit("main.py: --padding_type zero --batch_size %d trains %s on zero-padded packs only with BOTH %s=1 (training with lengths) and "
+                 "%s=1 or =long (validation scores under the mask) set; only one of them is.  Set both, or neither to keep the fixed-length "
+                 "behaviour" % (args.batch_size, name, VARLEN_TRAIN_OPT_IN[name], VARLEN_SCORING_OPT_IN[name]))
     model = MODEL_REGISTRY[config["model"]["name"]](config["model"], device, seed=args.seed, rank=rank)
     print("nb_params:", sum(p.numel() for p in model.parameters()))
 
@@ -484,7 +504,7 @@ def main(argv=None):
     # latter's clips are padded to the 17,680 samples its back-end needs): the others take no lengths and keep their behaviour.  One pack
     # per step needs no mask (a pack at its own length), --padding_type repeat has no padding.
     pad_kw = {}
-    if args.padding_type == "zero" and args.batch_size > 1 and config["model"]["name"] in VARLEN_MODELS:
+    if args.padding_type == "zero" and args.batch_size > 1 and _trains_varlen(config["model"]["name"]):
         if model.cfg.embed // model.cfg.heads != 64:
             sys.exit("main.py: --padding_type zero with --batch_size %d masks the padding in the streaming attention, which takes 64-wide "
                      "heads (this encoder's are %d wide); use --padding_type repeat or --batch_size 1"

@@ -282,6 +282,14 @@ class AasistHead(nn.Module):
         from . import aasist_long
         return aasist_long.forward_frames_long(self, feats, frames)
 
+    def forward_frames_train(self, feats, frames):
+        """Train mode with autograd on, on a zero-padded batch with host-side frame counts (min_frames() .. aasist_long.MAX_FRAMES): the
+        count-table per-layer composition with batch statistics over the batch's own positions and an exact backward
+        (aasist_long.forward_frames_train), at every length and independent of SCL_AASIST_FUSED / SCL_AASIST_FUSED_GRAPH.  Batch statistics
+        couple the rows: a row is not what its utterance gets alone."""
+        from . import aasist_long
+        return aasist_long.forward_frames_train(self, feats, frames)
+
     def graph_unfused(self, e_S, e_T):
         """The graph module as a composition of per-operation autograd Functions (round 2): the fall-back for graph sizes the fused
         kernels do not take, and the arm tests/test_graph_gpu.py compares them with."""

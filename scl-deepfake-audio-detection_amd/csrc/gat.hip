@@ -195,19 +195,27 @@ __global__ __launch_bounds__(GAT_PAIRS) void gat_score_bwd_kernel(const float* _
 }
 
 // dx[b][i][d] = sum_j (dP[b][i][j][d] + dP[b][j][i][d]) * x[b][j][d];  one block per (b, i), threads = 4 j-lanes x D
-template <int D>
-__global__ void gat_dx_kernel(const float* __restrict__ dP, const float* __restrict__ x, float* __restrict__ dx, int N) {
+// VAR: N is the batch's Nmax (the strides of x, dx and of the utterance's dP block), the sums run over the utterance's own nodes[b] nodes of
+// its own [N_b][N_b][D] matrix at the start of the block, and a row i >= N_b is written as zeros (the whole block: before the barrier).
+template <int D, bool VAR = false>
+__global__ void gat_dx_kernel(const float* __restrict__ dP, const float* __restrict__ x, float* __restrict__ dx, int N, const int* __restrict__ nodes = nullptr) {
     __shared__ float red[4][D];
     const int b = blockIdx.y, i = blockIdx.x;
     const int d = threadIdx.x % D, jl = threadIdx.x / D;
     const float* xb = x + (int64_t)b * N * D;
     const float* pb = dP + (int64_t)b * N * N * D;
+    float* dxr = dx + ((int64_t)b * N + i) * D;
+    if (VAR) {
+        const int Nmax = N;
+        N = nodes[b]; N = N < 1 ? 1 : (N > Nmax ? Nmax : N);
+        if (i >= N) { if (jl == 0) dxr[d] = 0.f; return; }
+    }
     float s = 0.f;
     for (int j = jl; j < N; j += 4)
         s += (pb[((int64_t)i * N + j) * D + d] + pb[((int64_t)j * N + i) * D + d]) * xb[(int64_t)j * D + d];
     red[jl][d] = s;
     __syncthreads();
-    if (jl == 0) dx[((int64_t)b * N + i) * D + d] = red[0][d] + red[1][d] + red[2][d] + red[3][d];
+    if (jl == 0) dxr[d] = red[0][d] + red[1][d] + red[2][d] + red[3][d];
 }
 
 // ---- matrix-core forms (D in {32, 64}, Do in {32, 64}) ----------------------------------------------------------------------------------
@@ -285,18 +293,38 @@ __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_fwd_mfma_kernel(const 
     }
 }
 
-template <int D, int Do>
+// VAR (training on zero-padded batches): the backward of the VAR forward above.  N is the batch's Nmax - the strides of x and of the
+// utterance's blocks of ds and dP - and the utterance's own N_b = nodes[b] and n1_b = n1s[b] replace N and n1 below: ds comes in the
+// forward's ragged layout (the own [N_b][N_b] at the start of the Nmax * Nmax block, row stride N_b), dP is written in the same layout, and
+// x rows and ds entries beyond the own graph are never read.  A block wholly beyond the utterance's nodes writes its row of `part` as zeros
+// (the caller sums every row) and leaves before any barrier; all of this is uniform in a workgroup.
+template <int D, int Do, bool VAR = false>
 __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_bwd_mfma_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                                          const float* __restrict__ bias, const float* __restrict__ a,
                                                                          const float* __restrict__ ds, float* __restrict__ dP,
-                                                                         float* __restrict__ part, int N, int n1) {
+                                                                         float* __restrict__ part, int N, int n1, const int* __restrict__ nodes = nullptr,
+                                                                         const int* __restrict__ n1s = nullptr) {
     constexpr int NS = D / 4, NOB = Do / 16, NDB = D / 16, NSO = Do / 4, XP = D + 1, TP = Do + 1;
     extern __shared__ float sm[];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+    const float* xb = x + (int64_t)b * N * D;                     // the padded batch's strides (VAR: N is still Nmax here)
+    const float* dsb = ds + (int64_t)b * N * N;
+    float* dPb = dP + (int64_t)b * N * N * D;
+    if (VAR) {
+        const int Nmax = N;
+        N = nodes[b]; N = N < 1 ? 1 : (N > Nmax ? Nmax : N);
+        n1 = n1s ? n1s[b] : N; n1 = n1 < 0 ? 0 : (n1 > N ? N : n1);
+        const int ipb_ = (N + (int)gridDim.x - 1) / (int)gridDim.x;
+        if ((int)blockIdx.x * ipb_ >= N) {
+            float* pz = part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * ((size_t)Do * D + 4 * Do);
+            for (int e = tid; e < Do * D + 4 * Do; e += GAT_PAIRS) pz[e] = 0.f;
+            return;
+        }
+    }
     float* xs = sm;                                        // [N + 16][XP]
     float* Tw = sm + (N + 16) * XP + wave * 16 * TP;       // this wave's dpre tile [16 pairs][TP]
     float* red = sm + (N + 16) * XP + 4 * 16 * TP;         // [4 waves][4 * Do]: db | da0 | da1 | da2
-    gat_stage_x<D>(xs, x + (int64_t)b * N * D, N);
+    gat_stage_x<D>(xs, xb, N);
     float wr[NOB][NS], wt[NDB][NSO], bo[NOB], av[3][NOB];
 #pragma unroll
     for (int ob = 0; ob < NOB; ++ob) {
@@ -337,7 +365,7 @@ __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_bwd_mfma_kernel(const 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = j0 + 4 * g + r;
-            const float gd = j < N ? ds[((int64_t)b * N + i) * N + j] : 0.f;
+            const float gd = j < N ? dsb[(int64_t)i * N + j] : 0.f;
             const int ty = gat_type(i, j < N ? j : 0, n1);
 #pragma unroll
             for (int ob = 0; ob < NOB; ++ob) {
@@ -373,7 +401,7 @@ __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_bwd_mfma_kernel(const 
             for (int db = 0; db < NDB; ++db) dpa[db] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[db][k], tv, dpa[db], 0, 0, 0);
         }
         if (j0 + li < N) {
-            float* out = dP + (((int64_t)b * N + i) * N + j0 + li) * D;
+            float* out = dPb + ((int64_t)i * N + j0 + li) * D;
 #pragma unroll
             for (int db = 0; db < NDB; ++db) *reinterpret_cast<f32x4*>(out + 16 * db + 4 * g) = dpa[db];
         }
@@ -501,11 +529,13 @@ __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_fwd_tiled_kernel(const
     }
 }
 
-template <int D, int Do>
+// VAR: as gat_score_bwd_mfma_kernel's, on the tiled forward's partition (GAT_IPB rows per block, the tile loop ends at N_b).
+template <int D, int Do, bool VAR = false>
 __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_bwd_tiled_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                                           const float* __restrict__ bias, const float* __restrict__ a,
                                                                           const float* __restrict__ ds, float* __restrict__ dP,
-                                                                          float* __restrict__ part, int N, int n1) {
+                                                                          float* __restrict__ part, int N, int n1, const int* __restrict__ nodes = nullptr,
+                                                                          const int* __restrict__ n1s = nullptr) {
     constexpr int NS = D / 4, NOB = Do / 16, NDB = D / 16, NSO = Do / 4, XP = D + 1, TP = Do + 1, XROWS = GAT_IPB + GAT_JT;
     extern __shared__ float sm[];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
@@ -513,9 +543,24 @@ __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_bwd_tiled_kernel(const
     float* xj = sm + GAT_IPB * XP;                         // [GAT_JT][XP]
     float* Tw = sm + XROWS * XP + wave * 16 * TP;          // this wave's dpre tile [16 pairs][TP]
     float* red = sm + XROWS * XP + 4 * 16 * TP;            // [4 waves][4 * Do]: db | da0 | da1 | da2
-    const int nblk = gridDim.x, ipb = (N + nblk - 1) / nblk;      // <= GAT_IPB (scl_gat_score_nblocks)
+    const float* xb = x + (int64_t)b * N * D;                     // the padded batch's strides (VAR: N is still Nmax here)
+    const float* dsb = ds + (int64_t)b * N * N;
+    float* dPb = dP + (int64_t)b * N * N * D;
+    int ipb = GAT_IPB;
+    if (VAR) {
+        const int Nmax = N;
+        N = nodes[b]; N = N < 1 ? 1 : (N > Nmax ? Nmax : N);
+        n1 = n1s ? n1s[b] : N; n1 = n1 < 0 ? 0 : (n1 > N ? N : n1);
+        if ((int)blockIdx.x * GAT_IPB >= N) {
+            float* pz = part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * ((size_t)Do * D + 4 * Do);
+            for (int e = tid; e < Do * D + 4 * Do; e += GAT_PAIRS) pz[e] = 0.f;
+            return;
+        }
+    } else {
+        const int nblk = gridDim.x;
+        ipb = (N + nblk - 1) / nblk;      // <= GAT_IPB (scl_gat_score_nblocks)
+    }
     const int i0 = blockIdx.x * ipb, i1 = min(N, i0 + ipb);
-    const float* xb = x + (int64_t)b * N * D;
     gat_stage_rows<D>(xi, xb, i0, GAT_IPB, N);
     float wr[NOB][NS], wt[NDB][NSO], bo[NOB], av[3][NOB];
 #pragma unroll
@@ -559,7 +604,7 @@ __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_bwd_tiled_kernel(const
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = j0 + 4 * g + r;
-                const float gd = j < N ? ds[((int64_t)b * N + i) * N + j] : 0.f;
+                const float gd = j < N ? dsb[(int64_t)i * N + j] : 0.f;
                 const int ty = gat_type(i, j < N ? j : 0, n1);
 #pragma unroll
                 for (int ob = 0; ob < NOB; ++ob) {
@@ -595,7 +640,7 @@ __global__ __launch_bounds__(GAT_PAIRS, 1) void gat_score_bwd_tiled_kernel(const
                 for (int db = 0; db < NDB; ++db) dpa[db] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[db][k], tv, dpa[db], 0, 0, 0);
             }
             if (j0 + li < N) {
-                float* out = dP + (((int64_t)b * N + i) * N + j0 + li) * D;
+                float* out = dPb + ((int64_t)i * N + j0 + li) * D;
 #pragma unroll
                 for (int db = 0; db < NDB; ++db) *reinterpret_cast<f32x4*>(out + 16 * db + 4 * g) = dpa[db];
             }
@@ -724,6 +769,137 @@ __global__ __launch_bounds__(256) void gat_softmax_agg_kernel(const float* __res
             if (i < rows) ob_[(int64_t)i * D + 16 * wave + li] = acc[r] / rs[AGG_IPB + 4 * g + r];
             else if (i < rows_max) ob_[(int64_t)i * D + 16 * wave + li] = 0.f;
         }
+    }
+}
+
+// Backward of the masked soft-max + aggregation (training on zero-padded batches).  With P = softmax_j(s / temp) over the own nodes,
+//   dP[i][j] = dout[i] . x[j],   ds[i][j] = P[i][j] (dP[i][j] - sum_j' P[i][j'] dP[i][j']) / temp,   dx[j] = sum_i P[i][j] dout[i].
+// P is recomputed from s by streaming; no [N][N] matrix but ds itself reaches HBM.  Two kernels, no atomics, fixed LDS (21 KB / 22 KB at D = 64):
+//   rows  a block owns AGB_IPB = 16 rows i and walks j in tiles of AGB_JT = 64 twice.  First walk: the running row maximum m, the sum l and
+//         r = sum_j p dP, rescaled together when m moves (the forward's scheme); m and l go to `stats` [B][rows][2].  Second walk: ds, written
+//         in the ragged layout of s (entries beyond the own [N_b][N_b] are not written).
+//   cols  a block owns 16 nodes j and walks i in tiles of 64 in order: p = exp(s / temp - m_i) / l_i from `stats`, dx[j] += p dout[i]; the rows
+//         j >= N_b of dx [B, Nmax, D] are written as zeros.
+// Neither reads s, x or dout beyond the own graph (0 is selected).  The row / tile partition is fixed and starts at 0 in every utterance, so
+// an utterance's ds and dx do not depend on the batch it sits in.  ONE: the master node's single score row (s, ds [B, Nmax]; dout [B, D]).
+constexpr int AGB_IPB = 16, AGB_JT = 64;
+
+template <int D, bool ONE>
+__global__ __launch_bounds__(256) void gat_softmax_agg_bwd_rows_kernel(const float* __restrict__ s, const float* __restrict__ x, const int* __restrict__ nodes,
+                                                                       const float* __restrict__ dout, float* __restrict__ ds, float* __restrict__ stats,
+                                                                       int Nmax, float temp) {
+    constexpr int XS = D + 1;
+    __shared__ float xs[AGB_JT * XS];       // x rows of the tile
+    __shared__ float dos[AGB_IPB * XS];     // the block's rows of dout
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int N = nodes[b]; N = N < 1 ? 1 : (N > Nmax ? Nmax : N);
+    const int rows = ONE ? 1 : N, rows_max = ONE ? 1 : Nmax;
+    const int i0 = blockIdx.x * AGB_IPB;
+    if (i0 >= rows) return;      // a block wholly beyond the utterance's rows has nothing to write: out before any barrier (uniform in the workgroup)
+    const float* sb = s + (int64_t)b * (ONE ? Nmax : (int64_t)Nmax * Nmax);
+    float* dsb = ds + (int64_t)b * (ONE ? Nmax : (int64_t)Nmax * Nmax);
+    const float* xb = x + (int64_t)b * Nmax * D;
+    const float* dob = dout + (int64_t)b * rows_max * D;
+    const int row = tid >> 4, c = tid & 15, gi = i0 + row;      // 16 threads per row, 4 pairs of a tile each
+    const bool own = gi < rows;
+    for (int e = tid; e < AGB_IPB * D; e += 256) {
+        const int r = e / D, d = e - r * D;
+        dos[r * XS + d] = i0 + r < rows ? dob[(int64_t)(i0 + r) * D + d] : 0.f;
+    }
+    float m_run = -INFINITY, l_run = 0.f, r_run = 0.f;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int t0 = 0; t0 < N; t0 += AGB_JT) {
+            __syncthreads();      // the previous tile's readers are done
+            for (int e = tid; e < AGB_JT * D; e += 256) {
+                const int r = e / D, d = e - r * D;
+                xs[r * XS + d] = t0 + r < N ? xb[(int64_t)(t0 + r) * D + d] : 0.f;
+            }
+            __syncthreads();
+            float v[4], dp[4], tmax = -INFINITY;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int jl = c + 16 * q, j = t0 + jl;
+                const bool ok = own && j < N;
+                v[q] = ok ? sb[(int64_t)gi * N + j] / temp : -INFINITY;
+                float acc = 0.f;
+                for (int d = 0; d < D; ++d) acc += dos[row * XS + d] * xs[jl * XS + d];
+                dp[q] = acc;
+                tmax = fmaxf(tmax, v[q]);
+            }
+            if (pass == 0) {
+                tmax = lanes16_max_x(tmax);
+                const float m_new = fmaxf(m_run, tmax);
+                const float sc = (m_new == -INFINITY) ? 0.f : expf(m_run - m_new);
+                float psum = 0.f, prs = 0.f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float p = v[q] == -INFINITY ? 0.f : expf(v[q] - m_new);
+                    psum += p; prs += p * dp[q];
+                }
+                l_run = l_run * sc + lanes16_sum_x(psum);
+                r_run = r_run * sc + lanes16_sum_x(prs);
+                m_run = m_new;
+            } else if (own) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int j = t0 + c + 16 * q;
+                    if (j < N) dsb[(int64_t)gi * N + j] = expf(v[q] - m_run) / l_run * (dp[q] - r_run) / temp;
+                }
+            }
+        }
+        if (pass == 0 && own) {      // l_run >= 1: the row's maximum contributes exp(0)
+            r_run /= l_run;
+            if (c == 0) { float* st = stats + ((int64_t)b * rows_max + gi) * 2; st[0] = m_run; st[1] = l_run; }
+        }
+    }
+}
+
+template <int D, bool ONE>
+__global__ __launch_bounds__(256) void gat_softmax_agg_bwd_cols_kernel(const float* __restrict__ s, const int* __restrict__ nodes, const float* __restrict__ dout,
+                                                                       const float* __restrict__ stats, float* __restrict__ dx, int Nmax, float temp) {
+    constexpr int XS = D + 1, PS = 17, ND = D / 16;
+    __shared__ float ps[AGB_JT * PS];       // p of the tile [row i][node j]
+    __shared__ float dos[AGB_JT * XS];      // dout rows of the tile
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int N = nodes[b]; N = N < 1 ? 1 : (N > Nmax ? Nmax : N);
+    const int rows = ONE ? 1 : N, rows_max = ONE ? 1 : Nmax;
+    const int j0 = blockIdx.x * 16;
+    float* dxb = dx + (int64_t)b * Nmax * D;
+    if (j0 >= N) {      // nodes wholly beyond the utterance's: zeros, and out before any barrier (uniform in the workgroup)
+        for (int e = tid; e < 16 * D; e += 256) { const int j = j0 + e / D; if (j < Nmax) dxb[(int64_t)j * D + (e % D)] = 0.f; }
+        return;
+    }
+    const float* sb = s + (int64_t)b * (ONE ? Nmax : (int64_t)Nmax * Nmax);
+    const float* dob = dout + (int64_t)b * rows_max * D;
+    const float* st = stats + (int64_t)b * rows_max * 2;
+    const int jr = tid >> 4, dg = tid & 15;      // this thread: node j0 + jr, features dg + 16 k
+    float acc[ND];
+#pragma unroll
+    for (int k = 0; k < ND; ++k) acc[k] = 0.f;
+    for (int t0 = 0; t0 < rows; t0 += AGB_JT) {
+        __syncthreads();      // the previous tile's readers are done
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int e = tid + 256 * q, il = e >> 4, jl = e & 15, i = t0 + il, j = j0 + jl;
+            float p = 0.f;
+            if (i < rows && j < N) p = expf(sb[(int64_t)i * N + j] / temp - st[2 * i]) / st[2 * i + 1];
+            ps[il * PS + jl] = p;
+        }
+        for (int e = tid; e < AGB_JT * D; e += 256) {
+            const int r = e / D, d = e - r * D;
+            dos[r * XS + d] = t0 + r < rows ? dob[(int64_t)(t0 + r) * D + d] : 0.f;
+        }
+        __syncthreads();
+        for (int il = 0; il < AGB_JT; ++il) {
+            const float pv = ps[il * PS + jr];
+#pragma unroll
+            for (int k = 0; k < ND; ++k) acc[k] += pv * dos[il * XS + dg + 16 * k];
+        }
+    }
+    const int j = j0 + jr;
+    if (j < Nmax) {
+#pragma unroll
+        for (int k = 0; k < ND; ++k) dxb[(int64_t)j * D + dg + 16 * k] = j < N ? acc[k] : 0.f;
     }
 }
 
@@ -877,4 +1053,58 @@ extern "C" int scl_gat_score_bwd(const float* x, const float* W, const float* bi
         hipLaunchKernelGGL((gat_dx_kernel<32>), dim3(N, B), dim3(128), 0, st, dP, x, dx, N);
     }
     return scl_check_launch("scl_gat_score_bwd");
+}
+
+// Backward of scl_gat_score_fwd_var: graphs of different sizes in one batch.  ds and dP in the forward's ragged layout (the utterance's own
+// [N_b][N_b] (x D) matrix at the start of its Nmax * Nmax (x D) block), dx [B, Nmax, D] with its rows >= N_b written as zeros, part as
+// scl_gat_score_bwd's with scl_gat_score_nblocks(Nmax) rows per utterance - the rows of blocks beyond N_b are zeros.
+extern "C" int scl_gat_score_bwd_var(const float* x, const float* W, const float* bias, const float* a, const float* ds, float* dP, float* part,
+                                     float* dx, const int32_t* nodes, const int32_t* n1, int B, int Nmax, int D, int Do, void* stream) {
+    SCL_REQUIRE(x && W && bias && a && ds && dP && part && dx && nodes && B > 0 && B <= 65535, "scl_gat_score_bwd_var: null pointer or batch beyond 65535");
+    SCL_REQUIRE(gat_is_mfma(D, Do) && Nmax >= 1 && Nmax <= GAT_CAP,
+                "scl_gat_score_bwd_var: the matrix-core forms only: (D, Do) in {(64, 64), (64, 32), (32, 32)}, Nmax <= %d (D=%d Do=%d Nmax=%d)", GAT_CAP, D,
+                Do, Nmax);
+    SCL_REQUIRE(Nmax <= GAT_MAXN || n1, "scl_gat_score_bwd_var: above %d nodes the tiled form reads both tables: n1 == NULL is refused (a homogeneous "
+                "layer passes nodes as n1) (Nmax=%d)", GAT_MAXN, Nmax);
+    dim3 grid(scl_gat_score_nblocks(Nmax), B), block(GAT_PAIRS);
+    hipStream_t st = (hipStream_t)stream;
+#define GAT_BWD_VAR(KERNEL, LDS, DD, OO)                                                                                                  \
+    do {                                                                                                                                   \
+        hipLaunchKernelGGL((KERNEL<DD, OO, true>), grid, block, (LDS), st, x, W, bias, a, ds, dP, part, Nmax, 0, nodes, n1);                 \
+        hipLaunchKernelGGL((gat_dx_kernel<DD, true>), dim3(Nmax, B), dim3(4 * DD), 0, st, dP, x, dx, Nmax, nodes);                         \
+    } while (0)
+    if (Nmax > GAT_MAXN) {
+        if (D == 64 && Do == 64) GAT_BWD_VAR(gat_score_bwd_tiled_kernel, (gat_tiled_lds<64, 64>(true)), 64, 64);
+        else if (D == 64 && Do == 32) GAT_BWD_VAR(gat_score_bwd_tiled_kernel, (gat_tiled_lds<64, 32>(true)), 64, 32);
+        else GAT_BWD_VAR(gat_score_bwd_tiled_kernel, (gat_tiled_lds<32, 32>(true)), 32, 32);
+    } else {
+        if (D == 64 && Do == 64) GAT_BWD_VAR(gat_score_bwd_mfma_kernel, (gat_mfma_lds<64, 64>(Nmax, true)), 64, 64);
+        else if (D == 64 && Do == 32) GAT_BWD_VAR(gat_score_bwd_mfma_kernel, (gat_mfma_lds<64, 32>(Nmax, true)), 64, 32);
+        else GAT_BWD_VAR(gat_score_bwd_mfma_kernel, (gat_mfma_lds<32, 32>(Nmax, true)), 32, 32);
+    }
+#undef GAT_BWD_VAR
+    return scl_check_launch("scl_gat_score_bwd_var");
+}
+
+// Backward of scl_gat_softmax_agg_var: ds in the layout of s (the utterance's own [N_b][N_b] at the start of its Nmax * Nmax block; entries beyond
+// are not written), dx [B, Nmax, D] with its rows >= N_b written as zeros.  stats: f32 [B, Nmax, 2] scratch (one_row: [B, 2]), the rows' soft-max
+// maximum and sum handed from the first kernel to the second.  one_row: s, ds [B, Nmax] and dout [B, D].
+extern "C" int scl_gat_softmax_agg_var_bwd(const float* s, const float* x, const int32_t* nodes, const float* dout, float* ds, float* dx, float* stats,
+                                           int B, int Nmax, int D, int one_row, float temp, void* stream) {
+    SCL_REQUIRE(s && x && nodes && dout && ds && dx && stats && B > 0 && B <= 65535, "scl_gat_softmax_agg_var_bwd: null pointer or batch beyond 65535");
+    SCL_REQUIRE((D == 64 || D == 32) && Nmax >= 1 && Nmax <= GAT_CAP && temp > 0.f,
+                "scl_gat_softmax_agg_var_bwd: need D in {32, 64}, 1 <= Nmax <= %d, temp > 0 (D=%d Nmax=%d)", GAT_CAP, D, Nmax);
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid_r(one_row ? 1 : (Nmax + AGB_IPB - 1) / AGB_IPB, B), grid_c((Nmax + 15) / 16, B), block(256);
+#define AGG_BWD(DD, ONE)                                                                                                                    \
+    do {                                                                                                                                     \
+        hipLaunchKernelGGL((gat_softmax_agg_bwd_rows_kernel<DD, ONE>), grid_r, block, 0, st, s, x, nodes, dout, ds, stats, Nmax, temp);       \
+        hipLaunchKernelGGL((gat_softmax_agg_bwd_cols_kernel<DD, ONE>), grid_c, block, 0, st, s, nodes, dout, (const float*)stats, dx, Nmax, temp); \
+    } while (0)
+    if (D == 64 && one_row) AGG_BWD(64, true);
+    else if (D == 64) AGG_BWD(64, false);
+    else if (one_row) AGG_BWD(32, true);
+    else AGG_BWD(32, false);
+#undef AGG_BWD
+    return scl_check_launch("scl_gat_softmax_agg_var_bwd");
 }

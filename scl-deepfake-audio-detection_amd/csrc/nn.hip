@@ -7,6 +7,7 @@
 // are accumulated per 512-row slab in fp32 and combined over slabs in fp64 (the reference's CPU path accumulates in double).
 // Zero-padded variable-length batches [B][H][W][C] (utterance b owns the rows h < valid[b]): eval-mode BatchNorm and the average for scoring,
 // train-mode BatchNorm (statistics, running statistics and the backward sums over the valid rows only) and the average's backward for training.
+// The AASIST stack's ragged axis is the column w (utterance b owns w < widths[b]): eval-mode and train-mode BatchNorm with that mask, zero_cols.
 #include "common.h"
 
 namespace {
@@ -502,6 +503,100 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_masked_kernel(const float* _
     }
 }
 
+// ---- batch statistics over the own COLUMNS of a zero-padded batch [B][H][W][C] (utterance b owns w < widths[b] of every row h) ----
+// An utterance's own positions are H strided runs of wb * C floats.  The statistics kernels walk them in COMPACT order - position
+// p = h * wb + w of the utterance - on masked_slab's partition (blockIdx.y the utterance, a slab is bn_slab_rows of the padded batch and
+// ends where the utterance's H * wb own positions end), so slab_sums, the term structs and both finishing kernels are the row form's:
+// ColsTerms only turns a compact element index into the map's (one 32-bit division per load; C % 4 == 0: a 16-byte vector lies inside
+// one position, own or padding as a whole).  Nothing at or beyond widths[b] is loaded.  The stats kernels are new instantiations and
+// the row form's kernels are not touched: their schedules (and bits) stay what they were.
+template <class F>
+struct ColsTerms {
+    F f; unsigned wc, WC;      // wb * C (at least 1: never divides by zero; no element is visited then), W * C
+    template <class T>
+    __device__ __forceinline__ void operator()(long long q, int c, T& u, T& v) const {
+        // 32 bits hold q: q < H * wb * C <= H * W * C, which bn_masked_args_ok keeps below 2^31 for every caller of these kernels
+        const unsigned p = (unsigned)q, h = p / wc;
+        f((long long)h * WC + (p - h * wc), c, u, v);
+    }
+};
+__device__ __forceinline__ void cols_slab(const int* __restrict__ widths, int H, int W, int C, int slab_rows, long long& base, long long& e0,
+                                          long long& e1, int& slot, unsigned& wc) {
+    const int b = blockIdx.y, wb = valid_cols(widths, b, W);
+    const long long rows = (long long)H * wb;
+    base = (long long)b * H * W * C;
+    e0 = (long long)blockIdx.x * slab_rows * C;
+    e1 = min((long long)(blockIdx.x + 1) * slab_rows, rows) * C;
+    slot = b * gridDim.x + blockIdx.x;
+    wc = wb > 0 ? (unsigned)wb * C : 1u;
+}
+__global__ __launch_bounds__(256) void bn_stats_cols_kernel(const float* __restrict__ x, const int* __restrict__ widths, int H, int W, int C,
+                                                            double* __restrict__ part, int slab_rows) {
+    long long base, e0, e1; int slot; unsigned wc;
+    cols_slab(widths, H, W, C, slab_rows, base, e0, e1, slot, wc);
+    slab_sums(e0, e1, C, part, slot, ColsTerms<BnFwdTerms>{BnFwdTerms{x + base}, wc, (unsigned)W * C});
+}
+__global__ __launch_bounds__(256) void bn_bwd_stats_cols_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                const int* __restrict__ widths, int H, int W, int C, int act,
+                                                                double* __restrict__ part, int slab_rows) {
+    long long base, e0, e1; int slot; unsigned wc;
+    cols_slab(widths, H, W, C, slab_rows, base, e0, e1, slot, wc);
+    slab_sums(e0, e1, C, part, slot, ColsTerms<BnBwdTerms>{BnBwdTerms{dy + base, y ? y + base : nullptr, x + base, mean, rstd, act}, wc, (unsigned)W * C});
+}
+// pass 2 of the backward: bn_bwd_apply_masked_kernel's expression on the columns w < widths[b], exactly 0 at and beyond - selected by COLUMN
+// (never by y == 0); dy, y and x are not read there.  The launch shape of bn_apply_cols_kernel.  Written apart from the row form for the
+// reason given above bn_bwd_apply_kernel: a shared body would change how the compiler contracts the row form's expression.
+__global__ __launch_bounds__(256) void bn_bwd_apply_cols_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                const float* __restrict__ gamma, const float* __restrict__ sums,
+                                                                const int* __restrict__ widths, long long per, int W, int C, int act,
+                                                                float* __restrict__ dx) {
+    const int b = blockIdx.y;
+    const int wb = valid_cols(widths, b, W);
+    const float invN = sums[2 * C];
+    const float* __restrict__ dyb = dy + (long long)b * per;
+    const float* __restrict__ yb = y ? y + (long long)b * per : nullptr;
+    const float* __restrict__ xb = x + (long long)b * per;
+    float* __restrict__ dxb = dx + (long long)b * per;
+    if ((C & 3) == 0) {
+        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < (per >> 2); q += (long long)gridDim.x * 256) {
+            const long long e = q << 2;
+            float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+            if ((int)((e / C) % W) < wb) {
+                const int c = (int)(e & (C - 1));
+                const float4 dv = *reinterpret_cast<const float4*>(dyb + e), xv = *reinterpret_cast<const float4*>(xb + e);
+                const float4 mv = *reinterpret_cast<const float4*>(mean + c), rv = *reinterpret_cast<const float4*>(rstd + c);
+                float4 yv = make_float4(0.f, 0.f, 0.f, 0.f), gv = make_float4(1.f, 1.f, 1.f, 1.f);
+                if (act) yv = *reinterpret_cast<const float4*>(yb + e);
+                if (gamma) gv = *reinterpret_cast<const float4*>(gamma + c);
+                const float d4[4] = {dv.x, dv.y, dv.z, dv.w}, x4[4] = {xv.x, xv.y, xv.z, xv.w}, m4[4] = {mv.x, mv.y, mv.z, mv.w};
+                const float r4[4] = {rv.x, rv.y, rv.z, rv.w}, y4[4] = {yv.x, yv.y, yv.z, yv.w}, g4[4] = {gv.x, gv.y, gv.z, gv.w};
+                float o[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float dz = d4[i] * (act ? nn_act_grad_from_y(act, y4[i]) : 1.f);
+                    const float xh = (x4[i] - m4[i]) * r4[i];
+                    o[i] = g4[i] * r4[i] * (dz - (sums[c + i] + xh * sums[C + c + i]) * invN);
+                }
+                out = make_float4(o[0], o[1], o[2], o[3]);
+            }
+            *reinterpret_cast<float4*>(dxb + e) = out;
+        }
+        return;
+    }
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < per; e += (long long)gridDim.x * 256) {
+        float out = 0.f;
+        if ((int)((e / C) % W) < wb) {
+            const int c = (int)(e & (C - 1));
+            const float dz = dyb[e] * (act ? nn_act_grad_from_y(act, yb[e]) : 1.f);
+            const float xh = (xb[e] - mean[c]) * rstd[c];
+            out = (gamma ? gamma[c] : 1.f) * rstd[c] * (dz - (sums[c] + xh * sums[C + c]) * invN);
+        }
+        dxb[e] = out;
+    }
+}
+
 // src [B, H, W, C] contiguous f32 -> interior of a padded / dilated map: dst[b][ph + i*dh][pw + j*dw][c]  (f32 or bf16)
 __global__ __launch_bounds__(256) void pad_nhwc_kernel(const float* __restrict__ src, long long n, int C, void* __restrict__ dst, int dst_bf16, RowMap map) {
     if ((C & 3) == 0 && !dst_bf16 && n < (1ll << 33) && ((map.bs | map.rs | map.cs | map.base) & 3) == 0) {
@@ -744,6 +839,45 @@ extern "C" int scl_bn_bwd_masked(const float* dy, const float* y, const float* x
     hipLaunchKernelGGL(bn_bwd_apply_masked_kernel, masked_grid(per, B, C), dim3(256), 0, s, dy, y, x, mean, rstd, gamma, sums, valid, per, W * C, H, C, act,
                        dx);
     return scl_check_launch("scl_bn_bwd_masked");
+}
+
+// The column-mask twins.  The partition has scl_bn_masked_nslabs(B, H, W) slots as the row form's (an utterance has at most H * W own
+// positions either way), and the finishing kernels are the row form's with the two axes swapped: N_v = H * sum_b widths[b].
+extern "C" int scl_bn_fwd_cols(const float* x, int B, int H, int W, int C, const float* gamma, const float* beta, float* running_mean,
+                               float* running_var, long long* num_batches_tracked, float momentum, float eps, int act, const int32_t* widths,
+                               const int32_t* widths_host, float* part, float* mean, float* rstd, float* y, void* stream) {
+    SCL_REQUIRE(x && widths && widths_host && part && mean && rstd && y, "bn_fwd_cols: null argument");
+    if (int rc = bn_masked_args_ok("bn_fwd_cols", B, H, W, C, act, part,
+                                   (uintptr_t)x | (uintptr_t)y | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)beta,
+                                   "x, y, mean, rstd, gamma, beta")) return rc;
+    SCL_REQUIRE(any_valid_row(widths_host, B), "bn_fwd_cols: no valid position (every widths[b] is 0): batch statistics over nothing");
+    hipStream_t s = (hipStream_t)stream;
+    const int slab_rows = bn_slab_rows(B * H * W), nslab = scl_bn_masked_nslabs(B, H, W);
+    hipLaunchKernelGGL(bn_stats_cols_kernel, dim3(nslab / B, B), dim3(256), 0, s, x, widths, H, W, C, (double*)part, slab_rows);
+    hipLaunchKernelGGL(bn_finish_masked_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, (const double*)part, nslab, widths, B, W, H, C, eps, momentum,
+                       running_mean, running_var, num_batches_tracked, mean, rstd);
+    const long long per = (long long)H * W * C;
+    hipLaunchKernelGGL(bn_apply_cols_kernel, masked_grid(per, B, C), dim3(256), 0, s, x, mean, rstd, gamma, beta, widths, per, W, C, act, y);
+    return scl_check_launch("scl_bn_fwd_cols");
+}
+
+extern "C" int scl_bn_bwd_cols(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* gamma, int B,
+                               int H, int W, int C, int act, const int32_t* widths, const int32_t* widths_host, float* part, float* sums,
+                               float* dgamma, float* dbeta, float* dx, int accumulate, void* stream) {
+    SCL_REQUIRE(dy && x && mean && rstd && widths && widths_host && part && sums && dx, "bn_bwd_cols: null argument");
+    if (int rc = bn_masked_args_ok("bn_bwd_cols", B, H, W, C, act, part,
+                                   (uintptr_t)dy | (uintptr_t)y | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma,
+                                   "dy, y, x, dx, mean, rstd, gamma")) return rc;
+    SCL_REQUIRE(act == 0 || y, "bn_bwd_cols: the activation gradient needs the forward output y");
+    SCL_REQUIRE(any_valid_row(widths_host, B), "bn_bwd_cols: no valid position (every widths[b] is 0)");
+    hipStream_t s = (hipStream_t)stream;
+    const int slab_rows = bn_slab_rows(B * H * W), nslab = scl_bn_masked_nslabs(B, H, W);
+    hipLaunchKernelGGL(bn_bwd_stats_cols_kernel, dim3(nslab / B, B), dim3(256), 0, s, dy, y, x, mean, rstd, widths, H, W, C, act, (double*)part, slab_rows);
+    hipLaunchKernelGGL(bn_bwd_finish_masked_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, (const double*)part, nslab, widths, B, W, H, C, dgamma, dbeta, sums,
+                       accumulate);
+    const long long per = (long long)H * W * C;
+    hipLaunchKernelGGL(bn_bwd_apply_cols_kernel, masked_grid(per, B, C), dim3(256), 0, s, dy, y, x, mean, rstd, gamma, sums, widths, per, W, C, act, dx);
+    return scl_check_launch("scl_bn_bwd_cols");
 }
 
 extern "C" int scl_bn_bwd(const float* dy, const float* y, const float* x, const float* mean, const float* rstd, const float* gamma, int N, int C,

@@ -369,6 +369,80 @@ def batch_norm_cols(x, bn, act, widths):
     return y
 
 
+class _BatchNormColsFn(torch.autograd.Function):
+    """Train-mode BatchNorm + activation over the own columns of a zero-padded variable-length batch (scl_bn_fwd_cols / scl_bn_bwd_cols)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, nbt, momentum, eps, act, grad_in_place, widths, counts):
+        B, H, W, C = x.shape
+        xc = x.contiguous().float()
+        dev = x.device
+        part = torch.empty(ops.bn_masked_nslabs(B, H, W) * 2 * C, dtype=torch.float64, device=dev)
+        mean, rstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
+        y = torch.empty_like(xc)
+        ops.bn_fwd_cols(xc, B, H, W, C, weight, bias, running_mean, running_var, nbt, momentum, eps, act, widths, counts, part, mean, rstd, y)
+        ctx.save_for_backward(xc, y, mean, rstd, weight, widths)
+        ctx.cfg = (B, H, W, C, act, weight is not None, bias is not None, counts)
+        ctx.in_place = (weight, bias) if grad_in_place else None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xc, y, mean, rstd, weight, widths = ctx.saved_tensors
+        B, H, W, C, act, has_w, has_b, counts = ctx.cfg
+        dev = dy.device
+        dyc = dy.contiguous().float()
+        part = torch.empty(ops.bn_masked_nslabs(B, H, W) * 2 * C, dtype=torch.float64, device=dev)
+        sums = torch.empty(2 * C + 4, device=dev)
+        dx = torch.empty_like(xc)
+        dg, db, acc = _bn_param_grads(ctx, C, dev, has_w, has_b)
+        ops.bn_bwd_cols(dyc, y, xc, mean, rstd, weight, B, H, W, C, act, widths, counts, part, sums, dg, db, dx, accumulate=acc)
+        return (dx,) + ((None, None) if acc else (dg, db)) + (None,) * 9
+
+
+def batch_norm_cols_train(x, bn, act, widths, counts=None, grad_in_place=False):
+    """Train-mode BatchNorm + `act` of x [B, H, W, C] with autograd on and the mask on the COLUMNS: utterance b owns w < widths[b] (int32 [B]
+    on the GPU) of every row.  Mean and biased variance over the batch's own positions only (N_v = H * sum widths), the running statistics
+    moved with the unbiased variance, num_batches_tracked + 1; y exactly 0 at and beyond widths[b] whatever x holds there (not read), and a
+    backward whose sums run over the own positions and whose dx is exactly 0 at and beyond.  counts: the same widths on the host (the entry
+    points refuse a batch without any own position before they launch); left out, they are read back from `widths`.
+    Batch statistics couple the rows of the batch: unlike batch_norm_cols (scoring), an utterance's result depends on its batch.
+    Eval mode and torch.no_grad() are batch_norm_cols' business and are refused here."""
+    training = bn.training or bn.running_mean is None
+    if not training or not torch.is_grad_enabled() or x.dim() != 4:
+        raise NotImplementedError("hipnn.batch_norm_cols_train: a BatchNorm in train mode with autograd on, on a [B, H, W, C] map "
+                                  "(scoring: hipnn.batch_norm_cols)")
+    if counts is None:
+        counts = widths.tolist()
+    momentum = 0.1 if bn.momentum is None else bn.momentum
+    return _BatchNormColsFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, momentum, bn.eps, act,
+                                  grad_in_place, widths, tuple(int(v) for v in counts))
+
+
+class _ZeroColsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, widths):
+        y = x.float().clone(memory_format=torch.contiguous_format)
+        ops.zero_cols(y, *y.shape, widths)
+        ctx.save_for_backward(widths)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (widths,) = ctx.saved_tensors
+        dx = dy.float().clone(memory_format=torch.contiguous_format)
+        ops.zero_cols(dx, *dx.shape, widths)
+        return dx, None
+
+
+def zero_cols(x, widths):
+    """Out of place and differentiable: a copy of x [B, H, W, C] with exact zeros stored at the columns w >= widths[b] (scl_zero_cols); the
+    backward stores exact zeros at the same columns of the gradient (selected: a NaN gradient there reaches nothing upstream)."""
+    if x.dim() != 4:
+        raise ValueError("hipnn.zero_cols: a [B, H, W, C] map, got %r" % (tuple(x.shape),))
+    return _ZeroColsFn.apply(x, widths)
+
+
 def zero_cols_(x, widths):
     """In place, under torch.no_grad(): x [B, H, W, C] (contiguous f32) gets exact zeros stored at the columns w >= widths[b]."""
     if torch.is_grad_enabled() or x.dim() != 4 or not x.is_contiguous() or x.dtype != torch.float32:

@@ -147,6 +147,8 @@ def _protos():
         "scl_bn_masked_nslabs": ([_i32, _i32, _i32], _i32),
         "scl_bn_fwd_masked": ([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
         "scl_bn_bwd_masked": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp], _i32),
+        "scl_bn_fwd_cols": ([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+        "scl_bn_bwd_cols": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp], _i32),
         "scl_avgpool_bwd_masked": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
         # norm.hip
         "scl_layernorm_fwd": ([_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _f32, _i32, _vp], _i32),
@@ -220,6 +222,8 @@ def _protos():
         "scl_gat_score_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
         "scl_gat_score_fwd_var": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
         "scl_gat_softmax_agg_var": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp], _i32),
+        "scl_gat_score_bwd_var": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
+        "scl_gat_softmax_agg_var_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp], _i32),
         "scl_dropout_rows": ([_vp, _vp, _i64, _i32, _i32, _i32, _u32, _f32, _vp], _i32),
         # resstack.hip
         "scl_rs_conv": ([P(SclRsConv), _vp], _i32),

@@ -14,6 +14,8 @@ scoring precision and either row layout, feats rows beyond an utterance's frames
 Variable-length TRAINING batches (train mode, autograd on) for a back-end that declares `head_trains_frames` besides: the autograd boundary
 carries the row layout, the encoder trains under its padding mask or on packed rows (SCL_VARLEN_PACK=1; the back-end stays padded), and the
 rows of d(feats) beyond an utterance's frames are zeroed before LL's gradients and the encoder backward; the back-end runs eagerly.
+`head_takes_frames` / `head_trains_frames` may be properties read at call time: the AASIST plugin declares the training mode only behind
+SCL_AASIST_TRAIN_LENGTHS=1 (AasistHead.forward_frames_train) and the scoring mode only behind SCL_AASIST_LENGTHS.
 Sub-classes supply `_build_head(args)` (an nn.Module whose children / parameters are grafted at the root under the
 reference's state-dict names) and `_head_forward(mod, feats) -> (output, emb)`.
 """

@@ -809,6 +809,31 @@ def gat_score_bwd(x, W, bias, a, ds, dP, part, dx, B, N, D, Do, n1):
     _call("scl_gat_score_bwd", _p(x), _p(W), _p(bias), _p(a), _p(ds), _p(dP), _p(part), _p(dx), B, N, D, Do, n1, _stream())
 
 
+def gat_score_bwd_var(x, W, bias, a, ds, dP, part, dx, nodes, n1, B, Nmax, D, Do):
+    """Backward of gat_score_fwd_var: ds and dP [B, Nmax * Nmax (, D)] in the forward's ragged layout, part [B * gat_score_nblocks(Nmax),
+    Do * D + 4 * Do] (every row written: zeros by the blocks beyond an utterance's nodes), dx [B, Nmax, D] with zeros at the rows >= nodes[b]."""
+    assert nodes.dtype == torch.int32 and nodes.numel() >= B and (n1 is None or (n1.dtype == torch.int32 and n1.numel() >= B))
+    ncol = Do * D + 4 * Do
+    assert ds.numel() >= B * Nmax * Nmax and dP.numel() >= B * Nmax * Nmax * D and x.numel() >= B * Nmax * D and dx.numel() >= B * Nmax * D
+    assert part.numel() >= B * gat_score_nblocks(Nmax) * ncol and W.numel() >= Do * D and bias.numel() >= Do and a.numel() >= 3 * Do
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (x, W, bias, a, ds, dP, part, dx))
+    if n1 is None and Nmax > 128:
+        n1 = nodes
+    _call("scl_gat_score_bwd_var", _p(x), _p(W), _p(bias), _p(a), _p(ds), _p(dP), _p(part), _p(dx), _p(_klen(nodes)), None if n1 is None else _p(_klen(n1)),
+          B, Nmax, D, Do, _stream())
+
+
+def gat_softmax_agg_var_bwd(s, x, nodes, dout, ds, dx, stats, B, Nmax, D, temp, one_row=False):
+    """Backward of gat_softmax_agg_var: ds in the layout of s, dx [B, Nmax, D] with zeros at the rows >= nodes[b]; dout [B, Nmax, D]
+    (one_row: [B, D], s and ds [B, Nmax]); stats: f32 scratch [B, Nmax, 2] (one_row: [B, 2])."""
+    r = 1 if one_row else Nmax
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (s, x, dout, ds, dx, stats))
+    assert x.numel() >= B * Nmax * D and dx.numel() >= B * Nmax * D and s.numel() >= B * Nmax * r and ds.numel() >= B * Nmax * r
+    assert dout.numel() >= B * r * D and stats.numel() >= B * r * 2 and nodes.dtype == torch.int32 and nodes.numel() >= B
+    _call("scl_gat_softmax_agg_var_bwd", _p(s), _p(x), _p(_klen(nodes)), _p(dout), _p(ds), _p(dx), _p(stats), B, Nmax, D, 1 if one_row else 0,
+          float(temp), _stream())
+
+
 # ---- back-end pieces over channels-last fp32 maps (csrc/nn.hip) ----------------------------------------------------------------------
 def bn_nslabs(N):
     return L.load().scl_bn_nslabs(N)
@@ -870,6 +895,21 @@ def bn_bwd_masked(dy, y, x, mean, rstd, gamma, B, H, W, C, act, valid, counts, p
     """Backward of bn_fwd_masked: sums over the valid positions only, dx exactly 0 beyond.  sums: f32 [2 * C + 1]."""
     assert valid.numel() >= B and sums.numel() >= 2 * C + 1
     _call("scl_bn_bwd_masked", _p(dy), _p(y), _p(x), _p(mean), _p(rstd), _p(gamma), B, H, W, C, act, _p(_klen(valid)), _host_counts(counts, B),
+          _p(part), _p(sums), _p(dgamma), _p(dbeta), _p(dx), 1 if accumulate else 0, _stream())
+
+
+def bn_fwd_cols(x, B, H, W, C, gamma, beta, running_mean, running_var, nbt, momentum, eps, act, widths, counts, part, mean, rstd, y):
+    """bn_fwd_masked with the mask on the columns: utterance b owns w < widths[b] (int32 [B] on the GPU; counts: the same on the host) of every
+    row of x [B, H, W, C].  Batch statistics over the own positions only, y exactly 0 at and beyond.  part: bn_masked_nslabs * 2 * C doubles."""
+    assert widths.numel() >= B and x.numel() >= B * H * W * C and y.numel() >= B * H * W * C
+    _call("scl_bn_fwd_cols", _p(x), B, H, W, C, _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(nbt), momentum, eps, act,
+          _p(_klen(widths)), _host_counts(counts, B), _p(part), _p(mean), _p(rstd), _p(y), _stream())
+
+
+def bn_bwd_cols(dy, y, x, mean, rstd, gamma, B, H, W, C, act, widths, counts, part, sums, dgamma, dbeta, dx, accumulate=False):
+    """Backward of bn_fwd_cols: sums over the own positions only, dx exactly 0 at and beyond widths[b].  sums: f32 [2 * C + 1]."""
+    assert widths.numel() >= B and sums.numel() >= 2 * C + 1 and dy.numel() >= B * H * W * C and dx.numel() >= B * H * W * C
+    _call("scl_bn_bwd_cols", _p(dy), _p(y), _p(x), _p(mean), _p(rstd), _p(gamma), B, H, W, C, act, _p(_klen(widths)), _host_counts(counts, B),
           _p(part), _p(sums), _p(dgamma), _p(dbeta), _p(dx), 1 if accumulate else 0, _stream())
 
 
