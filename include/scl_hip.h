@@ -524,6 +524,30 @@ int scl_attn_fwd_packed_f32(const float* qkv, float* ctx, const int32_t* row0, i
                             void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* learned weighted sum over all hidden states of the encoder (csrc/layer_mix.hip)             */
+/* ------------------------------------------------------------------------------------------ */
+/* mix = sum_l s_l h_l with s = softmax(logits): logits f32 [nstates] on the device, 1 <= nstates <= SCL_LAYER_MIX_MAX_STATES, the soft-max
+ * computed inside every kernel (same code, same bits).  All arrays are flat, n = rows * E elements, n % 8 == 0, 16-byte aligned;
+ * `states` is a HOST array of nstates device pointers (f32 [n] each), read when the call is made.  Memory-bound, 16-byte accesses, no
+ * atomics, every summation order fixed: results are bitwise reproducible. */
+#define SCL_LAYER_MIX_MAX_STATES 64
+/* mix_bf16[i] = bf16(sum_l s_l states[l][i]), accumulated in f32 in index order (fma) */
+int scl_layer_mix_fwd(const float* const* states, int nstates, const float* logits, void* mix_bf16, int64_t n, void* stream);
+/* acc[i] = (accumulate ? acc[i] : 0) + s_index h[i] in f32 (fma): the fp32 scoring path keeps one hidden state alive at a time */
+int scl_layer_mix_acc_f32(const float* h, const float* logits, int nstates, int index, float* acc, int accumulate, int64_t n,
+                          void* stream);
+/* g = d(mix), bf16 (g_f32 == 0) or f32.  d_logits[l] = s_l (dS_l - sum_k s_k dS_k) with dS_l = <g, states[l]>: per-block partials and
+ * their sum in block order in fp64, stored as f32; d_logits is OVERWRITTEN.  The same pass writes g_last[i] = s_{nstates-1} g[i] (f32 [n]):
+ * the gradient at the last state, i.e. what the final LayerNorm's backward takes.  ws: scl_layer_mix_bwd_w_ws_bytes(n, nstates) bytes. */
+long long scl_layer_mix_bwd_w_ws_bytes(int64_t n, int nstates);
+int scl_layer_mix_bwd_w(const void* g, int g_f32, const float* const* states, int nstates, const float* logits, float* g_last, void* ws,
+                        float* d_logits, int64_t n, void* stream);
+/* dx[i] += s_index g[i] on the f32 residual gradient (fma); dx_bf16 (may be NULL) = bf16(dx[i] * keep-mask(seed, i) / (1 - p)): the bf16
+ * companion as scl_layernorm_bwd wrote it under its `dout` mask (element index row * E + column = i); p == 0: a plain cast */
+int scl_layer_mix_bwd_inject(const void* g, int g_f32, const float* logits, int nstates, int index, float* dx, void* dx_bf16, int64_t n,
+                             uint32_t seed, float p, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* feature-extractor layer 0 (Conv1d(1,C,10,5) + LayerNorm + GELU), fused fwd / bwd            */
 /* ------------------------------------------------------------------------------------------ */
 /* stats (optional, may be NULL): f32 [B*T0][2] = per-frame (mean, rstd) of the LayerNorm, written by the forward and read

@@ -553,6 +553,9 @@ def main(argv=None):
             for k, v in val_detail.items():
                 writer.add_scalar("val_{}".format(k), v, epoch)
         print("\n{} - {} - {} ".format(epoch, running_loss, val_loss))
+        mix = model.layer_mix_weights() if hasattr(model, "layer_mix_weights") else None
+        if mix is not None:      # ssl_layer_mix: the share of each hidden state (0: positional-conv residual ... last: final LayerNorm)
+            print("layer mix: " + " ".join("%.4f" % v for v in mix.tolist()))
         scheduler.step()
         early(val_acc, model, epoch)
         if early.early_stop:

@@ -183,7 +183,7 @@ def row_layout(cfg, lengths, B, L, *, min_samples, refuse_short, score_f32, devi
 class W2VConfig:
     def __init__(self, conv_dim=512, conv_kernels=(10, 3, 3, 3, 3, 2, 2), conv_strides=(5, 2, 2, 2, 2, 2, 2), embed=1024,
                  layers=24, heads=16, ffn=4096, pos_k=128, pos_groups=16, final_dim=768, latent_vars=320, latent_groups=2,
-                 encoder_layerdrop=0.0, dropout=0.0, attention_dropout=0.0, activation_dropout=0.0, dropout_input=0.0):
+                 encoder_layerdrop=0.0, dropout=0.0, attention_dropout=0.0, activation_dropout=0.0, dropout_input=0.0, layer_mix=False):
         # element-dropout probabilities of fairseq's Wav2Vec2Config (read from the checkpoint's cfg by scl_amd.checkpoint; the
         # reference runs the encoder in train mode, model/xlsr.py:33-41): `dropout` after the positional conv and on the outputs of
         # out_proj / fc2, `attention_dropout` on the attention probabilities, `activation_dropout` after the FFN's GELU, `dropout_input`
@@ -194,6 +194,12 @@ class W2VConfig:
         self.pos_k, self.pos_groups = pos_k, pos_groups
         self.final_dim, self.latent_vars, self.latent_groups = final_dim, latent_vars, latent_groups
         self.encoder_layerdrop = encoder_layerdrop
+        # YAML `ssl_layer_mix`: the encoder hands on the learned soft-max-weighted sum over all layers + 1 hidden states (csrc/layer_mix.hip)
+        # instead of the last layer's alone; one more parameter, `layer_mix.weight` [layers + 1], beside the LL projection (mix_specs)
+        self.layer_mix = bool(layer_mix)
+        if self.layer_mix and layers + 1 > ops.LAYER_MIX_MAX_STATES:
+            raise SclError("ssl_layer_mix: %d layers give %d hidden states; the mix kernels take at most %d"
+                           % (layers, layers + 1, ops.LAYER_MIX_MAX_STATES))
         assert embed % heads == 0 and (embed // heads) % 8 == 0 and conv_dim % 8 == 0 and pos_k % 2 == 0
         assert (embed // pos_groups) % 8 == 0
 
@@ -211,6 +217,13 @@ class W2VConfig:
     def xlsr_2b(**kw):
         """XLS-R 2B as fairseq publishes its config (120-wide heads); the conv stack and the positional convolution of the 300M model."""
         return W2VConfig(embed=1920, layers=48, heads=16, ffn=7680, final_dim=1024, **kw)
+
+    def with_layer_mix(self, on=True):
+        """A copy of this config with the layer mix switched (the cap on the number of hidden states is checked as at construction)."""
+        fields = {k: getattr(self, k) for k in ("conv_dim", "conv_kernels", "conv_strides", "embed", "layers", "heads", "ffn", "pos_k", "pos_groups",
+                                                "final_dim", "latent_vars", "latent_groups", "encoder_layerdrop", "dropout", "attention_dropout",
+                                                "activation_dropout", "dropout_input")}
+        return W2VConfig(layer_mix=on, **fields)
 
     def conv_lens(self, L):
         out = []
@@ -237,12 +250,15 @@ W2V_ARCHS = {"xlsr_300m": W2VConfig, "xlsr_1b": W2VConfig.xlsr_1b, "xlsr_2b": W2
 def w2v_config_from(args):
     """The encoder a YAML names (needs no GPU).  `w2v_arch`: one of W2V_ARCHS ("xlsr_300m" when absent: the reference's only encoder;
     "tiny" for tests and plumbing), or a mapping of W2VConfig fields such as {embed: 1280, layers: 48, heads: 16, ffn: 5120, final_dim: 1024}
-    (fields left out keep the 300M model's values).  `encoder_layerdrop` of the YAML applies to every arch but "tiny"."""
+    (fields left out keep the 300M model's values).  `encoder_layerdrop` of the YAML applies to every arch but "tiny".
+    `ssl_layer_mix: true` (or `layer_mix` inside a mapping): W2VConfig.layer_mix, every arch."""
     arch = args.get("w2v_arch", "xlsr_300m")
     layerdrop = float(args.get("encoder_layerdrop", 0.0))
+    mix = bool(args.get("ssl_layer_mix", False))
     if isinstance(arch, collections.abc.Mapping):
         fields = dict(arch)
         fields.setdefault("encoder_layerdrop", layerdrop)
+        fields.setdefault("layer_mix", mix)
         try:
             return W2VConfig(**fields)
         except TypeError as e:
@@ -250,7 +266,10 @@ def w2v_config_from(args):
     if arch not in W2V_ARCHS:
         raise ValueError("w2v_arch: unknown encoder %r; the names are %s, or give a mapping of W2VConfig fields"
                          % (arch, ", ".join(sorted(W2V_ARCHS))))
-    return W2V_ARCHS[arch](encoder_layerdrop=layerdrop)
+    cfg = W2V_ARCHS[arch](encoder_layerdrop=layerdrop)
+    if mix:      # after construction: "tiny" takes no fields, and the switch-off path stays the call it was
+        cfg = cfg.with_layer_mix()
+    return cfg
 
 
 def param_specs(cfg, prefix="ssl_model.model."):
@@ -286,6 +305,16 @@ def param_specs(cfg, prefix="ssl_model.model."):
            (prefix + "project_q.weight", (cfg.final_dim, cfg.final_dim), False), (prefix + "project_q.bias", (cfg.final_dim,), False),
            (prefix + "final_proj.weight", (cfg.final_dim, E), False), (prefix + "final_proj.bias", (cfg.final_dim,), False)]
     return sp
+
+
+MIX_WEIGHT = "layer_mix.weight"
+
+
+def mix_specs(cfg):
+    """The layer mix's one parameter (cfg.layer_mix; nothing without it): the f32 logits of the soft-max over the layers + 1 hidden states,
+    zeros at initialisation (a uniform average).  A model puts it directly behind LL.bias, at the module root of its state dict: inside
+    trainable_range() with and without a frozen encoder, and no offset in front of it moves."""
+    return [(MIX_WEIGHT, (cfg.layers + 1,), True)] if cfg.layer_mix else []
 
 
 def plan_group_launches(pend, final, carry=True, round_tiles=256, max_members=8):
@@ -448,6 +477,12 @@ class Encoder:
         d["f"] = [bf(Mr * Fd) for _ in range(cfg.layers)]
         d["a"] = [bfz(Mp, Fd) for _ in range(cfg.layers)]
         d["out"], d["omean"], d["orstd"] = bf(Mr * E), f32(Mr), f32(Mr)
+        if cfg.layer_mix:
+            # the final LayerNorm's output as the f32 hidden state h_L (the one new activation; xin[0 .. L-1] are the others and `out` holds
+            # the mix); for the backward s_L d(mix), which that LayerNorm's backward takes, and the fp64 block partials of d(logits)
+            d["hL"], d["mix_gL"] = f32(Mr * E), f32(Mr * E)
+            d["mix_ws"] = torch.empty(ops.layer_mix_bwd_w_ws_bytes(Mr * E, cfg.layers + 1), dtype=torch.uint8, device=dev)
+            d["mix_a"] = torch.zeros(ops.LAYER_MIX_MAX_STATES, dtype=torch.float32, device=dev)      # the backward's own copy of the logits
         if packed:      # the padded ends of the packed stretch: xin[0] before the pack, the output behind the unpack, d(xin[0]) behind its unpack
             d["xin_pad"], d["out_pad"], d["dxin_pad"] = f32(M * E), bf(M * E), f32(M * E)
         # backward scratch (shared by all layers)
@@ -544,6 +579,22 @@ class Encoder:
         """The main stream goes on only when the second stream has drained: its inputs may be overwritten, its gradients read."""
         if self.wstream is not None:
             ops.stream_wait(torch.cuda.current_stream(), self.wstream)
+
+    def _mix_states(self, d):
+        """The hidden states of the layer mix in a bf16-path buffer set, in index order: the residual stream entering each layer
+        (xin[0]: behind the positional convolution and its dropout; a skipped layer copies its input on) and the final LayerNorm's output."""
+        return d["xin"][: self.cfg.layers] + [d["hL"]]
+
+    def _mix_bwd_w(self, d, g, Mt):
+        """d(logits) into the flat gradient buffer (overwritten) and s_L g into d["mix_gL"], from g = d(mix) over Mt rows.  Returns the
+        logits the whole backward reads: a copy taken here, because an optimizer that steps underneath the backward (optim._StepOverlap)
+        updates the tail of the flat buffer, the logits with it, as soon as this gradient is announced."""
+        S, o = self.cfg.layers + 1, self.P.off(MIX_WEIGHT)
+        n4 = (S + 3) // 4 * 4      # inside the parameter's slot: FlatParams aligns every tensor to 8 elements
+        ops.axpby(self.P.flat[o:o + n4], None, 1.0, 0.0, d["mix_a"], n4)
+        logits = d["mix_a"][:S]
+        ops.layer_mix_bwd_w(g, self._mix_states(d), logits, d["mix_gL"], d["mix_ws"], self.P.g(MIX_WEIGHT), Mt * self.cfg.embed)
+        return logits
 
     def _slab(self, d, slot, numel):
         """The split-K slab buffer of `slot` with room for `numel` floats.  A buffer only grows; the outgrown one is kept alive because
@@ -725,7 +776,9 @@ class Encoder:
         stack, zero_tail_rows(x0), the positional convolution and its dropout stay padded (the convolution needs the utterance's slab);
         then xin[0] is packed, the layers run over Mq rows with the packed attention, and the output is unpacked into the padded
         [B*T, E] buffer with zero rows beyond each utterance.  The rows [row0[B], Mq) belong to no utterance: they start as zeros (the
-        pack writes them), every kernel but the attention works row by row and keeps them finite, and the attention writes zeros there."""
+        pack writes them), every kernel but the attention works row by row and keeps them finite, and the attention writes zeros there.
+        cfg.layer_mix: enc_out is the soft-max-weighted sum over the layers + 1 hidden states (scl_layer_mix_fwd over the rows of the
+        transformer layers, ahead of the unpack) instead of the final LayerNorm's output, which is then kept in f32 as the last state."""
         cfg, P = self.cfg, self.P
         B, L = x.shape
         layout = RowLayout.of(frames, packed)
@@ -806,8 +859,13 @@ class Encoder:
                            R=d["x1"][n], rmode=1, drop_p=p_res, drop_seed=sseed(n, self.SITE_3))                                # dropout3
             if p_res > 0 and recording:
                 self._slot(slots, dsc, None, n, self.SITE_3)
-        ops.layernorm_fwd(d["xin"][cfg.layers], self.b("encoder.layer_norm.weight"), self.b("encoder.layer_norm.bias"),
-                          d["out"], None, d["omean"], d["orstd"], Mt, E)
+        if cfg.layer_mix:      # h_L in f32, then the mix of the layers + 1 states over the Mt rows (packed rows in a packed layout)
+            ops.layernorm_fwd(d["xin"][cfg.layers], self.b("encoder.layer_norm.weight"), self.b("encoder.layer_norm.bias"),
+                              None, d["hL"], d["omean"], d["orstd"], Mt, E)
+            ops.layer_mix_fwd(self._mix_states(d), self.P.f32(MIX_WEIGHT), d["out"], Mt * E)
+        else:
+            ops.layernorm_fwd(d["xin"][cfg.layers], self.b("encoder.layer_norm.weight"), self.b("encoder.layer_norm.bias"),
+                              d["out"], None, d["omean"], d["orstd"], Mt, E)
         out = d["out"]
         if layout.packed:      # back to the padded [B*T, E] rectangle, zero rows beyond each utterance
             out = d["out_pad"]
@@ -852,7 +910,10 @@ class Encoder:
         its f32 result is packed into the other ping-pong buffer, the layers and the final LayerNorm run over Mq rows with the streaming
         fp32 attention of csrc/attention_f32.hip (no S / Pm buffers, no chunk loop above 512 frames), and the output is unpacked into
         the padded [B*T, E] buffer with zero rows beyond each utterance.  The head dims of stream_attn_takes (72..128:
-        csrc/attention_f32_wide.hip); any other raises NotImplementedError."""
+        csrc/attention_f32_wide.hip); any other raises NotImplementedError.
+        cfg.layer_mix: the f32 weighted sum over the hidden states is returned instead; one layer is alive at a time here (xa / xb), so
+        scl_layer_mix_acc_f32 adds each state as it appears: behind the positional convolution (and the pack), behind every layer but
+        the last, and behind the final LayerNorm."""
         cfg, P = self.cfg, self.P
         B, L = x.shape
         C, E, H, Fd, K, G = cfg.conv_dim, cfg.embed, cfg.heads, cfg.ffn, cfg.pos_k, cfg.pos_groups
@@ -885,7 +946,14 @@ class Encoder:
                      a3b=torch.empty(R * 3 * Fd + 2 * slack, dtype=torch.bfloat16, device=self.dev))
             if layout.packed:      # the padded rectangle behind the unpack
                 d["out_pad"] = f32(M * E)
+            if cfg.layer_mix:      # the running weighted sum: one layer is alive at a time here, so every state is added as it appears
+                d["mix"] = f32(R * E)
             return d
+        mix_a = P.f32(MIX_WEIGHT) if cfg.layer_mix else None
+
+        def mix_add(h, index):
+            if mix_a is not None:
+                ops.layer_mix_acc_f32(h, mix_a, index, d["mix"], Mt * E, accumulate=index > 0)
         d = self._set(("f32",) + layout.key(B, L) + ((bc,) if long_attn else ()), make, layout, f32=True)
         fw = self._f32_weights()
         Wf = lambda name, ld: Op(P.flat, ld, offset=P.off(self.n(name)))
@@ -938,6 +1006,7 @@ class Encoder:
         if layout.packed:      # valid frames back to back into the other ping-pong buffer, rows [row0[B], Mt) zero
             ops.pack_rows(xin, xout, layout.row0, B, T, E, Mt)
             xin, xout = xout, xin
+        mix_add(xin, 0)
         qkv = d["qkv"]
         if not layout.packed:
             S, Pm = d["S"], d["Pm"]
@@ -972,16 +1041,28 @@ class Encoder:
                             bias=self.b(pn + "fc1.bias"), act=ACT_GELU)
                 lin(d["a"], Fd, pn + "fc2.weight", E, xout, bias=self.b(pn + "fc2.bias"), R=d["x1"], rmode=1)
             xin, xout = xout, xin
+            if n + 1 < cfg.layers:      # the last layer's raw output is no state of the mix: its LayerNorm below is
+                mix_add(xin, n + 1)
         ops.layernorm_fwd(xin, self.b("encoder.layer_norm.weight"), self.b("encoder.layer_norm.bias"), None, d["out"], mean, rstd, Mt, E)
+        mix_add(d["out"], cfg.layers)
+        out = d["mix"] if cfg.layer_mix else d["out"]
         if layout.packed:      # back to the padded [B*T, E] rectangle, zero rows beyond each utterance
-            ops.unpack_rows(d["out"], d["out_pad"], layout.row0, B, T, E, Mt)
+            ops.unpack_rows(out, d["out_pad"], layout.row0, B, T, E, Mt)
             return d["out_pad"], T
-        return d["out"], T
+        return out, T
 
     # ---- backward --------------------------------------------------------------------------------
-    def backward(self, ctx, d_out):
+    def backward(self, ctx, d_out, mix_only=False, after_mix=None):
         """d_out: bf16 or f32 [M, E] gradient w.r.t. forward()'s output.  Writes every parameter
         gradient of the encoder into the flat gradient buffer (overwrite semantics).
+        With cfg.layer_mix, d_out = g = d(mix).  First of all, since it needs nothing the chain produces, scl_layer_mix_bwd_w writes
+        d(logits) and s_L g, and after_mix() is called: the logits sit beside LL at the tail of the flat buffer, whose gradients a
+        data-parallel caller announces as final before the chain starts.  mix_only (a frozen encoder): that is all.  Otherwise the final
+        LayerNorm's backward takes s_L g; at the top of layer n's backward (n <= L - 2, a skipped layer included) s_{n+1} g is added to the
+        pair (d(xin[n+1]) f32, its bf16 companion under the dropout3 mask of the next active layer at or below n, as the LayerNorm
+        backward above wrote it) before anything reads it; behind the loop s_0 g goes into d(xin[0]), f32 only.  Nothing else moves: the
+        residual column sums riding on the LayerNorm backwards then sum the complete d(xout) / d(x1), and every weight-gradient launch, carried
+        or on the side stream, is issued behind the injection into the pair it reads.
         A forward with `frames` (ctx["layout"] padded or packed): d_out's rows beyond an utterance's frames must be 0 (the head's masked mean pool and feats
         give that).  Two kernels then carry the mask: scl_attn_bwd_varlen writes zero dqkv rows there, and the rows of d(x0) are zeroed
         behind the positional convolution's data gradient (the backward of the forward's zero_tail_rows(x0)).  Every other kernel of the
@@ -1010,6 +1091,15 @@ class Encoder:
             d_out = d[key]
         elif not (WGRAD_GROUP and Mp // 64 >= WGRAD_GROUP_MIN_KSTEPS):
             Mp = M      # short reductions stay on the split-K path, which is faster on the exact row count (pack of 11: 16.2 vs 17.6 ms per step)
+        mix_g = mix_a = None
+        if cfg.layer_mix:
+            mix_g = d_out
+            mix_a = self._mix_bwd_w(d, mix_g, Mt)
+            if after_mix is not None:
+                after_mix()
+            if mix_only:
+                return []
+            d_out = d["mix_gL"]
         nlnM = ops.layernorm_bwd_nparts(Mt)
         p_res, p_attn, p_act, p_in = ctx.get("drop", (0.0, 0.0, 0.0, 0.0))
         step_seed = ctx.get("step_seed", 0)
@@ -1037,6 +1127,11 @@ class Encoder:
         d["wgrad_group"], d["wgrad_pending"] = [], []      # nothing is carried across backward passes (an interrupted one may have left work)
         for n in reversed(range(cfg.layers)):
             pn = "encoder.layers.%d." % n
+            if mix_g is not None and n <= cfg.layers - 2:      # d(xin[n+1]) += s_{n+1} g, the bf16 companion under the mask it was written with
+                (sd, p_), lyr = mask3_of([m_ for m_ in active if m_ <= n])
+                e = ops.layer_mix_bwd_inject(mix_g, mix_a, n + 1, dx, dxb, Mt * E, seed=sd, p=p_)
+                if lyr is not None:
+                    self._slot(slots, e, ops.LAYER_MIX_INJECT_SEED, lyr, self.SITE_3)
             if n in ctx["skipped"]:
                 for nm in ("self_attn_layer_norm.weight", "self_attn_layer_norm.bias", "self_attn.q_proj.weight",
                            "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.q_proj.bias", "self_attn.k_proj.bias",
@@ -1112,6 +1207,8 @@ class Encoder:
             prev_off = this_off
             if self.on_grads_ready is not None and ready_off is not None:
                 ops.host_callback(self.on_grads_ready, ready_off)
+        if mix_g is not None:      # d(xin[0]) += s_0 g: only the f32 side is read from here on
+            ops.layer_mix_bwd_inject(mix_g, mix_a, 0, dx, None, Mt * E)
         if layout.packed:      # d(xin[0]) back to the padded rectangle (zero rows beyond each utterance): the convolution needs the slab
             ops.unpack_rows(dx, d["dxin_pad"], layout.row0, B, T, E, Mt)
             dx, (other, otherb) = d["dxin_pad"], d["dx0_pad"]

@@ -211,8 +211,14 @@ def _protos():
         "scl_unpack_rows": ([_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp], _i32),
         # attention_f32.hip
         "scl_attn_fwd_packed_f32": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp], _i32),
+        # layer_mix.hip
+        "scl_layer_mix_fwd": ([P(_vp), _i32, _vp, _vp, _i64, _vp], _i32),
+        "scl_layer_mix_acc_f32": ([_vp, _vp, _i32, _i32, _vp, _i32, _i64, _vp], _i32),
+        "scl_layer_mix_bwd_w_ws_bytes": ([_i64, _i32], ctypes.c_longlong),
+        "scl_layer_mix_bwd_w": ([_vp, _i32, P(_vp), _i32, _vp, _vp, _vp, _vp, _i64, _vp], _i32),
+        "scl_layer_mix_bwd_inject": ([_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _u32, _f32, _vp], _i32),
         # conv0.hip
-        "scl_conv0_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp], _i32),
+        "scl_conv0_fwd":([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp], _i32),
         "scl_conv0_fwd_f32": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp], _i32),
         "scl_conv0_bwd_nparts": ([_i32, _i32, _i32, _i32], _i32),
         "scl_conv0_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp], _i32),

@@ -9,7 +9,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .encoder import Encoder, RowLayout, VarlenSets, shape_entry, w2v_config_from
+from .encoder import MIX_WEIGHT, Encoder, RowLayout, VarlenSets, shape_entry, w2v_config_from
 from .params import FlatParams
 
 HEAD_DIM = 128
@@ -31,6 +31,8 @@ def init_parameters_(P, cfg, seed=0):
             t = torch.randn(shape, generator=g) * math.sqrt(4.0 / (cfg.pos_k * cfg.embed))
         elif short == "encoder.pos_conv.0.weight_g":
             continue
+        elif name == MIX_WEIGHT:      # a uniform average of the hidden states; draws nothing, so every other tensor starts as without it
+            t = torch.zeros(shape)
         elif name.startswith("LL.") or name.startswith("backend."):
             fan_in = shape[-1] if len(shape) > 1 else HEAD_DIM
             t = (torch.rand(shape, generator=g) * 2 - 1) / math.sqrt(fan_in)
@@ -116,6 +118,13 @@ class FlatModel(nn.Module):
         self.out_dim = self.cfg.embed
         self.grad_sync = None   # scl_amd.parallel.GradSync when data-parallel (set by FusedAdamW)
         self.pretrained_loaded = maybe_load_pretrained(self, args)
+
+    def layer_mix_weights(self):
+        """softmax(layer_mix.weight) on the host: the share of each of the layers + 1 hidden states in what the encoder hands on (YAML
+        `ssl_layer_mix`; index 0 the positional-conv residual, index `layers` the final LayerNorm's output).  None with the switch off."""
+        if not self.cfg.layer_mix:
+            return None
+        return torch.softmax(self.P.f32(MIX_WEIGHT).detach().float().cpu(), dim=0)
 
     # nn.Module plumbing ----------------------------------------------------------------------------
     def _apply(self, fn, recurse=True):

@@ -115,7 +115,7 @@ class FrontHeadModel(FlatModel):
         head_params = list(head.named_parameters())
         frozen = getattr(head, "frozen_names", ())      # no gradient in the reference
         specs = param_specs(self.cfg) + [("LL.weight", (FEAT_DIM, self.cfg.embed), True), ("LL.bias", (FEAT_DIM,), True)] + \
-            [(n, tuple(p.shape), n not in frozen) for n, p in head_params]
+            ENC.mix_specs(self.cfg) + [(n, tuple(p.shape), n not in frozen) for n, p in head_params]
         self._make_params(specs)
         self._head_lo = self.P.off(next(n for n, _ in head_params if n not in frozen))
         init_parameters_(self.P, self.cfg, seed)
@@ -129,7 +129,7 @@ class FrontHeadModel(FlatModel):
         for n, child in head.named_children():
             self.add_module(n, child)
         for name, p in self.P.params.items():
-            if name.startswith("ssl_model.") or name.startswith("LL."):
+            if name.startswith("ssl_model.") or name.startswith("LL.") or name == ENC.MIX_WEIGHT:
                 register_by_name(self, self.front_prefix + name, p)
             else:
                 mod = self
@@ -246,7 +246,15 @@ class FrontHeadModel(FlatModel):
             ops.cast_bf16(st["d_feats"], st["dfe_bf"], M * FEAT_DIM)
             ops.colsum_reduce(st["d_feats"], st["cs"], P.g("LL.bias"), M, FEAT_DIM)
             self.ssl._wgrad(sv["ectx"]["d"], Op(st["dfe_bf"], FEAT_DIM), Op(sv["enc_out"], E), P.g("LL.weight"), FEAT_DIM, E, M)
-            if not self.flag_fix_ssl:
+            if self.cfg.layer_mix:
+                # the mix's logits lie between LL and the torch head: final once the encoder backward's first launch has run (after_mix);
+                # a frozen encoder still forms d(mix) for them alone (mix_only) and announces nothing, as without the mix
+                ops.gemm(Op(st["dfe_bf"], FEAT_DIM), Op(P.bf16, E, offset=P.off("LL.weight")), st["denc"], M, E, FEAT_DIM, b_t=True)
+                ready = None
+                if self.grad_sync is not None and not self.flag_fix_ssl:
+                    ready = lambda: ops.host_callback(self.grad_sync.ready_above, P.off("LL.weight"))
+                enc_slots = self.ssl.backward(sv["ectx"], st["denc"], mix_only=self.flag_fix_ssl, after_mix=ready)
+            elif not self.flag_fix_ssl:
                 ops.gemm(Op(st["dfe_bf"], FEAT_DIM), Op(P.bf16, E, offset=P.off("LL.weight")), st["denc"], M, E, FEAT_DIM, b_t=True)
                 if self.grad_sync is not None:     # LL and the torch head's gradients (the END of the flat buffer) are final here
                     ops.host_callback(self.grad_sync.ready_above, P.off("LL.weight"))

@@ -10,7 +10,8 @@ numeric step executed by the HIP kernels behind the C ABI.
     loss(output, feats, emb, labels, config, info=None) -> dict of 0-d tensors, summed and .backward()-ed by the caller
 
 State-dict keys equal the reference's (ssl_model.model.<fairseq keys>, LL.*, first_bn.*, first_bn1.*,
-backend.m_frame_level.{0,3,6}.*, backend.m_utt_level.*), so its checkpoints load unchanged.
+backend.m_frame_level.{0,3,6}.*, backend.m_utt_level.*), so its checkpoints load unchanged.  The YAML key `ssl_layer_mix: true` (not in
+the reference) adds one, `layer_mix.weight`: LL then reads the learned weighted sum over all hidden states of the encoder (encoder.py).
 `train_loss.backward()` reaches the hand-written backward through two torch.autograd.Function
 boundaries (model, loss); parameter gradients are written straight into the flat gradient buffer.
 """
@@ -37,8 +38,9 @@ X3_OFF = {"x3": False} if HEAD_F32 else {}      # the training head's f32 GEMMs 
 DROP_P = 0.5  # BackEnd(128, 128, 2, 0.5, False): torch.nn.Dropout(0.5) after each frame-level layer
 
 
-def head_specs(embed):
-    return [("LL.weight", (HEAD_DIM, embed), True), ("LL.bias", (HEAD_DIM,), True),
+def head_specs(embed, mix=()):
+    """mix: encoder.mix_specs(cfg) — the layer mix's logits directly behind LL.bias (nothing with the switch off)."""
+    return [("LL.weight", (HEAD_DIM, embed), True), ("LL.bias", (HEAD_DIM,), True)] + list(mix) + [
             ("backend.m_frame_level.0.weight", (HEAD_DIM, HEAD_DIM), True), ("backend.m_frame_level.0.bias", (HEAD_DIM,), True),
             ("backend.m_frame_level.3.weight", (HEAD_DIM, HEAD_DIM), True), ("backend.m_frame_level.3.bias", (HEAD_DIM,), True),
             ("backend.m_frame_level.6.weight", (HEAD_DIM, HEAD_DIM), True), ("backend.m_frame_level.6.bias", (HEAD_DIM,), True),
@@ -72,7 +74,7 @@ class Model(FlatModel):
         if self.contra_mode not in ("all", "one"):
             raise ValueError("Unknown mode: {}".format(self.contra_mode))     # loss_metrics.py:161
         # memory order: trainable encoder, head, then the checkpoint-only tensors (FlatParams puts those last)
-        self._make_params(param_specs(self.cfg) + head_specs(self.cfg.embed))
+        self._make_params(param_specs(self.cfg) + head_specs(self.cfg.embed, ENC.mix_specs(self.cfg)))
         for name, p in self.P.params.items():
             register_by_name(self, name, p)
         # defined-but-unused modules of the reference (linear_nll:108-109) — state-dict compatibility only
@@ -248,7 +250,15 @@ class Model(FlatModel):
         ops.add_f32(hb["dfe"], st["d_feats"], hb["dfe"], hb["dfe_bf"], M * HEAD_DIM)
         ops.colsum_reduce(hb["dfe"], hb["cs"], P.g("LL.bias"), M, HEAD_DIM)
         self.encoder._wgrad(sv["ectx"]["d"], Op(hb["dfe_bf"], HEAD_DIM), Op(sv["enc_out"], E), P.g("LL.weight"), HEAD_DIM, E, M)
-        if not self.flag_fix_ssl:
+        if self.cfg.layer_mix:
+            # the mix's logits lie among the head's gradients: final once the encoder backward's first launch has run (after_mix), and a
+            # frozen encoder still forms d(mix) for them alone (mix_only); the frozen case announces nothing, as without the mix
+            ops.gemm(Op(hb["dfe_bf"], HEAD_DIM), W("LL.weight", E), hb["denc"], M, E, HEAD_DIM, b_t=True)
+            ready = None
+            if self.grad_sync is not None and not self.flag_fix_ssl:
+                ready = lambda: ops.host_callback(self.grad_sync.ready_above, P.off("LL.weight"))
+            enc_slots = self.encoder.backward(sv["ectx"], hb["denc"], mix_only=self.flag_fix_ssl, after_mix=ready)
+        elif not self.flag_fix_ssl:
             ops.gemm(Op(hb["dfe_bf"], HEAD_DIM), W("LL.weight", E), hb["denc"], M, E, HEAD_DIM, b_t=True)
             if self.grad_sync is not None:      # head gradients (the END of the flat buffer) are final: start their all-reduce
                 ops.host_callback(self.grad_sync.ready_above, P.off("LL.weight"))

@@ -629,6 +629,50 @@ def unpack_rows(src, dst, row0, B, T, C, Mq):
     _call("scl_unpack_rows", _p(src), _p(dst), _isf32(src), _p(_klen(row0)), B, T, C, int(Mq), _stream())
 
 
+# ---- csrc/layer_mix.hip: the learned weighted sum over the encoder's hidden states ---------------------------------------------------
+LAYER_MIX_MAX_STATES = 64      # SCL_LAYER_MIX_MAX_STATES
+LAYER_MIX_INJECT_SEED = 8      # position of the mask seed in a recorded scl_layer_mix_bwd_inject call
+
+
+def _mix_table(states, n):
+    assert 1 <= len(states) <= LAYER_MIX_MAX_STATES and n % 8 == 0
+    assert all(h.dtype == torch.float32 and h.numel() >= n for h in states)
+    return (ctypes.c_void_p * len(states))(*[_ptr(h) for h in states])
+
+
+def layer_mix_fwd(states, logits, mix_bf16, n):
+    """mix_bf16[:n] = bf16(sum_l softmax(logits)[l] * states[l][:n]): f32 accumulation in index order.  states: f32 buffers, one per logit."""
+    assert logits.dtype == torch.float32 and logits.numel() == len(states) and mix_bf16.dtype == torch.bfloat16 and mix_bf16.numel() >= n
+    tab = _mix_table(states, n)
+    return _call("scl_layer_mix_fwd", tab, len(states), _p(logits), _p(mix_bf16), n, _stream(), keep=tab)
+
+
+def layer_mix_acc_f32(h, logits, index, acc, n, accumulate=True):
+    """acc[:n] (+)= softmax(logits)[index] * h[:n], all f32."""
+    assert h.dtype == acc.dtype == logits.dtype == torch.float32 and h.numel() >= n and acc.numel() >= n
+    return _call("scl_layer_mix_acc_f32", _p(h), _p(logits), logits.numel(), int(index), _p(acc), 1 if accumulate else 0, n, _stream())
+
+
+def layer_mix_bwd_w_ws_bytes(n, nstates):
+    return int(L.load().scl_layer_mix_bwd_w_ws_bytes(n, nstates))
+
+
+def layer_mix_bwd_w(g, states, logits, g_last, ws, d_logits, n):
+    """d_logits (overwritten) = the soft-max Jacobian applied to the dot products <g, states[l]> (fp64 partials, fixed order), and
+    g_last[:n] = softmax(logits)[-1] * g in f32.  g: bf16 or f32; ws: layer_mix_bwd_w_ws_bytes(n, len(states)) bytes."""
+    assert logits.numel() == len(states) == d_logits.numel() and d_logits.dtype == g_last.dtype == torch.float32
+    assert g.numel() >= n and g_last.numel() >= n and ws.numel() * ws.element_size() >= layer_mix_bwd_w_ws_bytes(n, len(states))
+    tab = _mix_table(states, n)
+    return _call("scl_layer_mix_bwd_w", _p(g), _isf32(g), tab, len(states), _p(logits), _p(g_last), _p(ws), _p(d_logits), n, _stream(), keep=tab)
+
+
+def layer_mix_bwd_inject(g, logits, index, dx, dx_bf16, n, seed=0, p=0.0):
+    """dx[:n] += softmax(logits)[index] * g; dx_bf16 (or None) = bf16(dx * keep-mask(seed, i) / (1 - p)), the mask of layernorm_bwd's dout."""
+    assert dx.dtype == torch.float32 and g.numel() >= n and dx.numel() >= n and (dx_bf16 is None or dx_bf16.numel() >= n)
+    return _call("scl_layer_mix_bwd_inject", _p(g), _isf32(g), _p(logits), logits.numel(), int(index), _p(dx), _p(dx_bf16), n,
+                 int(seed), float(p), _stream())
+
+
 def attn_long_ws_bytes(B, T, H):
     return int(L.load().scl_attn_long_ws_bytes(B, T, H))
 
