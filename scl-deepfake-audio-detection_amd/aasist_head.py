@@ -15,8 +15,10 @@ utterance only through a convolution's taps, the soft-max over the time axis and
 written as exact zeros (selected, not multiplied) at and beyond the utterance's width — what the convolution's zero border holds for the
 utterance alone — the attention pooling runs over the utterance's own columns, and the graph kernels take their node counts per utterance
 (node_counts; csrc/resstack.hip, gat.hip, graph.hip).  The masks live in the fused kernels, so the mode has their limits:
-min_frames() .. max_frames() frames per utterance.  Beyond them AasistHead.forward_frames_long (aasist_long.py, SCL_AASIST_LENGTHS=long) keeps the
-same contract on the per-layer composition with count tables, up to 3074 frames.
+min_frames() .. max_frames() frames per utterance.  Beyond them one per-layer composition with count tables (aasist_long.py), up to 3074
+frames, is entered in one of two modes: AasistHead.forward_frames_long (SCL_AASIST_LENGTHS=long) keeps the same scoring contract, and
+AasistHead.forward_frames_train trains on the zero-padded batch with batch statistics over its own positions.  All three entries validate
+their frames argument with check_frames.
 
 Reference quirks kept on purpose: Residual_block applies conv1 to its INPUT (the bn1+SELU result is discarded, :414-420; in training
 that BatchNorm still updates its running statistics); the temporal / spectral attention pools share one 1x1-conv score map.
@@ -78,6 +80,18 @@ def max_nodes(cfg=None):
 def max_frames(cfg=None):
     """The most frames per utterance forward_frames takes (a last partial pool window included)."""
     return max_nodes(cfg) * POOL + POOL - 1
+
+
+def check_frames(feats, frames, hi, takes):
+    """The frames argument of every forward_frames* entry, as ints: one count per row of feats [B, T, 128], each in min_frames() .. T and
+    at most `hi`, the entry's own limit; `takes` ends the sentence "an utterance of n frames exceeds the `hi` frames ..."."""
+    frames = [int(t) for t in frames]
+    lo = min_frames()
+    if len(frames) != feats.shape[0] or not frames or min(frames) < lo or max(frames) > feats.shape[1]:
+        raise ValueError("frames: need one count in %d..%d per row of the %r batch, got %r" % (lo, feats.shape[1], tuple(feats.shape), frames))
+    if max(frames) > hi:
+        raise ValueError("AASIST back-end: an utterance of %d frames exceeds the %d frames %s" % (max(frames), hi, takes))
+    return frames
 
 
 def _xavier(*size):
@@ -259,14 +273,9 @@ class AasistHead(nn.Module):
         if not AasistHead.frames_supported(self):
             raise NotImplementedError("AasistHead.forward_frames runs on the fused stack and graph kernels only (csrc/resstack.hip, graph.hip): "
                                       "this configuration's shapes are not theirs, or SCL_AASIST_FUSED=0 / SCL_AASIST_FUSED_GRAPH=0 is set")
-        frames = [int(t) for t in frames]
-        lo, hi = min_frames(), max_frames(self.pool_cfg)
-        if len(frames) != feats.shape[0] or not frames or min(frames) < lo or max(frames) > feats.shape[1]:
-            raise ValueError("frames: need one count in %d..%d per row of the %r batch, got %r" % (lo, feats.shape[1], tuple(feats.shape), frames))
-        if max(frames) > hi:
-            raise ValueError("AASIST back-end: an utterance of %d frames exceeds the %d frames forward(x, lengths) takes: the masks live in the "
-                             "fused kernels, whose graph module keeps at most %d temporal nodes (%d frames each) per utterance in LDS"
-                             % (max(frames), hi, max_nodes(self.pool_cfg), POOL))
+        frames = check_frames(feats, frames, max_frames(self.pool_cfg),
+                              "forward(x, lengths) takes: the masks live in the fused kernels, whose graph module keeps at most %d temporal "
+                              "nodes (%d frames each) per utterance in LDS" % (max_nodes(self.pool_cfg), POOL))
         counts = node_counts(frames, self.pool_cfg)
         w_max = max(counts["W"])
         # only the batch's longest utterance sizes the maps, whatever T the batch was padded to
@@ -278,15 +287,16 @@ class AasistHead(nn.Module):
 
     def forward_frames_long(self, feats, frames):
         """forward_frames for utterances of up to aasist_long.MAX_FRAMES = 3074 frames (1024 temporal nodes): the same contract on the
-        per-layer composition with count tables (aasist_long.py), independent of SCL_AASIST_FUSED / SCL_AASIST_FUSED_GRAPH."""
+        per-layer composition with count tables in its scoring mode (aasist_long.py), independent of SCL_AASIST_FUSED /
+        SCL_AASIST_FUSED_GRAPH."""
         from . import aasist_long
         return aasist_long.forward_frames_long(self, feats, frames)
 
     def forward_frames_train(self, feats, frames):
         """Train mode with autograd on, on a zero-padded batch with host-side frame counts (min_frames() .. aasist_long.MAX_FRAMES): the
-        count-table per-layer composition with batch statistics over the batch's own positions and an exact backward
-        (aasist_long.forward_frames_train), at every length and independent of SCL_AASIST_FUSED / SCL_AASIST_FUSED_GRAPH.  Batch statistics
-        couple the rows: a row is not what its utterance gets alone."""
+        same count-table composition in its training mode (aasist_long.py), with batch statistics over the batch's own positions and an
+        exact backward, at every length and independent of SCL_AASIST_FUSED / SCL_AASIST_FUSED_GRAPH.  Batch statistics couple the rows: a
+        row is not what its utterance gets alone."""
         from . import aasist_long
         return aasist_long.forward_frames_train(self, feats, frames)
 

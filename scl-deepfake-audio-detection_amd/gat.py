@@ -20,6 +20,26 @@ from . import ops
 # 960,000-sample clip): beyond this it is a ValueError, not an allocator failure in the middle of a backward.
 MAX_DP_BYTES = 16 << 30
 
+
+def _score_backward(x, W, ds, na, who, n, launch):
+    """What the two pair-score backwards share around their one launch: the refusal of a scratch beyond MAX_DP_BYTES (`who`, `n`: the
+    message's own words), the scratch, launch(ds, dP, part, dx, B, N, D, Do), the column reduce -> (dx, dW, db, da[:na])."""
+    B, N, D = x.shape
+    Do = W.shape[0]
+    nb = ops.gat_score_nblocks(N) * B
+    ncol = Do * D + 4 * Do
+    if B * N * N * D * 4 > MAX_DP_BYTES:
+        raise ValueError("%s backward: the pair-gradient scratch dP [B=%d, %s=%d, %s, D=%d] f32 is %.1f GiB, above the %d GiB bound "
+                         "(MAX_DP_BYTES); use a smaller batch" % (who, B, n, N, n, D, B * N * N * D * 4 / 2 ** 30, MAX_DP_BYTES >> 30))
+    dP = torch.empty(B * N * N * D, device=x.device, dtype=torch.float32)
+    part = torch.empty(nb, ncol, device=x.device, dtype=torch.float32)
+    dx = torch.empty_like(x)
+    launch(ds.contiguous().float(), dP, part, dx, B, N, D, Do)
+    red = torch.empty(ncol, device=x.device, dtype=torch.float32)
+    ops.colreduce(part, red, nb, ncol)
+    return dx, red[: Do * D].view(Do, D), red[Do * D: Do * D + Do], red[Do * D + Do:].view(3, Do)[:na]
+
+
 class _GatScoreFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, bias, a, n1):
@@ -37,23 +57,8 @@ class _GatScoreFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ds):
         x, W, bias, a3 = ctx.saved_tensors
-        B, N, D = x.shape
-        Do = W.shape[0]
-        nb = ops.gat_score_nblocks(N) * B
-        ncol = Do * D + 4 * Do
-        if B * N * N * D * 4 > MAX_DP_BYTES:
-            raise ValueError("gat_score backward: the pair-gradient scratch dP [B=%d, N=%d, N, D=%d] f32 is %.1f GiB, above the %d GiB bound "
-                             "(MAX_DP_BYTES); use a smaller batch" % (B, N, D, B * N * N * D * 4 / 2 ** 30, MAX_DP_BYTES >> 30))
-        dP = torch.empty(B * N * N * D, device=x.device, dtype=torch.float32)
-        part = torch.empty(nb, ncol, device=x.device, dtype=torch.float32)
-        dx = torch.empty_like(x)
-        ops.gat_score_bwd(x, W, bias, a3, ds.contiguous().float(), dP, part, dx, B, N, D, Do, ctx.n1)
-        red = torch.empty(ncol, device=x.device, dtype=torch.float32)
-        ops.colreduce(part, red, nb, ncol)
-        dW = red[: Do * D].view(Do, D)
-        db = red[Do * D: Do * D + Do]
-        da = red[Do * D + Do:].view(3, Do)[: ctx.na]
-        return dx, dW, db, da, None
+        return _score_backward(x, W, ds, ctx.na, "gat_score", "N", lambda ds, dP, part, dx, *dims: ops.gat_score_bwd(
+            x, W, bias, a3, ds, dP, part, dx, *dims, ctx.n1)) + (None,)
 
 
 class _GatScoreVarFn(torch.autograd.Function):
@@ -75,23 +80,8 @@ class _GatScoreVarFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ds):
         x, W, bias, a3, nodes, n1 = ctx.saved_tensors
-        B, N, D = x.shape
-        Do = W.shape[0]
-        nb = ops.gat_score_nblocks(N) * B
-        ncol = Do * D + 4 * Do
-        if B * N * N * D * 4 > MAX_DP_BYTES:
-            raise ValueError("gat_score_var backward: the pair-gradient scratch dP [B=%d, Nmax=%d, Nmax, D=%d] f32 is %.1f GiB, above the %d GiB "
-                             "bound (MAX_DP_BYTES); use a smaller batch" % (B, N, D, B * N * N * D * 4 / 2 ** 30, MAX_DP_BYTES >> 30))
-        dP = torch.empty(B * N * N * D, device=x.device, dtype=torch.float32)
-        part = torch.empty(nb, ncol, device=x.device, dtype=torch.float32)
-        dx = torch.empty_like(x)
-        ops.gat_score_bwd_var(x, W, bias, a3, ds.contiguous().float(), dP, part, dx, nodes, n1, B, N, D, Do)
-        red = torch.empty(ncol, device=x.device, dtype=torch.float32)
-        ops.colreduce(part, red, nb, ncol)
-        dW = red[: Do * D].view(Do, D)
-        db = red[Do * D: Do * D + Do]
-        da = red[Do * D + Do:].view(3, Do)[: ctx.na]
-        return dx, dW, db, da, None, None
+        return _score_backward(x, W, ds, ctx.na, "gat_score_var", "Nmax", lambda ds, dP, part, dx, *dims: ops.gat_score_bwd_var(
+            x, W, bias, a3, ds, dP, part, dx, nodes, n1, *dims)) + (None, None)
 
 
 def gat_score_var(x, W, bias, a, nodes, n1=None):

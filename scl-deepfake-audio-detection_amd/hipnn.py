@@ -290,35 +290,46 @@ class _BatchNormFn(torch.autograd.Function):
         return (dx,) + ((None, None) if acc else (dg, db)) + (None,) * 8
 
 
-class _BatchNormMaskedFn(torch.autograd.Function):
-    """Train-mode BatchNorm + activation over the valid rows of a zero-padded variable-length batch (scl_bn_fwd_masked / scl_bn_bwd_masked)."""
+class _BatchNormOwnFn(torch.autograd.Function):
+    """Train-mode BatchNorm + activation over the own positions of a zero-padded variable-length batch x [B, H, W, C]: the rows
+    h < own[b] (scl_bn_fwd_masked / scl_bn_bwd_masked), or with `cols` the columns w < own[b] (scl_bn_fwd_cols / scl_bn_bwd_cols)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, nbt, momentum, eps, act, grad_in_place, valid, counts):
+    def forward(ctx, x, weight, bias, running_mean, running_var, nbt, momentum, eps, act, grad_in_place, cols, own, counts):
         B, H, W, C = x.shape
         xc = x.contiguous().float()
         dev = x.device
         part = torch.empty(ops.bn_masked_nslabs(B, H, W) * 2 * C, dtype=torch.float64, device=dev)
         mean, rstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
         y = torch.empty_like(xc)
-        ops.bn_fwd_masked(xc, B, H, W, C, weight, bias, running_mean, running_var, nbt, momentum, eps, act, valid, counts, part, mean, rstd, y)
-        ctx.save_for_backward(xc, y, mean, rstd, weight, valid)
-        ctx.cfg = (B, H, W, C, act, weight is not None, bias is not None, counts)
+        fwd = ops.bn_fwd_cols if cols else ops.bn_fwd_masked
+        fwd(xc, B, H, W, C, weight, bias, running_mean, running_var, nbt, momentum, eps, act, own, counts, part, mean, rstd, y)
+        ctx.save_for_backward(xc, y, mean, rstd, weight, own)
+        ctx.cfg = (B, H, W, C, act, weight is not None, bias is not None, cols, counts)
         ctx.in_place = (weight, bias) if grad_in_place else None
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        xc, y, mean, rstd, weight, valid = ctx.saved_tensors
-        B, H, W, C, act, has_w, has_b, counts = ctx.cfg
+        xc, y, mean, rstd, weight, own = ctx.saved_tensors
+        B, H, W, C, act, has_w, has_b, cols, counts = ctx.cfg
         dev = dy.device
         dyc = dy.contiguous().float()
         part = torch.empty(ops.bn_masked_nslabs(B, H, W) * 2 * C, dtype=torch.float64, device=dev)
         sums = torch.empty(2 * C + 4, device=dev)
         dx = torch.empty_like(xc)
         dg, db, acc = _bn_param_grads(ctx, C, dev, has_w, has_b)
-        ops.bn_bwd_masked(dyc, y, xc, mean, rstd, weight, B, H, W, C, act, valid, counts, part, sums, dg, db, dx, accumulate=acc)
-        return (dx,) + ((None, None) if acc else (dg, db)) + (None,) * 9
+        bwd = ops.bn_bwd_cols if cols else ops.bn_bwd_masked
+        bwd(dyc, y, xc, mean, rstd, weight, B, H, W, C, act, own, counts, part, sums, dg, db, dx, accumulate=acc)
+        return (dx,) + ((None, None) if acc else (dg, db)) + (None,) * 10
+
+
+def _batch_norm_own(x, bn, act, grad_in_place, cols, own, counts):
+    if counts is None:
+        counts = own.tolist()
+    momentum = 0.1 if bn.momentum is None else bn.momentum
+    return _BatchNormOwnFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, momentum, bn.eps, act,
+                                 grad_in_place, cols, own, tuple(int(v) for v in counts))
 
 
 def batch_norm(x, bn, act=ACT_NONE, grad_in_place=False, valid=None, counts=None):
@@ -336,11 +347,7 @@ def batch_norm(x, bn, act=ACT_NONE, grad_in_place=False, valid=None, counts=None
         if x.dim() != 4:
             raise ValueError("hipnn.batch_norm: `valid` needs a [B, H, W, C] map, got %r" % (tuple(x.shape),))
         if training and torch.is_grad_enabled():
-            if counts is None:
-                counts = valid.tolist()
-            momentum = 0.1 if bn.momentum is None else bn.momentum
-            return _BatchNormMaskedFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, momentum, bn.eps,
-                                            act, grad_in_place, valid, tuple(int(v) for v in counts))
+            return _batch_norm_own(x, bn, act, grad_in_place, False, valid, counts)
         if training or torch.is_grad_enabled():
             raise NotImplementedError("hipnn.batch_norm: `valid` is a scoring mode (a BatchNorm in eval mode under torch.no_grad()); "
                                       "batch statistics over the valid positions and a backward are not implemented")
@@ -369,37 +376,6 @@ def batch_norm_cols(x, bn, act, widths):
     return y
 
 
-class _BatchNormColsFn(torch.autograd.Function):
-    """Train-mode BatchNorm + activation over the own columns of a zero-padded variable-length batch (scl_bn_fwd_cols / scl_bn_bwd_cols)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, nbt, momentum, eps, act, grad_in_place, widths, counts):
-        B, H, W, C = x.shape
-        xc = x.contiguous().float()
-        dev = x.device
-        part = torch.empty(ops.bn_masked_nslabs(B, H, W) * 2 * C, dtype=torch.float64, device=dev)
-        mean, rstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
-        y = torch.empty_like(xc)
-        ops.bn_fwd_cols(xc, B, H, W, C, weight, bias, running_mean, running_var, nbt, momentum, eps, act, widths, counts, part, mean, rstd, y)
-        ctx.save_for_backward(xc, y, mean, rstd, weight, widths)
-        ctx.cfg = (B, H, W, C, act, weight is not None, bias is not None, counts)
-        ctx.in_place = (weight, bias) if grad_in_place else None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        xc, y, mean, rstd, weight, widths = ctx.saved_tensors
-        B, H, W, C, act, has_w, has_b, counts = ctx.cfg
-        dev = dy.device
-        dyc = dy.contiguous().float()
-        part = torch.empty(ops.bn_masked_nslabs(B, H, W) * 2 * C, dtype=torch.float64, device=dev)
-        sums = torch.empty(2 * C + 4, device=dev)
-        dx = torch.empty_like(xc)
-        dg, db, acc = _bn_param_grads(ctx, C, dev, has_w, has_b)
-        ops.bn_bwd_cols(dyc, y, xc, mean, rstd, weight, B, H, W, C, act, widths, counts, part, sums, dg, db, dx, accumulate=acc)
-        return (dx,) + ((None, None) if acc else (dg, db)) + (None,) * 9
-
-
 def batch_norm_cols_train(x, bn, act, widths, counts=None, grad_in_place=False):
     """Train-mode BatchNorm + `act` of x [B, H, W, C] with autograd on and the mask on the COLUMNS: utterance b owns w < widths[b] (int32 [B]
     on the GPU) of every row.  Mean and biased variance over the batch's own positions only (N_v = H * sum widths), the running statistics
@@ -412,11 +388,7 @@ def batch_norm_cols_train(x, bn, act, widths, counts=None, grad_in_place=False):
     if not training or not torch.is_grad_enabled() or x.dim() != 4:
         raise NotImplementedError("hipnn.batch_norm_cols_train: a BatchNorm in train mode with autograd on, on a [B, H, W, C] map "
                                   "(scoring: hipnn.batch_norm_cols)")
-    if counts is None:
-        counts = widths.tolist()
-    momentum = 0.1 if bn.momentum is None else bn.momentum
-    return _BatchNormColsFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, momentum, bn.eps, act,
-                                  grad_in_place, widths, tuple(int(v) for v in counts))
+    return _batch_norm_own(x, bn, act, grad_in_place, True, widths, counts)
 
 
 class _ZeroColsFn(torch.autograd.Function):

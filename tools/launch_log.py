@@ -7,12 +7,15 @@ included — and every address as the index of its first appearance in the secti
 outputs are equal (both on the same libscl_hip.so, SCL_LIB_PATH); the "# counts" lines give calls / scalar / address arguments.
 Python's cyclic collector is off while a case runs: when it runs depends on how many container objects the host code has allocated, and
 it decides when a temporary held in a reference cycle goes back to torch's caching allocator, that is, which later buffer aliases it.
+The head-level cases (aasist-long, aasist-train-lengths: the AASIST back-end alone on zero-padded batches, which records no plan) print every
+step's calls and then a SHA-256 of each output, d(feats), parameter gradient and buffer: equal digests are equal bits.
 
-    python tools/launch_log.py [--cases small,other,resnet,aasist,btse,xlsr] > launches.txt
+    python tools/launch_log.py [--cases small,other,resnet,aasist,aasist-long,aasist-train-lengths,btse,xlsr] > launches.txt
 """
 import argparse
 import ctypes
 import gc
+import hashlib
 import os
 import sys
 
@@ -88,8 +91,8 @@ def run(title, model, step):
         gc.enable()
 
 
-def _run(title, model, step):
-    torch.manual_seed(0)
+def log_calls(step):
+    """step() under the wrapped ops._call: every launch printed in issue order, then the counts; what step returned."""
     first, real = Canon(), ops._call
 
     def logged(name, *args, keep=None):
@@ -99,10 +102,16 @@ def _run(title, model, step):
         return e
     ops._call = logged
     try:
-        step()
+        out = step()
     finally:
         ops._call = real
     print(first.counts())
+    return out
+
+
+def _run(title, model, step):
+    torch.manual_seed(0)
+    log_calls(step)
     step()
     torch.cuda.synchronize()
     k = 0
@@ -203,6 +212,73 @@ def case_aasist(dev):
     run("aasist tiny 4x20000 train", m, train(m, batch(4, 20000)))
 
 
+def run_head(title, head, steps):
+    """The back-end alone, no recorded plans: every step under the wrapped ops._call, then a SHA-256 of every tensor the step returned, of
+    every parameter gradient and of every buffer of the head."""
+    gc.collect()
+    gc.disable()
+    try:
+        for i, step in enumerate(steps):
+            print("== %s: step %d" % (title, i))
+            out = log_calls(step)
+            torch.cuda.synchronize()
+            out.update({"grad " + k: p.grad for k, p in head.named_parameters() if p.grad is not None})
+            out.update({"buffer " + k: v for k, v in head.named_buffers()})
+            for k, v in out.items():
+                print("sha256 %s %s" % (hashlib.sha256(v.detach().cpu().contiguous().numpy().tobytes()).hexdigest(), k))
+            for p in head.parameters():
+                p.grad = None
+    finally:
+        gc.enable()
+
+
+def aasist_head(dev):
+    """tests/test_aasist_varlen_long_gpu.py's head: the upstream configuration filled by oracle.aasist.fill_state, seed 3."""
+    from oracle.aasist import fill_state
+    from scl_amd.aasist_head import AasistHead
+    head = AasistHead()
+    sd = fill_state({k: tuple(v.shape) for k, v in head.state_dict().items()}, seed=3)
+    head.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    return head.to(dev)
+
+
+def case_aasist_long(dev):
+    """Scoring on the count-table composition: 390 frames = 130 nodes (the first tiled pair-score size), 283 the first beyond the fused stack,
+    two short rows; NaN in the padding."""
+    frames, T = [390, 283, 100, 3], 400
+    gen = torch.Generator().manual_seed(110)
+    feats = torch.full((len(frames), T, 128), float("nan"))
+    for b, n in enumerate(frames):
+        feats[b, :n] = torch.randn(n, 128, generator=gen)
+    feats, head = feats.to(dev), aasist_head(dev).eval()
+
+    def step():
+        with torch.no_grad():
+            return dict(zip(("logits", "last_hidden"), head.forward_frames_long(feats, frames)))
+    run_head("aasist-long %r padded to %d" % (frames, T), head, [step])
+
+
+def case_aasist_train_lengths(dev):
+    """Training on the count-table composition, dropout on: tests/aasist_train_cases.py's ragged batches (780 frames: 260 nodes, the tiled
+    backward), two steps each with its inputs and cotangents."""
+    from tests import aasist_train_cases as AC
+    for case in sorted(AC.HEAD_RAGGED):
+        frames = AC.HEAD_RAGGED[case][0]
+        B, T = len(frames), max(frames)
+        head = aasist_head(dev).train()
+        torch.manual_seed(0)
+
+        def step(i):
+            x = AC.head_input(i, B, T)
+            for b, n in enumerate(frames):
+                x[b, n:] = float("nan")
+            x = x.to(dev).requires_grad_(True)
+            out, hid = head.forward_frames_train(x, frames)
+            torch.autograd.backward([out, hid], [g.float().to(dev) for g in AC.head_cotangents(i, B)])
+            return {"logits": out, "last_hidden": hid, "d(feats)": x.grad}
+        run_head("aasist-train-lengths %r" % (frames,), head, [lambda i=i: step(i) for i in range(2)])
+
+
 def case_btse(dev):
     import numpy as np
     from oracle import btse as OB
@@ -223,11 +299,11 @@ def case_xlsr(dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cases", default="small,other,resnet,aasist,btse,xlsr")
+    ap.add_argument("--cases", default="small,other,resnet,aasist,aasist-long,aasist-train-lengths,btse,xlsr")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     for name in args.cases.split(","):
-        globals()["case_" + name](torch.device("cuda:0"))
+        globals()["case_" + name.replace("-", "_")](torch.device("cuda:0"))
         torch.cuda.empty_cache()
 
 
