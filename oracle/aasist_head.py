@@ -160,6 +160,10 @@ class AasistHead(nn.Module):
         w = self.attention(x)
         e_S = (x * F.softmax(w, dim=-1)).sum(-1).transpose(1, 2) + self.pos_S      # spectral nodes  [B, 42, 64]
         e_T = (x * F.softmax(w, dim=-2)).sum(-2).transpose(1, 2)                   # temporal nodes  [B, T/3, 64]
+        return AasistHead.graph(self, e_S, e_T)      # unbound: forward is also called on modules that only carry this class's attributes
+
+    def graph(self, e_S, e_T):
+        """The graph module alone: spectral nodes e_S [B, 42, 64], temporal nodes e_T [B, T/3, 64] -> (logits, last_hidden)."""
         out_S = self.pool_S(self.GAT_layer_S(e_S))
         out_T = self.pool_T(self.GAT_layer_T(e_T))
         # two heterogeneous branches
